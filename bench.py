@@ -24,6 +24,16 @@ that cannot be started, N thread ranks of this process over the library's peer-t
 library at all).  `--launcher processes|threads` forces one.  Under an external launcher
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`) it is one of the ranks, as before.  Rank 0 prints ONE JSON
 line, the last line of stdout.
+
+Plain run and --full.  A plain run does what the headline needs and nothing else: set up, --warmup proofs, --steps timed proofs,
+the outputs if --dump-outputs is given, the line (metric, value, unit, higher_is_better, dtype, ms_per_step and what the run was).
+--full adds everything else the line reports, as before: the CPU baseline (and parity against its proof), the HIP-event sample of the
+timed steps behind the roofline and multiplier figures, the communicator's exchange timing and the scaling model's prediction at N > 1,
+the host-tables end-to-end proofs, and --min-gpu-seconds of untimed proofs after the clock (default 10 s under --full, 0 otherwise).
+
+--dump-outputs DIR writes the proof the LAST timed step returned (nv rounds x D evaluations, each a BLS12-381 Fr element as four
+little-endian uint64 Montgomery limbs, as sc_ml_prove returns it) to DIR/proof.npy: float64, shape (nv, D, 8), every limb split into
+its low and high 32-bit halves, so the values are exact.  The tables are seed-defined: the same arguments give the same inputs.
 """
 import argparse
 import ctypes as C
@@ -108,6 +118,16 @@ def round_bytes(nv_local, n_tables, i):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the proof (nv, D, 4) uint64 -> out_dir/proof.npy, float64 (nv, D, 8): limb j's low half at 2j, its high half at 2j+1"""
+    p = np.ascontiguousarray(proof, dtype=np.uint64)
+    halves = np.stack([p & np.uint64(0xFFFFFFFF), p >> np.uint64(32)], axis=-1).reshape(p.shape[:-1] + (2 * p.shape[-1],))
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "proof.npy")
+    np.save(path, halves.astype(np.float64))
+    return path
 
 
 def cpu_model():
@@ -462,7 +482,7 @@ def run_rank(args, W, result):
     # instance the GPUs prove (config 3, strong scaling: the metric as worded) its proof is kept and the GPU proofs are compared with it.
     force_sharded = os.environ.get("SC_BENCH_FORCE_SHARDED") == "1"  # exercise the N>1 code path on one GPU (tests)
     cpu, cpu_proof_nv, cpu_proof = None, 0, None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             cpu, (cpu_proof_nv, cpu_proof) = cpu_baseline(shapes, U, nv_full=min(nv_total, 24))
         except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
@@ -523,7 +543,7 @@ def run_rank(args, W, result):
         if box["python"] and not isinstance(W, ProcWorld):
             raise RuntimeError(f"thread ranks have no torch.distributed fallback: {box['why']}")
         log(f"[bench] rank {rank}: round loop = {'torch.distributed (fallback)' if box['python'] else round_loop} -- {box['why']}")
-        if not box["python"]:
+        if not box["python"] and args.full:
             # the per-round exchange on its own: back-to-back all-reduces of one round message (D x 8 lanes = 320 bytes for degree 4) in
             # the form a sharded round uses on this communicator, each waited for by the host like a round's
             # (a rank whose measurement raised must not skip a collective its peers enter: every rank agrees on the outcome first)
@@ -573,6 +593,7 @@ def run_rank(args, W, result):
     # The dominant kernel's duration is measured live, with HIP events on the launch stream inside the timed region -- on a sample of
     # the steps only: the events are instrumentation (four records and a collect per big round, ~3 % of a proof: gpu_leg.ms_per_event_sampled_proof), and the other steps
     # run as a caller's proofs do.  At least 4 steps are sampled whatever --steps is (kernel durations repeat to a percent).  The sampled steps are part of the K timed steps.
+    # Only under --full: in a plain run every timed step is a caller's proof.
     K = len(shapes)
     ms_acc, ln_acc, rounds_ms_acc, timed_steps = [0.0] * K, [0] * K, 0.0, 0
     rms_acc, rln_acc = [0.0] * nv_local, [0] * nv_local
@@ -586,7 +607,7 @@ def run_rank(args, W, result):
     t0 = time.perf_counter()
     step_s = []  # a step returns when its last round's message is on the host, so per-step wall times cost nothing extra
     for i in range(args.steps):
-        sampled = i % every == 0
+        sampled = args.full and i % every == 0
         if sampled:
             _lib.check(sc.lib().sc_prover_set_timing(handle, 1))
         ts = time.perf_counter()
@@ -614,10 +635,13 @@ def run_rank(args, W, result):
     # message, with the CPU proof, on every rank.  Elsewhere (weak scaling, config 4: no CPU proof of the instance exists) the proof
     # certifies itself the way the reference's own tests do (ml_sumcheck/test.rs:71-74): the verifier accepts every round and its
     # final oracle query is answered from the sharded tables.
-    have_cpu_proof = cpu_proof is not None and cpu_proof_nv == nv_total
-    all_have = W.any(have_cpu_proof)  # rank 0 decides (it alone ran the CPU leg)
-    parity = {"vs": None, "ok": None, "reason": "no CPU proof of this instance in this run (--no-cpu-baseline, or the CPU sample stopped below the full size)"}
+    # A plain run checks nothing here (--full does).
     timed_proof = np.asarray(proof, dtype=np.uint64).reshape(nv_total, D, 4)
+    if args.dump_outputs and rank == 0:  # (every rank holds the same proof)
+        log(f"[bench] outputs of the last timed step: {dump_outputs(args.dump_outputs, timed_proof)}")
+    have_cpu_proof = cpu_proof is not None and cpu_proof_nv == nv_total
+    all_have = args.full and W.any(have_cpu_proof)  # rank 0 decides (it alone ran the CPU leg)
+    parity = {"vs": None, "ok": None, "reason": "no CPU proof of this instance in this run (--no-cpu-baseline, or the CPU sample stopped below the full size)"}
     if all_have:
         after = np.asarray(step(), dtype=np.uint64).reshape(nv_total, D, 4)
         torch.cuda.synchronize(dev)
@@ -630,7 +654,7 @@ def run_rank(args, W, result):
                             + (f"; the proofs of all {world} ranks" if world > 1 else ""),
                       "rounds_equal": int(sum(eq_t)), "rounds_equal_after_timed_region": int(sum(eq_a)), "rounds": nv_total,
                       "ranks_compared": len(both), "ok": bool(all(eq_t) and all(eq_a))}
-    elif sharded_path:
+    elif sharded_path and args.full:
         try:
             from sumcheck_amd import field
             msgs = [sc.ProverMsg(np.asarray(m, dtype=np.uint64).reshape(-1, 4)) for m in timed_proof]
@@ -673,7 +697,7 @@ def run_rank(args, W, result):
         torch.cuda.synchronize(dev)
 
     e2e = None
-    if rank == 0 and not sharded_path and not args.no_end_to_end and nv_local <= 24:
+    if rank == 0 and args.full and not sharded_path and not args.no_end_to_end and nv_local <= 24:
         try:
             e2e = end_to_end(sc, _lib, torch, tables, shapes, coefs, nv_local, dev, timed_proof)
         except Exception as e:  # a report beside the line, never a reason to lose it
@@ -688,6 +712,23 @@ def run_rank(args, W, result):
     if rank == 0:
         ops = field_ops(nv_total, shapes, U)
         value = ops * args.steps / elapsed
+        ms_step = elapsed / args.steps * 1e3
+        cfg_name = ("BASELINE config 4" if args.config == 4 else "BASELINE config 3") + (f", {scaling} scaling" if world > 1 else "")
+        out = {
+            "metric": "MLSumcheck prover field-ops/s (BLS12-381 Fr, nv=24)" if args.config == 3 else "MLSumcheck prover field-ops/s (BLS12-381 Fr, nv=28, config 4)",
+            "value": value, "unit": "field-ops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_step, "ms_per_step_median": float(np.median(step_s)) * 1e3, "ms_per_step_min": min(step_s) * 1e3,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+            "dtype": "u256 (BLS12-381 Fr, Montgomery form; integer arithmetic on 9 x 29-bit limbs)", "data": "synthetic",
+            "config": {"workload": f"{cfg_name}: MLSumcheck prove, ListOfProducts {shapes} over {U} tables, nv={nv_total}"
+                                   f" ({nv_local} per GPU shard), BLS12-381 Fr, tables HBM-resident",
+                       "nv": nv_total, "nv_per_gpu": nv_local, "tables": U, "degree": max(len(s) for s in shapes),
+                       "field_ops_per_step": ops, "sharding": f"high-bit x{world}" if world > 1 else "none",
+                       "launcher": W.launcher, "ranks_seen": ranks_seen, "communicator": comm_kind,
+                       "round_loop": round_loop, "round_loop_reason": box["why"], "policy": args.policy},
+        }
+        result["line"] = out
+    if rank == 0 and args.full:  # everything beside the headline
         # dominant kernel: the merged big-round launch (every product of the round, one product per block row), launched once per BIG
         # round (more than 2^14 pairs on this GPU; later rounds are latency-bound and run through the small-round kernels).
         # Algorithmic bytes of those launches: round 1 reads the tables once; round i >= 2 reads T_{i-1} and writes T_i.
@@ -756,78 +797,63 @@ def run_rank(args, W, result):
         # rounds_ms: event span of the rounds launched with events = the big rounds (late rounds are pipelined and record none)
         big_all_bytes = sum(round_bytes(nv_local, U, i) for i in big_idx)
         big_rounds_gbps = big_all_bytes * ev_steps / (rounds_ms_total * 1e-3) / 1e9 if rounds_ms_total > 0 else 0.0
-        ms_step = elapsed / args.steps * 1e3
         whole_gbps = algorithmic_bytes(nv_local, U) * args.steps / elapsed / 1e9
         big_kernels_ms = sum(r["ms"] for r in per_round)
         pred = predict_ms(args.config, nv_total, world, U, comm_kind, (exchange or {}).get("exchange_us"))
         pred["measured_over_predicted"] = ms_step / pred["predicted_ms_per_step"]
-        cfg_name = ("BASELINE config 4" if args.config == 4 else "BASELINE config 3") + (f", {scaling} scaling" if world > 1 else "")
         ref_muls = reference_muls(nv_total, shapes, U)
         exe = executed_products(nv_local, shapes, U) * world + (executed_products(k, shapes, U) if k else 0)
-        out = {
-            "metric": "MLSumcheck prover field-ops/s (BLS12-381 Fr, nv=24)" if args.config == 3 else "MLSumcheck prover field-ops/s (BLS12-381 Fr, nv=28, config 4)",
-            "value": value, "unit": "field-ops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "ms_per_step_median": float(np.median(step_s)) * 1e3, "ms_per_step_min": min(step_s) * 1e3,
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "u256 (BLS12-381 Fr, Montgomery form; integer arithmetic on 9 x 29-bit limbs)", "data": "synthetic",
-            "config": {"workload": f"{cfg_name}: MLSumcheck prove, ListOfProducts {shapes} over {U} tables, nv={nv_total}"
-                                   f" ({nv_local} per GPU shard), BLS12-381 Fr, tables HBM-resident",
-                       "nv": nv_total, "nv_per_gpu": nv_local, "tables": U, "degree": max(len(s) for s in shapes),
-                       "field_ops_per_step": ops, "sharding": f"high-bit x{world}" if world > 1 else "none",
-                       "launcher": W.launcher, "ranks_seen": ranks_seen, "communicator": comm_kind, "exchange": exchange,
-                       "round_loop": round_loop, "round_loop_reason": box["why"], "policy": args.policy,
-                       # the scaling model's figure for THIS line, written down before any N > 1 hardware run: the line tests it
-                       "end_to_end": e2e,
-                       "predicted_ms_per_step": pred["predicted_ms_per_step"], "exchange_assumed_us": pred.get("exchange_assumed_us"), "prediction": pred,
-                       "gpu_leg": {"warmup_proofs": args.warmup, "timed_proofs": args.steps, "proofs_after_the_clock": cooldown + (1 if all_have else 0),
-                                   "event_sampled_proofs": timed_steps,
-                                   "ms_per_event_sampled_proof": float(np.mean([t for i, t in enumerate(step_s) if i % every == 0])) * 1e3,
-                                   "ms_per_other_proof": float(np.mean([t for i, t in enumerate(step_s) if i % every != 0] or [float("nan")])) * 1e3,
-                                   "gpu_leg_seconds_target": args.min_gpu_seconds,
-                                   "note": "the proofs after the clock keep the GPU busy for --min-gpu-seconds in all (an outside activity sampler with a 5 s period sees the run); they are not timed"}},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "traffic": traffic, "traffic_source": traffic_source, "kernel": (f"k_round1_tree_split (round 1) + k_round_tree_split (rounds 2..{big_rounds}): all products, one launch per big round, one product per block row" if merged
-                                    else f"{kname} (product {dom}, big rounds)"),
-                         "avg_launch_ms": avg_ms, "launches": launches, "algorithmic_bytes_per_launch": bytes_per_launch,
-                         # where `achieved` / `frac` come from: the tracked rocprofv3 summary of this command on this tree when there is one
-                         # (recomputable from profiles/), else this run's HIP events; the HIP-event figures of THIS run are always here
-                         "frac_source": ("rocprofv3: " + rocprof_source) if rocprof else ("HIP events of this run (" + str(rocprof_source) + ")"),
-                         "achieved_hip_events": achieved_events, "frac_hip_events": achieved_events / HBM_PEAK_GBPS, "avg_launch_ms_hip_events": avg_ms_events,
-                         "rocprof": ({"avg_launch_ms": rocprof["avg_ns"] * 1e-6, "launches": rocprof["launches"], "proofs": rocprof.get("proofs"),
-                                      "avg_launch_ms_warm_proofs_only": rocprof["warm"]["avg_ns"] * 1e-6,
-                                      "frac_warm_proofs_only": (big_bytes / big_rounds) / (rocprof["warm"]["avg_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBPS,
-                                      "per_proof_kernel_total_ms": rocprof.get("per_proof_kernel_total_ms"),
-                                      "stats_csv": rocprof.get("stats_csv")} if rocprof else None),
-                         "per_round": per_round,
-                         "big_rounds_GBps_incl_finalize": big_rounds_gbps, "big_rounds_ms_per_step": rounds_ms_total / ev_steps,
-                         "event_timed_steps": timed_steps, "event_timed_every": every,
-                         # THE WHOLE PROOF against the same roof (the headline figure: every round, finalize launch and host turn-around
-                         # included; `frac` above is the dominant kernel's launches alone, as the contract defines it)
-                         "whole_proof_GBps": whole_gbps,  # per GPU
-                         "whole_proof_frac": whole_gbps / HBM_PEAK_GBPS,
-                         # what the proof pays beside its big-round kernels, per step: the finalize launches inside the big rounds' event span,
-                         # and everything outside it (host turn-around of the big rounds: flag over PCIe, hash, bind constants, launch; the
-                         # latency-bound rounds below 2^14 pairs).  ms_per_step = big_round_kernels_ms + fixed_cost_ms.
-                         "fixed_cost_ms": max(0.0, ms_step - big_kernels_ms),
-                         "fixed_cost": {"big_round_kernels_ms": big_kernels_ms,
-                                        "finalize_inside_big_rounds_ms": max(0.0, rounds_ms_total / ev_steps - big_kernels_ms),
-                                        "turnaround_and_latency_bound_rounds_ms": max(0.0, ms_step - rounds_ms_total / ev_steps),
-                                        "latency_bound_rounds": nv_total - big_rounds,
-                                        "bytes_at_whole_proof_rate_ms": algorithmic_bytes(nv_local, U) / (HBM_PEAK_GBPS * 1e9) * 1e3},
-                         "per_product_ms_per_step": [m / ev_steps for m in ms],
-                         # SURVEY 8d's second ceiling: multiplications against what the chip's multiplier can do.  reference_muls_per_s is
-                         # the reference ALGORITHM's count over the measured time (a throughput, not a utilisation: the kernels execute
-                         # fewer products -- nodes, product tree, claim identity); executed_products_per_s is what the kernels do execute
-                         # (binds weighted 97/153), and frac_executed sets that against the carry-free product's in-kernel ceiling.
-                         "multiplier": {"reference_muls_per_s": ref_muls * args.steps / elapsed,
-                                        "executed_products_per_s": exe * args.steps / elapsed,
-                                        "fe_mul_ceiling_per_s": FE_MUL_CEILING_PER_S * world,
-                                        "frac_executed": exe * args.steps / elapsed / (FE_MUL_CEILING_PER_S * world),
-                                        "executed_products_per_step": exe, "reference_muls_per_step": ref_muls}},
-            "cpu_baseline": cpu,
-            "parity": parity,
-        }
-        result["line"] = out
+        out["config"].update({
+            "exchange": exchange, "end_to_end": e2e,
+            # the scaling model's figure for THIS line, written down before any N > 1 hardware run: the line tests it
+            "predicted_ms_per_step": pred["predicted_ms_per_step"], "exchange_assumed_us": pred.get("exchange_assumed_us"), "prediction": pred,
+            "gpu_leg": {"warmup_proofs": args.warmup, "timed_proofs": args.steps, "proofs_after_the_clock": cooldown + (1 if all_have else 0),
+                        "event_sampled_proofs": timed_steps,
+                        "ms_per_event_sampled_proof": float(np.mean([t for i, t in enumerate(step_s) if i % every == 0])) * 1e3,
+                        "ms_per_other_proof": float(np.mean([t for i, t in enumerate(step_s) if i % every != 0] or [float("nan")])) * 1e3,
+                        "gpu_leg_seconds_target": args.min_gpu_seconds,
+                        "note": "the proofs after the clock keep the GPU busy for --min-gpu-seconds in all (an outside activity sampler with a 5 s period sees the run); they are not timed"}})
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                           "traffic": traffic, "traffic_source": traffic_source, "kernel": (f"k_round1_tree_split (round 1) + k_round_tree_split (rounds 2..{big_rounds}): all products, one launch per big round, one product per block row" if merged
+                                      else f"{kname} (product {dom}, big rounds)"),
+                           "avg_launch_ms": avg_ms, "launches": launches, "algorithmic_bytes_per_launch": bytes_per_launch,
+                           # where `achieved` / `frac` come from: the tracked rocprofv3 summary of this command on this tree when there is one
+                           # (recomputable from profiles/), else this run's HIP events; the HIP-event figures of THIS run are always here
+                           "frac_source": ("rocprofv3: " + rocprof_source) if rocprof else ("HIP events of this run (" + str(rocprof_source) + ")"),
+                           "achieved_hip_events": achieved_events, "frac_hip_events": achieved_events / HBM_PEAK_GBPS, "avg_launch_ms_hip_events": avg_ms_events,
+                           "rocprof": ({"avg_launch_ms": rocprof["avg_ns"] * 1e-6, "launches": rocprof["launches"], "proofs": rocprof.get("proofs"),
+                                        "avg_launch_ms_warm_proofs_only": rocprof["warm"]["avg_ns"] * 1e-6,
+                                        "frac_warm_proofs_only": (big_bytes / big_rounds) / (rocprof["warm"]["avg_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBPS,
+                                        "per_proof_kernel_total_ms": rocprof.get("per_proof_kernel_total_ms"),
+                                        "stats_csv": rocprof.get("stats_csv")} if rocprof else None),
+                           "per_round": per_round,
+                           "big_rounds_GBps_incl_finalize": big_rounds_gbps, "big_rounds_ms_per_step": rounds_ms_total / ev_steps,
+                           "event_timed_steps": timed_steps, "event_timed_every": every,
+                           # THE WHOLE PROOF against the same roof (the headline figure: every round, finalize launch and host turn-around
+                           # included; `frac` above is the dominant kernel's launches alone, as the contract defines it)
+                           "whole_proof_GBps": whole_gbps,  # per GPU
+                           "whole_proof_frac": whole_gbps / HBM_PEAK_GBPS,
+                           # what the proof pays beside its big-round kernels, per step: the finalize launches inside the big rounds' event span,
+                           # and everything outside it (host turn-around of the big rounds: flag over PCIe, hash, bind constants, launch; the
+                           # latency-bound rounds below 2^14 pairs).  ms_per_step = big_round_kernels_ms + fixed_cost_ms.
+                           "fixed_cost_ms": max(0.0, ms_step - big_kernels_ms),
+                           "fixed_cost": {"big_round_kernels_ms": big_kernels_ms,
+                                          "finalize_inside_big_rounds_ms": max(0.0, rounds_ms_total / ev_steps - big_kernels_ms),
+                                          "turnaround_and_latency_bound_rounds_ms": max(0.0, ms_step - rounds_ms_total / ev_steps),
+                                          "latency_bound_rounds": nv_total - big_rounds,
+                                          "bytes_at_whole_proof_rate_ms": algorithmic_bytes(nv_local, U) / (HBM_PEAK_GBPS * 1e9) * 1e3},
+                           "per_product_ms_per_step": [m / ev_steps for m in ms],
+                           # SURVEY 8d's second ceiling: multiplications against what the chip's multiplier can do.  reference_muls_per_s is
+                           # the reference ALGORITHM's count over the measured time (a throughput, not a utilisation: the kernels execute
+                           # fewer products -- nodes, product tree, claim identity); executed_products_per_s is what the kernels do execute
+                           # (binds weighted 97/153), and frac_executed sets that against the carry-free product's in-kernel ceiling.
+                           "multiplier": {"reference_muls_per_s": ref_muls * args.steps / elapsed,
+                                          "executed_products_per_s": exe * args.steps / elapsed,
+                                          "fe_mul_ceiling_per_s": FE_MUL_CEILING_PER_S * world,
+                                          "frac_executed": exe * args.steps / elapsed / (FE_MUL_CEILING_PER_S * world),
+                                          "executed_products_per_step": exe, "reference_muls_per_step": ref_muls}}
+        out["cpu_baseline"] = cpu
+        out["parity"] = parity
     W.finish()
     result.setdefault("parity_ok", {})[rank] = parity["ok"]
 
@@ -867,7 +893,7 @@ def run_threads(args):
         log("[bench] thread ranks failed:\n" + "\n".join(real))
         return 1
     print_line(result["line"])
-    if result["line"]["parity"]["ok"] is False:
+    if any(v is False for v in result.get("parity_ok", {}).values()):  # (a plain line carries no parity)
         log("[bench] PARITY FAILURE: the GPU proof differs from the CPU oracle's proof of the same instance")
         return 1
     return 0
@@ -928,6 +954,8 @@ def self_launch(args):
         s.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={N}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.abspath(__file__)] + sys.argv[1:]
+        if args.dump_outputs:  # (the ranks run in ROOT: a relative DIR means the caller's)
+            cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         log(f"[bench] --gpus {N} without a launcher: starting {N} ranks: {' '.join(cmd[1:9])} bench.py ...")
         env, full_mask = launcher_env()
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT, preexec_fn=full_mask)
@@ -966,11 +994,20 @@ def main():
                          "process over the library's peer-to-peer communicator; auto = processes, threads if that cannot start")
     ap.add_argument("--policy", action="append", default=[], metavar="KEY=VALUE",
                     help="sc_set_policy(KEY, VALUE) on every rank before anything else (include/sumcheck_hip.h lists the keys), e.g. --policy rccl_direct=0; repeatable")
-    ap.add_argument("--min-gpu-seconds", type=float, default=10.0,
-                    help="after the timed region, keep proving (untimed) until the GPU leg has lasted about this long; 0 = off")
+    ap.add_argument("--min-gpu-seconds", type=float, default=None,
+                    help="after the timed region, keep proving (untimed) until the GPU leg has lasted about this long; 0 = off (default: 10 with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: CPU baseline and parity, roofline / multiplier figures from HIP events, exchange timing "
+                         "and scaling prediction, end-to-end host-table proofs, --min-gpu-seconds of untimed proofs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's proof to DIR/proof.npy (float64 (nv, D, 8): 32-bit halves of the Montgomery limbs)")
     args = ap.parse_args()
     if args.gpus < 1 or args.gpus & (args.gpus - 1):
         ap.error("--gpus must be a power of two")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.min_gpu_seconds is None:
+        args.min_gpu_seconds = 10.0 if args.full else 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))

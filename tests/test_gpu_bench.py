@@ -20,7 +20,7 @@ def _last_json(out: str):
 
 
 def test_bench_line_single_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--nv", "19", "--min-gpu-seconds", "0.5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--nv", "19", "--min-gpu-seconds", "0.5"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -63,13 +63,42 @@ def test_bench_line_single_gpu():
         assert e["h2d_ms"] > 0 and e["staged_total_ms"] > 0 and e["copy_then_prove_total_ms"] > 0 and e["total_ms"] == e["staged_total_ms"]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full): the headline fields and nothing measured beside them; --dump-outputs writes the last timed step's proof,
+    which is the CPU oracle's proof of the same seed-defined instance"""
+    import numpy as np
+    from oracle import cref
+    nv = 16
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--nv", str(nv), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] - d["config"]["field_ops_per_step"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "parity"):
+        assert k not in d, k
+    assert not {"exchange", "end_to_end", "prediction", "gpu_leg"} & set(d["config"])
+    got = np.load(tmp_path / "proof.npy")
+    assert got.dtype == np.float64 and got.shape == (nv, 5, 8)
+    limbs = got.astype(np.uint64).reshape(nv, 5, 4, 2)
+    proof = limbs[..., 0] | (limbs[..., 1] << np.uint64(32))
+    seed = 0x5C20241008
+    shapes = [[0, 1, 2, 3], [4, 5, 6], [7, 8], [9]]
+    coefs = cref.synth_table(seed, 1000, len(shapes))
+    desc = cref.PolyDesc(nv, [(coefs[k], s) for k, s in enumerate(shapes)], [cref.synth_table(seed, u, 1 << nv) for u in range(10)])
+    want, _ = cref.ml_prove(desc, threads=cref.max_threads())
+    assert np.array_equal(proof, np.asarray(want, dtype=np.uint64).reshape(nv, 5, 4))
+
+
 def _two_ranks(extra, launcher=None, timeout=900):
     """launcher None: `python bench.py --gpus 2 ...` with NO launcher around it (the driver's command line); "external": under
     `python -m torch.distributed.run`; "threads" / "processes": the self-launch forced to one form"""
     env = dict(os.environ, SC_BENCH_ONE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--min-gpu-seconds", "0.5"] + extra
+    tail = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--min-gpu-seconds", "0.5"] + extra
     if launcher == "external":
         s = socket.socket()
         s.bind(("127.0.0.1", 0))
@@ -139,7 +168,7 @@ def test_bench_rccl_code_path_with_a_world_of_one():
     env = dict(os.environ, SC_BENCH_FORCE_SHARDED="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SC_BENCH_ONE_GPU"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nv", "19", "--steps", "2", "--warmup", "1", "--min-gpu-seconds", "0.5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--nv", "19", "--steps", "2", "--warmup", "1", "--min-gpu-seconds", "0.5"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -149,7 +178,7 @@ def test_bench_rccl_code_path_with_a_world_of_one():
     assert c["exchange"]["publication"].startswith("direct"), c["exchange"]  # the RCCL rounds run without a publish kernel (probed at sc_comm_init)
     assert d["parity"]["ok"] is True and d["parity"]["rounds_equal"] == 19, d["parity"]
     # ... and with sc_set_policy("rccl_direct", 0) through the publish kernel, to the same bits
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nv", "19", "--steps", "2", "--warmup", "1", "--min-gpu-seconds", "0.5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--nv", "19", "--steps", "2", "--warmup", "1", "--min-gpu-seconds", "0.5",
                         "--no-cpu-baseline", "--policy", "rccl_direct=0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d0 = json.loads(r.stdout.strip().splitlines()[-1])

@@ -286,6 +286,30 @@ def test_bench_refuses_a_multi_gpu_run_it_cannot_place():
     assert r.returncode == 2 and "power of two" in r.stderr
 
 
+def test_bench_refuses_a_run_without_timed_steps():
+    """--steps sets the number of timed steps: zero of them is an argument error, before any device is touched"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+
+def test_bench_dumped_proof_is_exact(tmp_path):
+    """--dump-outputs: the proof's uint64 limbs as float64 32-bit halves, every value exact and recoverable"""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(7)
+    proof = rng.integers(0, 1 << 63, size=(6, 5, 4), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    proof[0, 0] = [0, 1, 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF]
+    path = bench.dump_outputs(str(tmp_path / "out"), proof)
+    got = np.load(path)
+    assert path == str(tmp_path / "out" / "proof.npy") and got.dtype == np.float64 and got.shape == (6, 5, 8)
+    assert np.all(got == np.floor(got)) and got.min() >= 0 and got.max() <= 0xFFFFFFFF
+    halves = got.astype(np.uint64).reshape(6, 5, 4, 2)
+    assert np.array_equal(halves[..., 0] | (halves[..., 1] << np.uint64(32)), proof)
+
+
 def test_bench_scaling_model_is_consistent_with_the_sharded_schedule():
     """bench.py's predicted_ms_per_step: T1(nv per GPU) + one exchange per sharded round + the gather + log2(N) extra
     replicated rounds.  The round split it assumes is the library's (protocol.hip: sharded_tail_m, gather at 2^14 pairs): sharded and

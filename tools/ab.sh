@@ -7,7 +7,7 @@
 #          literal `exp` for the experiments build (SC_LIB_VARIANT=exp; combine with -e "SC_F29=0" and the like)
 #   -k     run this slice of the GPU parity suite on every LIB first (a variant that is not bit-exact is not a candidate)
 #   -w     what to time, comma separated (default bench,rounds):
-#            bench        python bench.py --no-cpu-baseline: ms per proof (mean, min), average big-round launch     [config 3, nv=24]
+#            bench        python bench.py --full --no-cpu-baseline: ms per proof (mean, min), average big-round launch [config 3, nv=24]
 #            rounds       tools/round_times.py 24: device and wall time per round   (-R "25 c4": other arguments, e.g. config 4's shard)
 #            small        tools/small_proofs.py: whole proofs at nv 8..16 (latency-bound rounds)                     [SC_SHAPE=c3|c2|gkr]
 #            configs      tools/bench_configs.py: BASELINE configs 2, README shape, 5                                (+ config 4 with configs4)
@@ -32,7 +32,7 @@ if [ -n "$K" ]; then
 fi
 for rep in $(seq 1 $REPS); do
   for L in "$@"; do
-    if has bench; then echo -n "bench $L  "; env $(libenv $L) timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$line"; fi
+    if has bench; then echo -n "bench $L  "; env $(libenv $L) timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$line"; fi
     if has small; then echo "small $L"; env $(libenv $L) timeout 300 python tools/small_proofs.py 2>&1 | grep "nv="; fi
     if has configs; then echo -n "configs $L  "; env $(libenv $L) timeout 600 python tools/bench_configs.py 2>/dev/null | grep -E "gpu_ms_median" | tr '\n' ' '; echo; fi
     if has configs4; then echo -n "configs4 $L  "; env $(libenv $L) timeout 900 python tools/bench_configs.py --config4 2>/dev/null | grep -E "gpu_ms_median" | tr '\n' ' '; echo; fi

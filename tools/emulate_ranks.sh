@@ -5,10 +5,10 @@ TAG=${1:?tag}
 cd "$(dirname "$0")/.."
 export SC_BENCH_ONE_GPU=1
 run() { name=$1; shift; timeout 900 python3 bench.py "$@" --steps 5 --warmup 2 --min-gpu-seconds 0 > gpurun_out/$name.json 2> gpurun_out/$name.err; echo "$name rc=$?"; }
-run ${TAG}_n2_proc --gpus 2
-run ${TAG}_n4_proc --gpus 4
-run ${TAG}_n8_threads --gpus 8 --launcher threads
-run ${TAG}_n8_c4_threads --gpus 8 --launcher threads --config 4
+run ${TAG}_n2_proc --full --gpus 2
+run ${TAG}_n4_proc --full --gpus 4
+run ${TAG}_n8_threads --full --gpus 8 --launcher threads
+run ${TAG}_n8_c4_threads --full --gpus 8 --launcher threads --config 4
 TAG=$TAG python3 - <<'PY'
 import json,glob,os
 print("# file  n_gpus  ms_per_step  predicted_ms_per_step(real N GPUs)  exchange_assumed_us  parity.ok  ranks_seen  communicator  publication  launcher")

@@ -28,6 +28,7 @@ echo "[scale_day] $NGPU visible GPUs, N in {$NS }, emulation=$EMU, $STEPS steps 
 
 run() { # name, bench.py arguments
   name=${TAG}_scale_$1; shift
+  set -- --full "$@"  # (each line carries its exchange timing, the scaling model's prediction and parity)
   timeout 1200 python3 bench.py "$@" --steps $STEPS --warmup 3 --min-gpu-seconds 0 --no-end-to-end > gpurun_out/$name.json 2> gpurun_out/$name.err
   echo "$name rc=$?"
 }
