@@ -315,6 +315,41 @@ struct MLSumcheck {
         for (size_t i = 0; i < nv; ++i) proof[i].evaluations.assign(flat.begin() + i * Dg, flat.begin() + (i + 1) * Dg);
         return proof;
     }
+    // n independent proofs of ONE structure (the same num_variables and product lists; tables and coefficients per instance) in one
+    // library call (sc_ml_prove_batch): what the reference's caller writes as polys.par_iter().map(MLSumcheck::prove).  Proof i is bit
+    // for bit prove(*polynomials[i]) -- with `rngs` (one per polynomial, or empty) prove_as_subprotocol's proof over rngs[i], which is
+    // continued accordingly.  challenges_or_null: the sampled challenges, instance-major, num_variables each.
+    static std::vector<Proof> prove_batch(const std::vector<const ListOfProductsOfPolynomials *> &polynomials, const std::vector<Blake2b512Rng *> &rngs = {},
+                                          std::vector<std::vector<Fr>> *challenges_or_null = nullptr) {
+        const size_t n = polynomials.size();
+        if (!rngs.empty() && rngs.size() != n) throw Panic(SC_ERR_BAD_ARG, "one rng per polynomial");
+        std::vector<Proof> out(n);
+        if (n == 0) {
+            check(sc_ml_prove_batch(nullptr, 0, nullptr, nullptr, nullptr));
+            return out;
+        }
+        std::vector<std::unique_ptr<ListOfProductsOfPolynomials::Desc>> keep;
+        std::vector<sc_poly_desc> descs;
+        for (const ListOfProductsOfPolynomials *p : polynomials) {
+            if (!p) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            keep.push_back(p->desc());
+            descs.push_back(keep.back()->d);
+        }
+        std::vector<sc_rng *> raw;
+        for (Blake2b512Rng *r : rngs) raw.push_back(r ? r->raw() : nullptr);
+        const size_t nv = polynomials[0]->num_variables, Dg = polynomials[0]->max_multiplicands + 1, rows = std::max<size_t>(nv, 1);
+        std::vector<Fr> flat(n * rows * Dg), rand(n * rows);
+        check(sc_ml_prove_batch(descs.data(), (uint32_t)n, raw.empty() ? nullptr : raw.data(), flat[0].l, rand[0].l));
+        for (size_t i = 0; i < n; ++i) {
+            out[i].resize(nv);
+            for (size_t j = 0; j < nv; ++j) out[i][j].evaluations.assign(flat.begin() + (i * nv + j) * Dg, flat.begin() + (i * nv + j + 1) * Dg);
+        }
+        if (challenges_or_null) {
+            challenges_or_null->assign(n, {});
+            for (size_t i = 0; i < n; ++i) (*challenges_or_null)[i].assign(rand.begin() + i * nv, rand.begin() + (i + 1) * nv);
+        }
+        return out;
+    }
     static SubClaim verify_as_subprotocol(Blake2b512Rng &fs_rng, const PolynomialInfo &info, const Fr &claimed_sum, const Proof &proof) {
         const size_t nv = info.num_variables, Dg = info.max_multiplicands + 1;
         if (proof.size() < nv) throw Panic(SC_ERR_BAD_ARG, "proof is incomplete");

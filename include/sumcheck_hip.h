@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch (an addition: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -247,6 +247,25 @@ SC_API int sc_ml_prove(const sc_poly_desc *desc, sc_rng *rng_or_null, uint64_t *
 SC_API int sc_ml_prove_rounds(sc_prover *p, sc_rng *rng, uint32_t n_rounds, uint64_t *out_proof, uint64_t *out_randomness);
 /* the same loop on an existing handle at round 0 (sc_prover_init / sc_prover_reset): no allocation per proof */
 SC_API int sc_ml_prove_handle(sc_prover *p, sc_rng *rng_or_null, uint64_t *out_proof);
+/* n independent instances of MLSumcheck::prove (mod.rs:42-70), proved concurrently.  descs[i] are n complete descriptors of the
+ * SAME structure (num_vars, max_multiplicands, n_products, prod_offsets, prod_indices, n_tables, flags); tables and coefficients
+ * are per instance.  rngs_or_null: NULL = a fresh Blake2b512Rng::setup() per instance, else n transcripts, rngs[i] continued by
+ * instance i exactly as sc_ml_prove continues its rng (PolynomialInfo fed first).  out_proofs: n x num_vars x (deg+1) x 4 limbs,
+ * instance-major; out_randomness_or_null: n x num_vars x 4.  Instance i's output is bit for bit what
+ * sc_ml_prove(&descs[i], rngs[i], ...) alone would have produced.  Caller memory is only read.
+ * What a caller with many small instances (a GKR prover's side claims, a lookup argument per column, proofs for many clients) uses
+ * instead of a loop -- the reference's caller would put a rayon par_iter around MLSumcheck::prove.  A whole proof over 2^6 .. 2^10
+ * entries is latency from end to end; here every instance that fits ONE block's LDS (three tables up to 2^9 entries, two up to 2^10,
+ * ten up to 2^8; products of at most 8 multiplicands) is proved by a block of its own, all of them in flight at once in one kernel
+ * that publishes every message into host-mapped memory, while the calling thread hashes and answers whichever instance has
+ * published.  The call is TOTAL over shapes: instances beyond that envelope, very small n, a busy device (another proof's persistent
+ * kernel holds it) or device-side waits switched off take the serial plan -- instance after instance on one prover -- with the same
+ * output; an instance whose block's bounded wait for the host expired is proved again by the serial plan inside the call
+ * (sc_library_stats word 5 counts them).  Only argument errors return an error: n == 0 is SC_OK and touches nothing; the first
+ * invalid instance decides the status (before any HIP call); a descriptor whose structure differs from descs[0] is SC_ERR_BAD_ARG
+ * and sc_last_error() names the instance and the field.  Policy "batch" selects the plan.  Work areas are cached (sc_release_caches). */
+SC_API int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_null, uint64_t *out_proofs,
+                             uint64_t *out_randomness_or_null);
 
 /* ---- verifier (reference src/ml_sumcheck/protocol/verifier.rs:90-251) -- host side, O(nv*deg) - */
 /* interpolate_uni_poly (verifier.rs:139-251, including its three tiers: i64 ratios for len <= 20, i128 for len <= 33, field
@@ -331,7 +350,8 @@ SC_API int sc_sparse_evaluate(const uint64_t *idx, const uint64_t *vals, uint64_
 /* The GKR entry points keep their device scratch (about 1 GB at dim = 20) and a two-table prover handle in a process-wide
  * cache between calls (allocating and freeing them costs more than a millisecond per call), sc_poly_evaluate / sc_fix_variables keep
  * their work areas (an eighth of the tables) and stream, and sc_ml_prove keeps the last prover it built (bound-table buffers of
- * at most 16 GiB) for the next one-shot proof of the same shape.  This releases all of it. */
+ * at most 16 GiB) for the next one-shot proof of the same shape; sc_ml_prove_batch keeps its message pages, mailboxes and
+ * staging area.  This releases all of it. */
 SC_API int sc_release_caches(void);
 /* Upper bound, in bytes of device memory, of what EACH of those three caches may keep between calls (default 16 GiB; 0 = nothing is
  * kept: every call allocates and frees its own, as a library without caches would).  Lowering the limit releases what is cached now. */
@@ -360,6 +380,8 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "wait_spins" (2^22)      bound of a device-side wait for a challenge, in polls (tests shorten it to exercise the give-up path)
  *   "staged_init" (1)        0: sc_prover_init over HOST tables copies them whole before round 1 instead of in chunks with round 1 computed
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
+ *   "batch" (1)              sc_ml_prove_batch: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
+ *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);
 SC_API int sc_get_policy(const char *key, int64_t *value);

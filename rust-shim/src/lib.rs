@@ -5,6 +5,7 @@
 //! |---|---|
 //! | [`prover_init`], [`prove_round`]            | `IPForMLSumcheck::{prover_init, prove_round}` `src/ml_sumcheck/protocol/prover.rs:49,74` |
 //! | [`prove`], [`prove_as_subprotocol`]         | `MLSumcheck::{prove, prove_as_subprotocol}` `src/ml_sumcheck/mod.rs:42,50` |
+//! | [`prove_batch`]                            | (new) `polys.par_iter().map(MLSumcheck::prove)`: many small instances of one structure in one call |
 //! | [`evaluate`]                                | `ListOfProductsOfPolynomials::evaluate` `src/ml_sumcheck/data_structures.rs:99` |
 //! | [`initialize_phase_one`], [`initialize_phase_two`] | `src/gkr_round_sumcheck/mod.rs:22,57` |
 //! | [`gkr_prove`]                               | `GKRRoundSumcheck::prove` `src/gkr_round_sumcheck/mod.rs:93` |
@@ -98,6 +99,8 @@ extern "C" {
     pub fn sc_poly_evaluate(desc: *const sc_poly_desc, point: *const u64, out_value: *mut u64, out_table_values_or_null: *mut u64) -> c_int;
     pub fn sc_sparse_evaluate(idx: *const u64, vals: *const u64, nnz: u64, num_vars: u32, point: *const u64, out: *mut u64) -> c_int;
     pub fn sc_ml_prove(desc: *const sc_poly_desc, rng_or_null: *mut sc_rng, out_proof: *mut u64, out_state_or_null: *mut *mut sc_prover) -> c_int;
+    pub fn sc_ml_prove_batch(descs: *const sc_poly_desc, n: u32, rngs_or_null: *const *mut sc_rng, out_proofs: *mut u64,
+                             out_randomness_or_null: *mut u64) -> c_int;
     pub fn sc_ml_verify(num_vars: u32, max_multiplicands: u32, claimed_sum: *const u64, proof: *const u64, proof_elems: u64,
                         rng_or_null: *mut sc_rng, out_point: *mut u64, out_expected: *mut u64) -> c_int;
     pub fn sc_gkr_phase_one(f1_idx: *const u64, f1_vals: *const u64, nnz: u64, dim: u32, f3: *const u64, g: *const u64, flags: u32,
@@ -323,6 +326,23 @@ pub fn prove<F: Limbs4>(polynomial: &ListOfProductsOfPolynomials<F>) -> Proof<F>
     let mut proof = vec![[0u64; 4]; polynomial.num_variables.max(1) * d];
     check(unsafe { sc_ml_prove(&desc, core::ptr::null_mut(), proof.as_mut_ptr() as *mut u64, core::ptr::null_mut()) });
     proof.chunks(d).take(polynomial.num_variables).map(prover_msg).collect()
+}
+
+/// `polys.par_iter().map(MLSumcheck::prove).collect()` for instances of ONE structure (the same number of variables and the same
+/// product lists; tables and coefficients are each instance's own) in one FFI call (`sc_ml_prove_batch`).  Small instances -- every
+/// table of an instance within one workgroup's LDS -- are proved concurrently, a workgroup each, inside one kernel; other shapes are
+/// proved one after the other inside the call.  Every proof is bit for bit what [`prove`] returns for that polynomial.  Panics like
+/// [`prove`] on an invalid instance, and if the structures differ.
+pub fn prove_batch<F: Limbs4>(polynomials: &[ListOfProductsOfPolynomials<F>]) -> Vec<Proof<F>> {
+    if polynomials.is_empty() {
+        return Vec::new();
+    }
+    let flats: Vec<Flattened> = polynomials.iter().map(flatten).collect();
+    let descs: Vec<sc_poly_desc> = flats.iter().zip(polynomials).map(|(f, p)| f.desc(p.num_variables, p.max_multiplicands, 0)).collect();
+    let (nv, d) = (polynomials[0].num_variables, polynomials[0].max_multiplicands + 1);
+    let mut proofs = vec![[0u64; 4]; polynomials.len() * nv.max(1) * d];
+    check(unsafe { sc_ml_prove_batch(descs.as_ptr(), descs.len() as u32, core::ptr::null(), proofs.as_mut_ptr() as *mut u64, core::ptr::null_mut()) });
+    proofs.chunks(nv.max(1) * d).map(|one| one.chunks(d).take(nv).map(prover_msg).collect()).collect()
 }
 
 /// The library keeps device memory between calls so that one-shot use costs what a kept prover costs: the last prover it built (up to

@@ -99,6 +99,7 @@ SIGNATURES = {
     "sc_rng_sample_fr": (None, [_V, _V]),
     "sc_ml_prove": (C.c_int, [C.POINTER(PolyDesc), _V, _V, C.POINTER(_V)]),
     "sc_ml_prove_handle": (C.c_int, [_V, _V, _V]),
+    "sc_ml_prove_batch": (C.c_int, [C.POINTER(PolyDesc), C.c_uint32, C.POINTER(_V), _V, _V]),
     "sc_interpolate_uni_poly": (C.c_int, [_V, C.c_uint32, _V, _V]),
     "sc_ml_verify": (C.c_int, [C.c_uint32, C.c_uint32, _V, _V, C.c_uint64, _V, _V, _V]),
     "sc_gkr_phase_one": (C.c_int, [_V, _V, C.c_uint64, C.c_uint32, _V, _V, C.c_uint32, _V, _V, _V, u64p]),
@@ -195,7 +196,8 @@ def get_policy(key: str) -> int:
 
 
 class policy:
-    """with _lib.policy(tail_slices=0): ...  -- set for the block, restored afterwards (tests, A/B runs)"""
+    """with _lib.policy(tail_slices=0): ...  -- set for the block, restored afterwards (tests, A/B runs); batch=0 / 2: sc_ml_prove_batch
+    always serial / batched for every n that fits"""
 
     def __init__(self, **kv):
         self.kv, self.old = kv, {}

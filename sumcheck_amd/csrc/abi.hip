@@ -1128,7 +1128,7 @@ struct PolicyDef {
 constexpr PolicyDef kPolicyDefs[scd::kPolCount] = {
     {"pipeline", 1, 0, 1},     {"resident", 1, 0, 1},          {"tail_slices", 1, 0, 1}, {"vram_mailbox", 1, 0, 1},           {"wide_tree", 1, 0, 1},
     {"rccl_direct", 1, 0, 1},  {"shard_gather_log2", 15, 1, 15}, {"gkr_direct", 1, 0, 1},  {"wait_spins", 1 << 22, 1, 0xffffffffLL}, {"tail", 1, 0, 1},
-    {"staged_init", 1, 0, 1},
+    {"staged_init", 1, 0, 1},  {"batch", 1, 0, 2},
 };
 struct PolicyTable {
     std::atomic<int64_t> v[scd::kPolCount];
@@ -1155,6 +1155,7 @@ constexpr const char *kPlanNames[scd::kPlanCount] = {
     "small.launched", "small.combos_table", "small.ptrs", "small.pipelined", "tail.slices8", "tail.slices12", "tail.rounds", "resident.slices",
     "resident.rounds", "sharded.rccl_direct", "sharded.rccl_publish", "sharded.host", "sharded.p2p", "sharded.gather_tail", "gkr.bucketed_grouped",
     "gkr.bucketed_counted", "gkr.list_form", "gkr.coeff_from_bound_table", "gkr.sharded", "fold_multi",
+    "batch.one_block", "batch.serial",
 };
 } // namespace
 int64_t scd::policy(int key) { return key >= 0 && key < scd::kPolCount ? policy_table().v[key].load(std::memory_order_relaxed) : 0; }

@@ -1,0 +1,576 @@
+// batch.hip -- sc_ml_prove_batch: n independent instances of MLSumcheck::prove (reference src/ml_sumcheck/mod.rs:42-70) of one
+// structure, proved concurrently.  Two plans, same bits:
+//   batch.one_block  k_batch_proofs (kernels_batch.hip): one block per instance, every round out of LDS; this thread serves whichever
+//                    instance's message has appeared -- copy, feed_prover_msg, sample_fr, post the challenge -- and makes no HIP call
+//                    while it does (compare run_tail, protocol.hip);
+//   batch.serial     instance after instance on one prover handle (rewound onto the next instance's tables; rebuilt where the
+//                    coefficients change): shapes beyond the kernel's envelope, n below the measured crossover, policy "batch" = 0,
+//                    device-side waits off, the device's tail slot taken -- and the instances whose block gave up waiting.
+#include "prover_internal.hpp"
+
+namespace {
+
+// ---- the serial plan -------------------------------------------------------------------------------------------------------------------
+// sc_ml_prove's steps (protocol.hip) with the handle kept across the instances of the call: the structure is the same by contract, so
+// a handle whose coefficients match is rewound onto the next tables (sc_prover_reset), as the kept prover of one-shot proofs is.
+struct SerialRunner {
+    sc_prover *p = nullptr;
+    std::vector<uint64_t> coeffs; // of the instance `p` was built for
+    bool no_polling = false;      // every round launched after its challenge (the retry of an instance whose device-side wait expired)
+    ~SerialRunner() {
+        if (p) sc_prover_free(p); // (back to the pool: the next one-shot proof of this structure finds it)
+    }
+    int prove(const sc_poly_desc *d, sc_rng *rng_or_null, uint64_t *out_proof, uint64_t *out_rand_or_null) {
+        sc_poly_desc eff = *d;
+        if ((eff.flags & SC_TABLES_ON_DEVICE) && !(eff.flags & SC_TABLES_BORROW)) eff.flags |= SC_TABLES_BORROW; // read in place: the handle does not outlive the call
+        const size_t cw = (size_t)d->n_products * 4;
+        if (p && (coeffs.size() != cw || (cw && std::memcmp(coeffs.data(), d->coeffs, cw * 8) != 0))) {
+            sc_prover_free(p);
+            p = nullptr;
+        }
+        int rc;
+        if (p) {
+            rc = sc_prover_reset(p, eff.tables, eff.flags & SC_TABLES_ON_DEVICE);
+        } else {
+            rc = sc_prover_init(&eff, &p);
+            if (rc == SC_OK) coeffs.assign(d->coeffs, d->coeffs + cw);
+        }
+        if (rc == SC_OK && no_polling) rc = sc_prover_set_polling(p, 0);
+        if (rc == SC_OK) rc = sc_ml_prove_handle(p, rng_or_null, out_proof);
+        if (rc != SC_OK) {
+            if (p) {
+                p->pool_key.clear();
+                prover_destroy(p);
+                p = nullptr;
+            }
+            return rc;
+        }
+        if (out_rand_or_null) std::memcpy(out_rand_or_null, p->randomness.data(), (size_t)p->nv * 32);
+        return SC_OK;
+    }
+};
+
+// ---- the batched plan's work areas: process-wide, one call at a time holds them (a concurrent call takes the serial plan: the device
+// has one tail slot anyway); obey sc_set_cache_limit / sc_release_caches like the other caches ------------------------------------------
+struct BatchArea {
+    std::mutex mu;
+    int device = -1;
+    int n_cus = 0;
+    sc_prover owner;            // never built: the identity under which the call holds the device's tail slot, and the stream of the launch probe
+    hipStream_t stream = nullptr;
+    char *d_buf = nullptr;      // device: ticket (256 B) | table pointers | weight matrices | staged host tables
+    size_t d_cap = 0;
+    char *h_up = nullptr;       // pinned: what is uploaded behind the ticket, in the same layout (one copy per call)
+    size_t up_cap = 0;
+    char *h_page = nullptr;     // host-mapped: messages | give-up markers | mailboxes
+    char *h_page_dev = nullptr;
+    size_t page_cap = 0;
+    uint64_t *d_vmail = nullptr; // mailboxes in host-visible device memory (large BAR, policy "vram_mailbox")
+    size_t vmail_cap = 0;
+    uint32_t gen = 0;           // tags of a launch: gen << 6 | round
+    uint64_t occ_key = 0;       // the last shape the occupancy query was made for, and its answer
+    int occ_val = 0;
+    int large_bar = -1;         // hipDeviceAttributeIsLargeBar, asked once per device
+    size_t device_bytes() const { return d_cap + vmail_cap; }
+    void free_all() {
+        if (device >= 0) (void)hipSetDevice(device);
+        if (d_buf) (void)hipFree(d_buf);
+        if (h_up) (void)hipHostFree(h_up);
+        if (h_page) (void)hipHostFree(h_page);
+        if (d_vmail) (void)hipFree(d_vmail);
+        if (stream) (void)hipStreamDestroy(stream);
+        (void)hipGetLastError();
+        d_buf = h_up = h_page = h_page_dev = nullptr;
+        d_vmail = nullptr;
+        stream = nullptr;
+        d_cap = up_cap = page_cap = vmail_cap = 0;
+        device = -1;
+        n_cus = 0;
+        gen = 0;
+        occ_key = 0;
+        occ_val = 0;
+        large_bar = -1;
+    }
+};
+BatchArea g_area;
+struct AreaLease {
+    bool held;
+    AreaLease() : held(g_area.mu.try_lock()) {}
+    ~AreaLease() {
+        if (!held) return;
+        if (g_area.device_bytes() > sc_internal_cache_limit()) g_area.free_all(); // (over the limit: nothing is kept between calls)
+        g_area.mu.unlock();
+    }
+};
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the structure every instance shares, as the kernels take it (prover_build's records: abi.hip)
+struct SharedMeta {
+    uint32_t nv = 0, U = 0, K = 0, D = 0, max_mult = 0;
+    int n_combos = 0;
+    bool fits_args = false;
+    scd::ComboMeta combo;
+    scd::FinMeta fin;
+    std::vector<uint32_t> M;                    // per product
+    std::vector<const std::vector<sch::Fr> *> unit; // per product: its node -> message matrix for a coefficient of one
+    uint32_t w_elems = 0;                       // matrices of one instance, both copies of every product
+};
+void build_shared(const sc_poly_desc *d, SharedMeta &s) {
+    s.nv = d->num_vars;
+    s.U = d->n_tables;
+    s.K = d->n_products;
+    s.max_mult = d->max_multiplicands;
+    s.D = d->max_multiplicands + 1;
+    std::memset(&s.combo, 0, sizeof(s.combo));
+    std::memset(&s.fin, 0, sizeof(s.fin));
+    std::vector<Combo> combos;
+    std::vector<uint32_t> slot_table, slot_exp;
+    uint64_t partial_elems = 0;
+    for (uint32_t k = 0; k < s.K; ++k) {
+        std::vector<uint32_t> tables, exps;
+        for (uint32_t q = d->prod_offsets[k]; q < d->prod_offsets[k + 1]; ++q) {
+            const uint32_t t = d->prod_indices[q];
+            auto it = std::find(tables.begin(), tables.end(), t);
+            if (it == tables.end()) {
+                tables.push_back(t);
+                exps.push_back(1);
+            } else {
+                exps[it - tables.begin()]++;
+            }
+        }
+        const uint32_t M = d->prod_offsets[k + 1] - d->prod_offsets[k];
+        s.M.push_back(M);
+        const uint32_t slot_off = (uint32_t)slot_table.size();
+        slot_table.insert(slot_table.end(), tables.begin(), tables.end());
+        slot_exp.insert(slot_exp.end(), exps.begin(), exps.end());
+        if (k < (uint32_t)scd::kMetaProds) {
+            s.fin.prod[k].M = M;
+            s.fin.prod[k].partial_off = partial_elems; // (the product's identity in the combination records; nothing is stored there)
+            s.fin.prod[k].w_off = s.w_elems;
+        }
+        for (uint32_t t = 0; t <= M; ++t) {
+            Combo c;
+            c.t = t;
+            c.M = M;
+            c.slot_off = slot_off;
+            c.n_slots = (uint32_t)tables.size();
+            c.partial_off = partial_elems;
+            combos.push_back(c);
+        }
+        partial_elems += (uint64_t)scd::kMaxGrid * (M + 1);
+        s.w_elems += 2 * s.D * (M + 1);
+    }
+    s.n_combos = (int)combos.size();
+    s.fits_args = s.K >= 1 && s.K <= (uint32_t)scd::kMetaProds && combos.size() <= (size_t)scd::kMetaCombos && slot_table.size() <= (size_t)scd::kMetaSlots;
+    if (s.fits_args) {
+        std::copy(combos.begin(), combos.end(), s.combo.combo);
+        std::copy(slot_table.begin(), slot_table.end(), s.combo.slot_table);
+        std::copy(slot_exp.begin(), slot_exp.end(), s.combo.slot_exp);
+    }
+}
+// the node -> message matrix of a product of M multiplicands in a message of D points, for a coefficient of one: exact Lagrange weights
+// (a field inversion per entry), the same for every instance of every batch -- computed once per process
+const std::vector<sch::Fr> *unit_matrix(uint32_t M, uint32_t D) {
+    static std::mutex mu;
+    static std::map<std::pair<uint32_t, uint32_t>, std::vector<sch::Fr>> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find({M, D});
+    if (it == cache.end()) {
+        it = cache.emplace(std::make_pair(M, D), std::vector<sch::Fr>()).first;
+        build_node_matrix(M, D, sch::kOne, it->second);
+    }
+    return &it->second; // (map nodes do not move)
+}
+// instance weights: c_k W_k and c_k 2^(5(M-1)) W_k behind it, product after product (FinProd::w_off) -- c x (1 x w) is c x w, bit for bit
+void instance_weights(const SharedMeta &s, const uint64_t *coeffs, sch::Fr *out) {
+    for (uint32_t k = 0; k < s.K; ++k) {
+        sch::Fr c, sc;
+        std::memcpy(&c, coeffs + 4 * k, 32);
+        sc = c; // coeff * 2^(5(M-1)) in Montgomery form = Montgomery form doubled 5(M-1) times
+        for (uint32_t dbl = 0; dbl < 5 * (s.M[k] - 1); ++dbl) sc = sch::add(sc, sc);
+        const std::vector<sch::Fr> &w = *s.unit[k];
+        for (size_t i = 0; i < w.size(); ++i) *out++ = sch::mul(c, w[i]);
+        for (size_t i = 0; i < w.size(); ++i) *out++ = sch::mul(sc, w[i]);
+    }
+}
+
+// The smallest n the batched kernel takes under policy "batch" = 1 (profiles/batch_bench.json).  Measured per call: about
+// 70-150 us whatever n (wait for the tables' producers, one upload, the launch, num_vars round trips, the drain of the stream) plus
+// 5-10 us per instance, against 65-130 us per instance for the serial plan -- so from n = 2 on the kernel wins everywhere (3x at n = 4),
+// and at n = 1 it is level with or ahead of the serial plan except where ONE block has a long first round to itself: config 3's shape at
+// 2^8 entries (14 combinations of 16 lanes: 8 passes over the pairs x 4 dependent products; 151 against 131 us).  The measure is
+// tail_slices_blocks': passes over a combination's pairs x multiplicands; up to 16 (a GKR phase's shape at 2^10: 131 against 132 us)
+// a lone instance runs batched.
+uint32_t batch_min_n(const SharedMeta &s) {
+    int L = 64;
+    while (L * s.n_combos > scd::kTsBlock) L >>= 1;
+    const uint64_t pairs = 1ULL << (s.nv - 1), passes = (pairs + (uint64_t)L - 1) / (uint64_t)L;
+    return passes * s.max_mult <= 16 ? 1 : 2;
+}
+
+bool device_waits_allowed(BatchArea &a) {
+    if (scd::policy(scd::kPolPipeline) == 0) return false;
+    for (const char *name : {"AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING"}) {
+        const char *v = std::getenv(name);
+        if (v && std::atoi(v) != 0) return false;
+    }
+    return launches_are_async(&a.owner);
+}
+
+struct GateHold { // the device gate until release()
+    const int device;
+    bool held = true;
+    explicit GateHold(int d) : device(d) { gate_lock(d); }
+    void release() {
+        if (held) gate_unlock(device);
+        held = false;
+    }
+    ~GateHold() { release(); }
+};
+struct SlotHold {
+    sc_prover *p;
+    bool held;
+    explicit SlotHold(sc_prover *p_) : p(p_), held(tail_slot_acquire(p_, false)) {}
+    ~SlotHold() {
+        if (held) tail_slot_release(p);
+    }
+};
+
+enum { kInFlight = 0, kDone = 1, kGaveUp = 2 };
+
+// The batched plan.  *took = false: nothing was proved and nothing written (the caller takes the serial plan); otherwise instances
+// whose state is kGaveUp are left for the caller to prove again.
+int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_null, uint64_t *out_proofs, uint64_t *out_rand_or_null, SharedMeta &s,
+                std::vector<uint8_t> &state, bool *took) {
+    using clk = std::chrono::steady_clock;
+    *took = false;
+    AreaLease lease;
+    if (!lease.held) return SC_OK;
+    BatchArea &a = g_area;
+    const int dev = sc_internal_device_ref();
+    GateHold gate(dev);
+    HIP_TRY(hipSetDevice(dev));
+    if (a.device != dev) {
+        a.free_all();
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        HIP_TRY(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
+        a.device = dev;
+        a.n_cus = prop.multiProcessorCount;
+        a.owner.device = dev;
+        a.owner.stream = a.stream;
+    }
+    if (!device_waits_allowed(a)) return SC_OK;
+    const uint64_t occ_key = ((uint64_t)s.nv << 48) | ((uint64_t)s.U << 32) | ((uint64_t)s.K << 16) | s.D;
+    if (a.occ_key != occ_key) {
+        a.occ_val = scd::batch_blocks_per_cu(dev, s.nv, s.U, (int)s.K, (int)s.D);
+        a.occ_key = occ_key;
+    }
+    const int per_cu = a.occ_val;
+    if (per_cu < 1 || a.n_cus < 1) return SC_OK;
+    SlotHold slot(&a.owner);
+    if (!slot.held) return SC_OK;
+    const auto t_begin = clk::now();
+
+    // ---- layout of the call's data ---------------------------------------------------------------------------------------------------
+    const bool host_tables = !(descs[0].flags & SC_TABLES_ON_DEVICE);
+    const size_t table_bytes = (size_t)32 << s.nv, msg_words = (size_t)s.D * 8;
+    const size_t ptr_bytes = round_up((size_t)n * s.U * sizeof(void *), 256), w_bytes = round_up((size_t)n * s.w_elems * 32, 256);
+    const size_t stage_bytes = host_tables ? (size_t)n * s.U * table_bytes : 0;
+    const size_t up_bytes = ptr_bytes + w_bytes + stage_bytes, d_bytes = 256 + up_bytes;
+    const size_t msg_bytes = round_up((size_t)n * msg_words * 8, 256), giveup_bytes = round_up((size_t)n * 4, 256), mail_bytes = (size_t)n * 128;
+    const size_t page_bytes = msg_bytes + giveup_bytes + mail_bytes;
+    if (a.d_cap < d_bytes) {
+        if (a.d_buf) (void)hipFree(a.d_buf);
+        a.d_buf = nullptr;
+        a.d_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.d_buf), d_bytes));
+        a.d_cap = d_bytes;
+    }
+    if (a.up_cap < up_bytes) {
+        if (a.h_up) (void)hipHostFree(a.h_up);
+        a.h_up = nullptr;
+        a.up_cap = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a.h_up), up_bytes, hipHostMallocDefault));
+        a.up_cap = up_bytes;
+    }
+    if (a.page_cap < page_bytes) {
+        if (a.h_page) (void)hipHostFree(a.h_page);
+        a.h_page = nullptr;
+        a.page_cap = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a.h_page), page_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        a.page_cap = page_bytes;
+        std::memset(a.h_page, 0, page_bytes);
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.h_page_dev), a.h_page, 0));
+    }
+    bool vram = false;
+    if (scd::policy(scd::kPolVramMailbox) != 0) {
+        if (a.large_bar < 0) {
+            int lb = 0;
+            a.large_bar = hipDeviceGetAttribute(&lb, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && lb ? 1 : 0;
+        }
+        if (a.large_bar == 1) {
+            if (a.vmail_cap < mail_bytes) {
+                if (a.d_vmail) (void)hipFree(a.d_vmail);
+                a.d_vmail = nullptr;
+                a.vmail_cap = 0;
+                void *m = nullptr;
+                if (hipExtMallocWithFlags(&m, mail_bytes, hipDeviceMallocFinegrained) == hipSuccess && hipMemsetAsync(m, 0, mail_bytes, a.stream) == hipSuccess &&
+                    hipStreamSynchronize(a.stream) == hipSuccess) {
+                    a.d_vmail = static_cast<uint64_t *>(m);
+                    a.vmail_cap = mail_bytes;
+                } else if (m) {
+                    (void)hipFree(m);
+                }
+            }
+            vram = a.d_vmail != nullptr;
+        }
+        (void)hipGetLastError();
+    }
+    if (a.gen >= (1u << 24)) { // (tags only ever grow; after 2^24 launches the pages start over)
+        std::memset(a.h_page, 0, a.page_cap);
+        if (a.d_vmail) HIP_TRY(hipMemset(a.d_vmail, 0, a.vmail_cap));
+        a.gen = 0;
+    }
+    const uint32_t tag0 = ++a.gen << 6;
+
+    // ---- upload: table pointers, per-instance weights, host tables -------------------------------------------------------------------
+    if (descs[0].flags & SC_TABLES_ON_DEVICE) HIP_TRY(hipDeviceSynchronize()); // the tables are read in place: their producers are waited for, as a copy would
+    const void **h_ptrs = reinterpret_cast<const void **>(a.h_up);
+    sch::Fr *h_w = reinterpret_cast<sch::Fr *>(a.h_up + ptr_bytes);
+    char *d_up = a.d_buf + 256;
+    for (uint32_t i = 0; i < n; ++i) {
+        for (uint32_t k = 0; k < s.K; ++k) {
+            sch::Fr c;
+            std::memcpy(&c, descs[i].coeffs + 4 * k, 32);
+            if (sch::geq_p(c)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: coefficient %u is not a canonical field element", i, k);
+        }
+        instance_weights(s, descs[i].coeffs, h_w + (size_t)i * s.w_elems);
+        for (uint32_t u = 0; u < s.U; ++u) {
+            if (host_tables) {
+                const size_t off = ptr_bytes + w_bytes + ((size_t)i * s.U + u) * table_bytes;
+                std::memcpy(a.h_up + off, descs[i].tables[u], table_bytes);
+                h_ptrs[(size_t)i * s.U + u] = d_up + off;
+            } else {
+                h_ptrs[(size_t)i * s.U + u] = descs[i].tables[u];
+            }
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(d_up, a.h_up, up_bytes, hipMemcpyHostToDevice, a.stream));
+    HIP_TRY(scd::launch_zero_words(reinterpret_cast<uint32_t *>(a.d_buf), 64, a.stream));
+
+    // ---- launch ----------------------------------------------------------------------------------------------------------------------
+    uint64_t *h_msg = reinterpret_cast<uint64_t *>(a.h_page);
+    uint32_t *h_giveup = reinterpret_cast<uint32_t *>(a.h_page + msg_bytes);
+    uint64_t *h_mail = reinterpret_cast<uint64_t *>(a.h_page + msg_bytes + giveup_bytes);
+    scd::BatchArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.tables = reinterpret_cast<const uint4 *const *>(d_up);
+    A.Wm = reinterpret_cast<const uint4 *>(d_up + ptr_bytes);
+    A.w_stride = s.w_elems;
+    A.n = n;
+    A.n_tables = s.U;
+    A.nv = s.nv;
+    A.n_combos = s.n_combos;
+    A.K = (int)s.K;
+    A.D = (int)s.D;
+    A.ticket = reinterpret_cast<uint32_t *>(a.d_buf);
+    A.h_msg = reinterpret_cast<uint64_t *>(a.h_page_dev);
+    A.h_giveup = reinterpret_cast<uint32_t *>(a.h_page_dev + msg_bytes);
+    A.mail = vram ? a.d_vmail : reinterpret_cast<const uint64_t *>(a.h_page_dev + msg_bytes + giveup_bytes);
+    A.mail_local = vram ? 1u : 0u;
+    A.tag0 = tag0;
+    A.max_spins = scd::wait_spins_default();
+    const int grid = (int)std::min<uint64_t>(n, (uint64_t)per_cu * (uint64_t)a.n_cus);
+    static const bool trace = std::getenv("SC_HOST_TRACE") != nullptr; // stderr: one line per batch
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (trace && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) (void)hipGetLastError();
+    if (ev0 && ev1) (void)hipEventRecord(ev0, a.stream);
+    HIP_TRY(scd::launch_batch_proofs(A, s.combo, s.fin, grid, a.stream));
+    if (ev0 && ev1) (void)hipEventRecord(ev1, a.stream);
+    scd::plan_hit(scd::kPlanBatchOneBlock);
+    *took = true;
+    gate.release(); // the loop below makes no HIP calls
+
+    // ---- the host's half: whichever instance has published, in any order -------------------------------------------------------------
+    std::vector<sch::Blake2b512Rng> tr(n); // (the callers' transcripts are touched only by instances that complete)
+    std::vector<uint32_t> round(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (rngs_or_null) tr[i] = rngs_or_null[i]->rng;
+        tr[i].feed_poly_info(s.max_mult, s.nv); // mod.rs:54
+    }
+    auto post = [&](uint32_t i, uint32_t tag, uint32_t slot_ix, const sch::Fr &vm) { // tail_post_challenge's two forms, into the instance's own slots
+        if (vram) {
+            volatile uint64_t *slot = a.d_vmail + (size_t)i * 16 + 8 * slot_ix;
+            for (int q = 0; q < 8; ++q) slot[q] = ((uint64_t)(uint32_t)(vm.l[q >> 1] >> (32 * (q & 1))) << 32) | tag;
+            __atomic_thread_fence(__ATOMIC_SEQ_CST); // (the mapping is write-combining: the fence pushes the eight words out)
+        } else {
+            uint64_t *slot = h_mail + (size_t)i * 16 + 8 * slot_ix;
+            for (int q = 0; q < 8; ++q) __atomic_store_n(slot + q, ((uint64_t)(uint32_t)(vm.l[q >> 1] >> (32 * (q & 1))) << 32) | tag, __ATOMIC_RELEASE);
+        }
+    };
+    uint32_t lo = 0, hi_seen = 0, remaining = n;
+    uint64_t idle = 0;
+    double hash_us = 0;
+    auto t_progress = clk::now();
+    bool dead = false;
+    uint32_t words[9 * 8];
+    while (remaining > 0) {
+        // tickets are taken in order: an instance beyond (highest that has shown a message) + grid cannot have started
+        const uint32_t end = (uint32_t)std::min<uint64_t>(n, (uint64_t)hi_seen + (uint64_t)grid + 1);
+        bool progress = false;
+        for (uint32_t i = lo; i < end; ++i) {
+            if (state[i] != kInFlight) continue;
+            const uint32_t tag = tag0 + round[i];
+            const uint64_t *m = h_msg + (size_t)i * msg_words;
+            bool all = (uint32_t)(__atomic_load_n(m + msg_words - 1, __ATOMIC_RELAXED) >> 32) == tag;
+            for (size_t q = 0; all && q < msg_words; ++q) {
+                const uint64_t w = __atomic_load_n(m + q, __ATOMIC_RELAXED);
+                all = (uint32_t)(w >> 32) == tag;
+                words[q] = (uint32_t)w;
+            }
+            if (!all) {
+                const uint32_t g = __atomic_load_n(h_giveup + i, __ATOMIC_ACQUIRE);
+                if (g >= tag0 && g < tag0 + 64) { // its block's wait expired: nothing of this instance is returned from here
+                    state[i] = kGaveUp;
+                    --remaining;
+                    hi_seen = std::max(hi_seen, i + 1);
+                    progress = true;
+                }
+                continue;
+            }
+            uint64_t *pm = out_proofs + ((size_t)i * s.nv + round[i]) * s.D * 4;
+            std::memcpy(pm, words, msg_words * 4);
+            const auto h0 = trace ? clk::now() : clk::time_point();
+            tr[i].feed_prover_msg(reinterpret_cast<const sch::Fr *>(pm), s.D); // mod.rs:61
+            const sch::Fr vm = tr[i].sample_fr();                              // mod.rs:63
+            if (trace) hash_us += std::chrono::duration<double, std::micro>(clk::now() - h0).count();
+            if (out_rand_or_null) std::memcpy(out_rand_or_null + ((size_t)i * s.nv + round[i]) * 4, &vm, 32);
+            if (++round[i] < s.nv) {
+                post(i, tag, (round[i] - 1) & 1u, vm);
+            } else {
+                state[i] = kDone;
+                --remaining;
+                if (rngs_or_null) rngs_or_null[i]->rng = tr[i];
+            }
+            hi_seen = std::max(hi_seen, i + 1);
+            progress = true;
+        }
+        while (lo < n && state[lo] != kInFlight) ++lo;
+        if (progress) {
+            idle = 0;
+        } else if ((++idle & 0x3ff) == 0) {
+            const auto now = clk::now();
+            if (idle == 0x400) t_progress = now; // (the clock is read only once the loop has been idle for a while)
+            else if (now - t_progress > publish_timeout()) {
+                dead = true;
+                break;
+            }
+        }
+    }
+    if (dead) { // ask every block to drop what it holds (and what it would take next), so that the stream drains
+        for (uint32_t i = 0; i < n; ++i)
+            if (state[i] == kInFlight) post(i, (tag0 + round[i]) ^ 0x80000000u, round[i] & 1u, sch::zero()); // (the wait behind the message the host never saw)
+    }
+    {
+        DeviceGate g2(dev);
+        (void)hipSetDevice(dev);
+        const hipError_t e = hipStreamSynchronize(a.stream); // the kernel has left the GPU before the tail slot is given back
+        float ms = 0;
+        if (ev0 && ev1 && e == hipSuccess) (void)hipEventElapsedTime(&ms, ev0, ev1);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (trace) {
+            uint32_t gave_up = 0;
+            for (uint32_t i = 0; i < n; ++i) gave_up += state[i] == kGaveUp;
+            std::fprintf(stderr, "[sc] batch: n %u, nv %u, plan batch.one_block, grid %d (%d per CU), mailbox %s, total %.1f us, kernel %.1f us, host hash %.1f us, gave up %u\n", n, s.nv,
+                         grid, per_cu, vram ? "vram" : "host", std::chrono::duration<double, std::micro>(clk::now() - t_begin).count(), ms * 1e3, hash_us, gave_up);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return sc_internal_fail(SC_ERR_HIP, "hipStreamSynchronize failed after a batch: %s", hipGetErrorString(e));
+        }
+    }
+    if (dead) return sc_internal_fail(SC_ERR_HIP, "a batched instance did not publish its message within the publish timeout");
+    return SC_OK;
+}
+
+const char *first_structure_difference(const sc_poly_desc &a, const sc_poly_desc &b) {
+    if (a.num_vars != b.num_vars) return "num_vars";
+    if (a.max_multiplicands != b.max_multiplicands) return "max_multiplicands";
+    if (a.n_products != b.n_products) return "n_products";
+    if (a.n_tables != b.n_tables) return "n_tables";
+    if (a.flags != b.flags) return "flags";
+    if (a.n_products) {
+        if (std::memcmp(a.prod_offsets, b.prod_offsets, (size_t)(a.n_products + 1) * 4) != 0) return "prod_offsets";
+        if (std::memcmp(a.prod_indices, b.prod_indices, (size_t)a.prod_offsets[a.n_products] * 4) != 0) return "prod_indices";
+    }
+    return nullptr;
+}
+
+} // namespace
+
+void sc_internal_release_batch_cache() {
+    std::lock_guard<std::mutex> lk(g_area.mu);
+    g_area.free_all();
+}
+
+extern "C" int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_null, uint64_t *out_proofs, uint64_t *out_randomness_or_null) {
+    if (n == 0) return SC_OK;
+    if (!descs || !out_proofs) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    for (uint32_t i = 0; i < n; ++i) {
+        int rc = validate_desc(&descs[i]); // prover_init panics on a constant before anything is proved (prover.rs:50-52)
+        if (rc) {
+            const std::string why = sc_last_error();
+            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+        }
+        if (rngs_or_null && !rngs_or_null[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null rng", i);
+        if (const char *field = i ? first_structure_difference(descs[0], descs[i]) : nullptr)
+            return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u differs from instance 0 in %s: a batch has one structure", i, field);
+    }
+    if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
+    static const bool trace = std::getenv("SC_HOST_TRACE") != nullptr;
+    const uint32_t nv = descs[0].num_vars, D = descs[0].max_multiplicands + 1;
+    std::vector<uint8_t> state(n, kGaveUp); // (what the serial plan below proves)
+    bool took = false;
+    const int64_t pol = scd::policy(scd::kPolBatch);
+    if (pol != 0 && descs[0].n_products > 0 && !(descs[0].flags & (SC_TABLES_STREAM | SC_NO_DEVICE_POLLING))) {
+        SharedMeta s;
+        build_shared(&descs[0], s);
+        if (s.fits_args && scd::batch_shape_fits(s.nv, s.U, (int)s.K, (int)s.D, s.max_mult) && (pol == 2 || n >= batch_min_n(s))) {
+            for (uint32_t k = 0; k < s.K; ++k) s.unit.push_back(unit_matrix(s.M[k], s.D));
+            std::fill(state.begin(), state.end(), (uint8_t)kInFlight);
+            int rc = run_batched(descs, n, rngs_or_null, out_proofs, out_randomness_or_null, s, state, &took);
+            if (rc) return rc;
+            if (!took) std::fill(state.begin(), state.end(), (uint8_t)kGaveUp);
+        }
+    }
+    // ---- the serial plan: everything (nothing ran batched), or the instances whose block gave up waiting -- those with device-side waits off
+    uint32_t todo = 0;
+    for (uint32_t i = 0; i < n; ++i) todo += state[i] != kDone;
+    if (todo == 0) return SC_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!took) scd::plan_hit(scd::kPlanBatchSerial);
+    if (descs[0].flags & SC_TABLES_ON_DEVICE) { // read in place: whatever produced the tables is waited for, as a copy would
+        const int dev = sc_internal_device_ref();
+        DeviceGate gate_(dev);
+        HIP_TRY(hipSetDevice(dev));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    SerialRunner serial;
+    serial.no_polling = took;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (state[i] == kDone) continue;
+        int rc = serial.prove(&descs[i], rngs_or_null ? rngs_or_null[i] : nullptr, out_proofs + (size_t)i * nv * D * 4,
+                              out_randomness_or_null ? out_randomness_or_null + (size_t)i * nv * 4 : nullptr);
+        if (rc) {
+            const std::string why = sc_last_error();
+            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+        }
+        if (took) g_stat[kStatProofRetries].fetch_add(1, std::memory_order_relaxed);
+    }
+    if (trace)
+        std::fprintf(stderr, "[sc] batch: n %u, nv %u, plan batch.serial (%u instances%s), total %.1f us\n", n, nv, todo, took ? ", after an expired device-side wait" : "",
+                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    return SC_OK;
+}

@@ -216,6 +216,27 @@ int tail_slices_max_blocks(int device, int max_multiplicands); // occupancy of k
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, DEVICE): thread ranks of one process drive several GPUs
 hipError_t ensure_dynamic_lds(const void *kernel, int bytes, bool (&done)[64]);
 hipError_t launch_tail_slices(TailSlicesArgs args, const ComboMeta &meta, const FinMeta &fin, int max_multiplicands, hipStream_t stream);
+// Batched proving (kernels_batch.hip: k_batch_proofs): n independent small instances of one structure, ONE block per instance from round 1
+// on -- k_tail_slices' last phase ("one block finishes the proof alone, out of LDS") for the whole proof.  Persistent blocks take instance
+// numbers from a ticket; a block waits for the host only, never for another block, so the grid may exceed what is resident.
+struct BatchArgs {
+    const uint4 *const *tables; // device: [n][n_tables] pointers to the instances' tables (reference layout, 2^nv entries, only read)
+    const uint4 *Wm;            // device: n x w_stride elements, instance i's node -> message matrices with its c_k folded in (FinProd::w_off inside)
+    uint32_t w_stride;
+    uint32_t n, n_tables, nv;
+    int n_combos, K, D;
+    uint32_t *ticket;           // device, zero at launch: the next instance number
+    uint64_t *h_msg;            // host-mapped, [n][D * 8] words: 32-bit limb | tag << 32 -- round j of an instance publishes its message under tag0 + j
+    const uint64_t *mail;       // [n][2][8] words: limb << 32 | tag -- the challenge behind message j under tag0 + j in slot j & 1 (tail_post_challenge's form)
+    uint32_t mail_local;        // 1: `mail` is device memory the host stores into over the BAR (a poll is local); 0: host-mapped
+    uint32_t *h_giveup;         // host-mapped, [n]: the tag an instance's block waited for in vain (it then takes the next ticket)
+    uint32_t tag0;              // a multiple of 64 >= 64, above every tag an earlier launch over the same pages used
+    uint32_t max_spins;
+    uint32_t fin_bytes;         // (filled in by the launcher: LDS layout -- finalize scratch | message | tables)
+};
+bool batch_shape_fits(uint32_t nv, uint32_t n_tables, int K, int D, uint32_t max_multiplicands); // the envelope: one block's LDS, products of <= kMaxFusedM
+int batch_blocks_per_cu(int device, uint32_t nv, uint32_t n_tables, int K, int D);             // occupancy of k_batch_proofs at that LDS size (0: unknown)
+hipError_t launch_batch_proofs(BatchArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -233,6 +254,7 @@ enum PolicyKey {
     kPolWaitSpins,        // "wait_spins"         bound of a device-side wait for a challenge, in polls (default 2^22)
     kPolTail,             // "tail"               1: the persistent tail kernels; 0: latency-bound rounds as pipelined launches (what sharded RCCL rounds use)
     kPolStagedInit,       // "staged_init"        1: sc_prover_init over HOST tables copies them in chunks and computes round 1 under the copy (shapes of the merged big-round kernel, >= 2^18 entries)
+    kPolBatch,            // "batch"              sc_ml_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
     kPolCount
 };
 int64_t policy(int key);
@@ -278,6 +300,8 @@ enum Plan {
     kPlanGkrCoeffFromBound,   // phase two's coefficient f2(u) from phase one's bound table
     kPlanGkrSharded,          // sc_gkr_prove_sharded
     kPlanFoldMulti,           // sc_poly_evaluate / sc_fix_variables (k_fold_multi)
+    kPlanBatchOneBlock,       // sc_ml_prove_batch: k_batch_proofs, one block per instance, every round out of LDS
+    kPlanBatchSerial,         // ... instance after instance on the kept prover (shapes beyond the envelope, small n, slot busy, device-side waits off)
     kPlanCount
 };
 void plan_hit(int plan);

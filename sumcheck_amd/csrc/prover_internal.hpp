@@ -226,6 +226,7 @@ bool handle_pool_offer(sc_prover *p);
 std::vector<uint8_t> pool_key_of(const sc_poly_desc *d, int device);
 sc_prover *handle_pool_take(const std::vector<uint8_t> &key);
 void claim_weights(uint32_t M, const sch::Fr &r, sch::Fr *lam);
+void build_node_matrix(uint32_t M, uint32_t D, const sch::Fr &scale, std::vector<sch::Fr> &out); // a product's node -> message matrix, times `scale`
 int collect_timing(sc_prover *p);
 int prover_bind_out(sc_prover *p, const uint64_t *r, uint64_t *d_out);
 uint64_t sc_internal_cache_limit();
@@ -242,6 +243,11 @@ int await_round(sc_prover *p, uint64_t *out_evals, uint32_t want);
 bool wait_gave_up(sc_prover *p);   // the give-up marker of k_wait_challenge
 void abandon_deferred(sc_prover *p); // error path: let a stream that is blocked on the wait drain
 int sc_internal_run_rounds(sc_prover *p, sch::Blake2b512Rng &rng, uint32_t n_rounds, uint64_t *out_msgs, sch::Fr *out_challenges);
+bool launches_are_async(sc_prover *p);              // one-time probe on p->stream: does a launch return before its kernel has finished?
+bool tail_slot_acquire(sc_prover *p, bool resident); // the device's one tail slot (p: the owner's identity); false: taken
+void tail_slot_release(sc_prover *p);
+// ---- batch.hip ----
+void sc_internal_release_batch_cache(); // sc_release_caches: sc_ml_prove_batch's work areas
 // ---- comm.hip ----
 struct NcclApi {
     void *lib = nullptr;

@@ -351,6 +351,36 @@ class MLSumcheck:
         return [ProverMsg(proof[i].copy()) for i in range(polynomial.num_variables)]
 
     @staticmethod
+    def prove_batch(polynomials: Sequence[ListOfProductsOfPolynomials], rngs: Optional[Sequence[Blake2b512Rng]] = None, return_randomness: bool = False):
+        """n independent proofs of ONE structure (the same num_variables and product lists; tables and coefficients per instance) in one
+        library call (sc_ml_prove_batch) -> a list of proofs, proof i bit for bit MLSumcheck.prove(polynomials[i]) -- or, with `rngs`,
+        prove_as_subprotocol(rngs[i], polynomials[i]), rngs[i] continued accordingly.  Instances small enough for one workgroup's LDS are
+        proved concurrently in one kernel; other shapes one after the other inside the call.  return_randomness: also the challenges,
+        (n, num_variables, 4)."""
+        n = len(polynomials)
+        if rngs is not None and len(rngs) != n:
+            raise ValueError("one rng per polynomial")
+        if n == 0:
+            check(lib().sc_ml_prove_batch(None, 0, None, None, None))
+            return ([], np.zeros((0, 0, 4), np.uint64)) if return_randomness else []
+        descs = (PolyDesc * n)()
+        keep = []
+        for i, poly in enumerate(polynomials):
+            d, k = poly._desc(False)
+            C.memmove(C.byref(descs, i * C.sizeof(PolyDesc)), C.byref(d), C.sizeof(PolyDesc))
+            keep.append(k)
+        nv, D = polynomials[0].num_variables, polynomials[0].max_multiplicands + 1
+        proofs = np.empty((n, max(nv, 1), D, 4), dtype=np.uint64)
+        rand = np.empty((n, max(nv, 1), 4), dtype=np.uint64)
+        rp = None
+        if rngs is not None:
+            rp = (C.c_void_p * n)(*[r._h for r in rngs])
+        check(lib().sc_ml_prove_batch(descs, n, rp, _ptr(proofs), _ptr(rand)))
+        del keep
+        out = [[ProverMsg(proofs[i, j].copy()) for j in range(nv)] for i in range(n)]
+        return (out, rand[:, :nv].copy()) if return_randomness else out
+
+    @staticmethod
     def prove_as_subprotocol(fs_rng: Blake2b512Rng, polynomial: ListOfProductsOfPolynomials, borrow: bool = False):
         """mod.rs:50-70: the whole Fiat-Shamir loop runs inside the library (sc_ml_prove)."""
         d, keep = polynomial._desc(borrow)
