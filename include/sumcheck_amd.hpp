@@ -479,6 +479,50 @@ struct GKRRoundSumcheck {
         }
         return pr;
     }
+    // n independent GKRRoundSumcheck::prove of ONE dim in one library call (sc_gkr_prove_batch): proof i is bit for bit
+    // prove(*rngs[i], *f1s[i], *f2s[i], *f3s[i], gs[i]), and rngs[i] is continued accordingly.  Pointers may repeat (one wiring predicate f1
+    // for many data instances) -- except the rngs, which are all distinct.  uv_or_null: per instance the sampled u then v (2 dim elements).
+    static std::vector<GKRProof> prove_batch(const std::vector<Blake2b512Rng *> &rngs, const std::vector<const SparseMultilinearExtension *> &f1s,
+                                             const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s,
+                                             const std::vector<std::vector<Fr>> &gs, std::vector<std::vector<Fr>> *uv_or_null = nullptr) {
+        const size_t n = rngs.size();
+        if (f1s.size() != n || f2s.size() != n || f3s.size() != n || gs.size() != n) throw Panic(SC_ERR_BAD_ARG, "one f1, f2, f3 and g per rng");
+        std::vector<GKRProof> out(n);
+        if (n == 0) {
+            check(sc_gkr_prove_batch(0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+            return out;
+        }
+        if (!f2s[0]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+        const size_t dim = f2s[0]->num_vars, rows = std::max<size_t>(dim, 1);
+        std::vector<sc_rng *> raw(n);
+        std::vector<const uint64_t *> idx(n), vals(n), p2(n), p3(n), pg(n);
+        std::vector<uint64_t> nnz(n);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f1s[i] || !f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f1s[i]->num_vars != 3 * dim || f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            raw[i] = rngs[i] ? rngs[i]->raw() : nullptr;
+            idx[i] = f1s[i]->indices.data();
+            vals[i] = f1s[i]->values.empty() ? nullptr : f1s[i]->values[0].l;
+            nnz[i] = f1s[i]->indices.size();
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+            pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+        }
+        std::vector<Fr> flat(n * 2 * rows * 3), uv(n * 2 * rows);
+        check(sc_gkr_prove_batch((uint32_t)n, (uint32_t)dim, raw.data(), idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), 0, flat[0].l, uv[0].l));
+        for (size_t i = 0; i < n; ++i) {
+            const Fr *m = flat.data() + i * 2 * dim * 3;
+            for (size_t j = 0; j < dim; ++j) {
+                out[i].phase1_sumcheck_msgs.push_back(ProverMsg{std::vector<Fr>(m + 3 * j, m + 3 * j + 3)});
+                out[i].phase2_sumcheck_msgs.push_back(ProverMsg{std::vector<Fr>(m + 3 * (dim + j), m + 3 * (dim + j) + 3)});
+            }
+        }
+        if (uv_or_null) {
+            uv_or_null->assign(n, {});
+            for (size_t i = 0; i < n; ++i) (*uv_or_null)[i].assign(uv.begin() + i * 2 * dim, uv.begin() + (i + 1) * 2 * dim);
+        }
+        return out;
+    }
 };
 
 } // namespace sumcheck

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch (an addition: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch and sc_gkr_prove_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -303,6 +303,27 @@ SC_API int sc_gkr_phase_two(const uint64_t *f1g_idx, const uint64_t *f1g_vals, u
  * sc_gkr_phase_one / _two above return the list and take the sorting route. */
 SC_API int sc_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t *f1_vals, uint64_t nnz, uint32_t dim,
                  const uint64_t *f2, const uint64_t *f3, const uint64_t *g, uint32_t flags, uint64_t *out_proof, uint64_t *out_uv_or_null);
+/* n independent instances of GKRRoundSumcheck::prove (mod.rs:93-139) of one `dim`, proved concurrently.
+ * Per instance i: f1_idx[i] / f1_vals[i] (nnz[i] pairs), f2[i], f3[i] (2^dim x 4 limbs), g[i] (dim x 4, host).
+ * Pointers may repeat across instances (one wiring predicate f1 for many data instances is the usual case).
+ * flags: SC_TABLES_ON_DEVICE => f1_idx[i], f1_vals[i], f2[i], f3[i] are device pointers, read in place;
+ * the pointer arrays themselves, nnz[] and g[i] are always host memory.
+ * rngs: n transcripts, all distinct, rngs[i] continued exactly as sc_gkr_prove continues its rng.
+ * out_proofs: n x 2 x dim x 3 x 4 limbs, instance-major; out_uv_or_null: n x 2 x dim x 4.
+ * Instance i's proof, (u, v) and the final state of rngs[i] are bit for bit what sc_gkr_prove on rngs[i] alone would have produced
+ * (repeated indices summed, any order of the list, zero values).  Small instances -- dim <= 9 and nnz[i] <= 64 x 2^dim for every i:
+ * both tables of a phase, the two eq tables and the cells the non-zeros are added into within one workgroup's LDS -- are proved a
+ * workgroup each inside one kernel, the host hashing and answering; every other shape runs instance after instance through
+ * sc_gkr_prove's path inside the call, with the same bits.  Policy "batch" selects the plan as for sc_ml_prove_batch.
+ * The argument checks are sc_gkr_prove's, per instance; everything the host can check is checked before any HIP call, so a bad
+ * argument is SC_ERR_BAD_ARG with or without a GPU.  The lowest failing instance decides the status, sc_last_error() starts with
+ * "instance %u: ", and no caller transcript has been advanced when an argument error is returned (an out-of-range index in a
+ * device-resident list included: it is found on the device in front of the proofs, never followed).  n == 0: SC_OK, nothing is touched.
+ * A null rngs[i], or one sc_rng twice: SC_ERR_BAD_ARG.  dim == 0: SC_ERR_CONSTANT_POLY.  Work areas are cached (sc_release_caches). */
+SC_API int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
+                              const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
+                              const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
+                              uint32_t flags, uint64_t *out_proofs, uint64_t *out_uv_or_null);
 /* f4 -- the same two initialisations with f1's non-zeros SPREAD OVER SEVERAL GPUs (worth it from dim ~ 24).
  * Every rank passes a disjoint subset of f1's (index, value) pairs -- any partition -- and all of f3 / g.  A rank's scatter is a
  * partial sum of a_hg, so the ranks' dense tables are added with ONE table-sized integer all-reduce of the widened limbs
@@ -380,7 +401,7 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "wait_spins" (2^22)      bound of a device-side wait for a challenge, in polls (tests shorten it to exercise the give-up path)
  *   "staged_init" (1)        0: sc_prover_init over HOST tables copies them whole before round 1 instead of in chunks with round 1 computed
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
- *   "batch" (1)              sc_ml_prove_batch: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
+ *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
  *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);

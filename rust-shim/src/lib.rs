@@ -108,6 +108,9 @@ extern "C" {
     pub fn sc_gkr_phase_two(f1g_idx: *const u64, f1g_vals: *const u64, nnz: u64, dim: u32, u: *const u64, flags: u32, f1_gu: *mut u64) -> c_int;
     pub fn sc_gkr_prove(rng: *mut sc_rng, f1_idx: *const u64, f1_vals: *const u64, nnz: u64, dim: u32, f2: *const u64, f3: *const u64,
                         g: *const u64, flags: u32, out_proof: *mut u64, out_uv_or_null: *mut u64) -> c_int;
+    pub fn sc_gkr_prove_batch(n: u32, dim: u32, rngs: *const *mut sc_rng, f1_idx: *const *const u64, f1_vals: *const *const u64, nnz: *const u64,
+                              f2: *const *const u64, f3: *const *const u64, g: *const *const u64, flags: u32, out_proofs: *mut u64,
+                              out_uv_or_null: *mut u64) -> c_int;
     pub fn sc_gkr_prove_sharded(comm: *mut sc_comm, rng: *mut sc_rng, f1_idx: *const u64, f1_vals: *const u64, nnz_local: u64, dim: u32, f2: *const u64,
                                 f3: *const u64, g: *const u64, flags: u32, out_proof: *mut u64, out_uv_or_null: *mut u64) -> c_int;
     pub fn sc_comm_unique_id(out128: *mut u8) -> c_int;
@@ -465,6 +468,63 @@ pub fn gkr_prove<F: Limbs4>(rng: &mut HipRng, f1: &SparseMultilinearExtension<F>
         u: uv[..dim].iter().map(|l| F::from_limbs(*l)).collect(),
         v: uv[dim..2 * dim].iter().map(|l| F::from_limbs(*l)).collect(),
     }
+}
+
+/// One instance of [`gkr_prove_batch`]: what a single [`gkr_prove`] call takes.
+pub struct GkrInstance<'a, F: Limbs4> {
+    pub rng: &'a mut HipRng,
+    pub f1: &'a SparseMultilinearExtension<F>,
+    pub f2: &'a DenseMultilinearExtension<F>,
+    pub f3: &'a DenseMultilinearExtension<F>,
+    pub g: &'a [F],
+}
+
+/// `instances.iter_mut().map(GKRRoundSumcheck::prove)` for instances of ONE `dim` in one FFI call (`sc_gkr_prove_batch`).  Small
+/// instances (`dim <= 9`) are proved concurrently, a workgroup each, inside one kernel; other shapes are proved one after the other
+/// inside the call.  Every proof, `(u, v)` and final transcript state is bit for bit what [`gkr_prove`] gives for that instance.
+pub fn gkr_prove_batch<F: Limbs4>(instances: &mut [GkrInstance<F>]) -> Vec<HipGKRProof<F>> {
+    if instances.is_empty() {
+        return Vec::new();
+    }
+    let dim = instances[0].f2.num_vars;
+    let n = instances.len();
+    let mut arrays = Vec::with_capacity(n);
+    let mut gls: Vec<Vec<[u64; 4]>> = Vec::with_capacity(n);
+    for inst in instances.iter() {
+        assert_eq!(inst.f1.num_vars, 3 * dim);
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        arrays.push(sparse_arrays(inst.f1));
+        gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+    }
+    let rngs: Vec<*mut sc_rng> = instances.iter().map(|i| i.rng.0).collect();
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let f2: Vec<*const u64> = instances.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = instances.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = gls.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let rows = dim.max(1);
+    let mut proofs = vec![[0u64; 4]; n * 2 * rows * 3];
+    let mut uv = vec![[0u64; 4]; n * 2 * rows];
+    check(unsafe {
+        sc_gkr_prove_batch(n as u32, dim as u32, rngs.as_ptr(), idx.as_ptr(), vals.as_ptr(), nnz.as_ptr(), f2.as_ptr(), f3.as_ptr(), g.as_ptr(), 0,
+                           proofs.as_mut_ptr() as *mut u64, uv.as_mut_ptr() as *mut u64)
+    });
+    (0..n)
+        .map(|i| {
+            let p = &proofs[i * 2 * dim * 3..(i + 1) * 2 * dim * 3];
+            let w = &uv[i * 2 * dim..(i + 1) * 2 * dim];
+            let msgs = |off: usize| (0..dim).map(|j| prover_msg(&p[3 * (off + j)..3 * (off + j) + 3])).collect();
+            HipGKRProof {
+                phase1_sumcheck_msgs: msgs(0),
+                phase2_sumcheck_msgs: msgs(dim),
+                u: w[..dim].iter().map(|l| F::from_limbs(*l)).collect(),
+                v: w[dim..2 * dim].iter().map(|l| F::from_limbs(*l)).collect(),
+            }
+        })
+        .collect()
 }
 
 // ---- multi-GPU ------------------------------------------------------------------------------------------------------------------

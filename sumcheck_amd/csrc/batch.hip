@@ -6,7 +6,18 @@
 //   batch.serial     instance after instance on one prover handle (rewound onto the next instance's tables; rebuilt where the
 //                    coefficients change): shapes beyond the kernel's envelope, n below the measured crossover, policy "batch" = 0,
 //                    device-side waits off, the device's tail slot taken -- and the instances whose block gave up waiting.
+// sc_gkr_prove_batch: n independent instances of GKRRoundSumcheck::prove (reference src/gkr_round_sumcheck/mod.rs:93-139) of one dim, the
+// same two plans over the same work areas, serving loop and give-up protocol (run_batched takes what differs as a BatchJob):
+//   batch.gkr_one_block  k_batch_gkr (kernels_batch_gkr.hip): one block per instance builds both phases' tables in LDS and runs the
+//                        2 x dim rounds; no PolynomialInfo is fed (mod.rs:108-133) and the challenge behind every message but the last is posted;
+//   batch.gkr_serial     instance after instance through sc_gkr_prove's path, on copies of the callers' transcripts.
+#include <functional>
+#include <unordered_set>
+
 #include "prover_internal.hpp"
+
+int sc_internal_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t *f1_vals, uint64_t nnz, uint32_t dim, const uint64_t *f2, const uint64_t *f3, const uint64_t *g,
+                          uint32_t flags, uint64_t *out_proof, uint64_t *out_uv_or_null, bool no_polling); // gkr.hip: sc_gkr_prove, optionally with device-side waits off
 
 namespace {
 
@@ -238,12 +249,37 @@ struct SlotHold {
 
 enum { kInFlight = 0, kDone = 1, kGaveUp = 2 };
 
+// What an entry point hands to the batched plan: the shape of the exchange with the host, and the three steps that differ.
+struct BatchPages { // where a launch finds the call's pages
+    char *d_up;     // device: the uploaded image
+    uint32_t *ticket;
+    uint64_t *h_msg;
+    uint32_t *h_giveup;
+    const uint64_t *mail;
+    uint32_t mail_local, tag0, max_spins;
+};
+struct BatchJob {
+    uint32_t n = 0, n_rounds = 0, D = 0; // instances; messages per instance (the challenge behind every one but the last is posted); evaluations per message
+    bool poly_info = false;              // MLSumcheck::prove feeds PolynomialInfo first (mod.rs:54); GKRRoundSumcheck::prove continues the transcript as it is
+    uint32_t max_mult = 0;
+    bool inputs_on_device = false;       // read in place: their producers are waited for
+    uint64_t occ_key = 0;                // identifies the launch shape of the occupancy query
+    int plan = 0;
+    const char *plan_name = "", *size_name = "nv"; // (the SC_HOST_TRACE line)
+    uint32_t size = 0;
+    size_t up_bytes = 0;                 // what is uploaded behind the ticket
+    std::function<int(int)> blocks_per_cu;                                        // (device) -> resident blocks per CU of the kernel at this shape
+    std::function<int(char *, char *)> fill;                                      // (h_up, d_up): write the image (pointers into it are d_up + offset)
+    std::function<int(char *, char *, hipStream_t)> check_on_device;              // optional, behind the upload and in front of the launch: an argument error found on the device
+    std::function<hipError_t(const BatchPages &, int, hipStream_t)> launch;      // (pages, grid, stream)
+};
+
 // The batched plan.  *took = false: nothing was proved and nothing written (the caller takes the serial plan); otherwise instances
 // whose state is kGaveUp are left for the caller to prove again.
-int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_null, uint64_t *out_proofs, uint64_t *out_rand_or_null, SharedMeta &s,
-                std::vector<uint8_t> &state, bool *took) {
+int run_batched(const BatchJob &job, sc_rng *const *rngs_or_null, uint64_t *out_proofs, uint64_t *out_rand_or_null, std::vector<uint8_t> &state, bool *took) {
     using clk = std::chrono::steady_clock;
     *took = false;
+    const uint32_t n = job.n;
     AreaLease lease;
     if (!lease.held) return SC_OK;
     BatchArea &a = g_area;
@@ -261,10 +297,9 @@ int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_nu
         a.owner.stream = a.stream;
     }
     if (!device_waits_allowed(a)) return SC_OK;
-    const uint64_t occ_key = ((uint64_t)s.nv << 48) | ((uint64_t)s.U << 32) | ((uint64_t)s.K << 16) | s.D;
-    if (a.occ_key != occ_key) {
-        a.occ_val = scd::batch_blocks_per_cu(dev, s.nv, s.U, (int)s.K, (int)s.D);
-        a.occ_key = occ_key;
+    if (a.occ_key != job.occ_key) {
+        a.occ_val = job.blocks_per_cu(dev);
+        a.occ_key = job.occ_key;
     }
     const int per_cu = a.occ_val;
     if (per_cu < 1 || a.n_cus < 1) return SC_OK;
@@ -273,11 +308,8 @@ int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_nu
     const auto t_begin = clk::now();
 
     // ---- layout of the call's data ---------------------------------------------------------------------------------------------------
-    const bool host_tables = !(descs[0].flags & SC_TABLES_ON_DEVICE);
-    const size_t table_bytes = (size_t)32 << s.nv, msg_words = (size_t)s.D * 8;
-    const size_t ptr_bytes = round_up((size_t)n * s.U * sizeof(void *), 256), w_bytes = round_up((size_t)n * s.w_elems * 32, 256);
-    const size_t stage_bytes = host_tables ? (size_t)n * s.U * table_bytes : 0;
-    const size_t up_bytes = ptr_bytes + w_bytes + stage_bytes, d_bytes = 256 + up_bytes;
+    const size_t msg_words = (size_t)job.D * 8;
+    const size_t up_bytes = job.up_bytes, d_bytes = 256 + up_bytes;
     const size_t msg_bytes = round_up((size_t)n * msg_words * 8, 256), giveup_bytes = round_up((size_t)n * 4, 256), mail_bytes = (size_t)n * 128;
     const size_t page_bytes = msg_bytes + giveup_bytes + mail_bytes;
     if (a.d_cap < d_bytes) {
@@ -334,61 +366,41 @@ int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_nu
     }
     const uint32_t tag0 = ++a.gen << 6;
 
-    // ---- upload: table pointers, per-instance weights, host tables -------------------------------------------------------------------
-    if (descs[0].flags & SC_TABLES_ON_DEVICE) HIP_TRY(hipDeviceSynchronize()); // the tables are read in place: their producers are waited for, as a copy would
-    const void **h_ptrs = reinterpret_cast<const void **>(a.h_up);
-    sch::Fr *h_w = reinterpret_cast<sch::Fr *>(a.h_up + ptr_bytes);
+    // ---- upload: what the kernel reads behind the ticket, in one copy ------------------------------------------------------------------
+    if (job.inputs_on_device) HIP_TRY(hipDeviceSynchronize()); // the inputs are read in place: their producers are waited for, as a copy would
     char *d_up = a.d_buf + 256;
-    for (uint32_t i = 0; i < n; ++i) {
-        for (uint32_t k = 0; k < s.K; ++k) {
-            sch::Fr c;
-            std::memcpy(&c, descs[i].coeffs + 4 * k, 32);
-            if (sch::geq_p(c)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: coefficient %u is not a canonical field element", i, k);
-        }
-        instance_weights(s, descs[i].coeffs, h_w + (size_t)i * s.w_elems);
-        for (uint32_t u = 0; u < s.U; ++u) {
-            if (host_tables) {
-                const size_t off = ptr_bytes + w_bytes + ((size_t)i * s.U + u) * table_bytes;
-                std::memcpy(a.h_up + off, descs[i].tables[u], table_bytes);
-                h_ptrs[(size_t)i * s.U + u] = d_up + off;
-            } else {
-                h_ptrs[(size_t)i * s.U + u] = descs[i].tables[u];
-            }
-        }
+    {
+        int rc = job.fill(a.h_up, d_up);
+        if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(d_up, a.h_up, up_bytes, hipMemcpyHostToDevice, a.stream));
     HIP_TRY(scd::launch_zero_words(reinterpret_cast<uint32_t *>(a.d_buf), 64, a.stream));
+    if (job.check_on_device) {
+        int rc = job.check_on_device(a.h_up, d_up, a.stream);
+        if (rc) return rc;
+    }
 
     // ---- launch ----------------------------------------------------------------------------------------------------------------------
     uint64_t *h_msg = reinterpret_cast<uint64_t *>(a.h_page);
     uint32_t *h_giveup = reinterpret_cast<uint32_t *>(a.h_page + msg_bytes);
     uint64_t *h_mail = reinterpret_cast<uint64_t *>(a.h_page + msg_bytes + giveup_bytes);
-    scd::BatchArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.tables = reinterpret_cast<const uint4 *const *>(d_up);
-    A.Wm = reinterpret_cast<const uint4 *>(d_up + ptr_bytes);
-    A.w_stride = s.w_elems;
-    A.n = n;
-    A.n_tables = s.U;
-    A.nv = s.nv;
-    A.n_combos = s.n_combos;
-    A.K = (int)s.K;
-    A.D = (int)s.D;
-    A.ticket = reinterpret_cast<uint32_t *>(a.d_buf);
-    A.h_msg = reinterpret_cast<uint64_t *>(a.h_page_dev);
-    A.h_giveup = reinterpret_cast<uint32_t *>(a.h_page_dev + msg_bytes);
-    A.mail = vram ? a.d_vmail : reinterpret_cast<const uint64_t *>(a.h_page_dev + msg_bytes + giveup_bytes);
-    A.mail_local = vram ? 1u : 0u;
-    A.tag0 = tag0;
-    A.max_spins = scd::wait_spins_default();
+    BatchPages pg;
+    pg.d_up = d_up;
+    pg.ticket = reinterpret_cast<uint32_t *>(a.d_buf);
+    pg.h_msg = reinterpret_cast<uint64_t *>(a.h_page_dev);
+    pg.h_giveup = reinterpret_cast<uint32_t *>(a.h_page_dev + msg_bytes);
+    pg.mail = vram ? a.d_vmail : reinterpret_cast<const uint64_t *>(a.h_page_dev + msg_bytes + giveup_bytes);
+    pg.mail_local = vram ? 1u : 0u;
+    pg.tag0 = tag0;
+    pg.max_spins = scd::wait_spins_default();
     const int grid = (int)std::min<uint64_t>(n, (uint64_t)per_cu * (uint64_t)a.n_cus);
     static const bool trace = std::getenv("SC_HOST_TRACE") != nullptr; // stderr: one line per batch
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (trace && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) (void)hipGetLastError();
     if (ev0 && ev1) (void)hipEventRecord(ev0, a.stream);
-    HIP_TRY(scd::launch_batch_proofs(A, s.combo, s.fin, grid, a.stream));
+    HIP_TRY(job.launch(pg, grid, a.stream));
     if (ev0 && ev1) (void)hipEventRecord(ev1, a.stream);
-    scd::plan_hit(scd::kPlanBatchOneBlock);
+    scd::plan_hit(job.plan);
     *took = true;
     gate.release(); // the loop below makes no HIP calls
 
@@ -397,7 +409,7 @@ int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_nu
     std::vector<uint32_t> round(n, 0);
     for (uint32_t i = 0; i < n; ++i) {
         if (rngs_or_null) tr[i] = rngs_or_null[i]->rng;
-        tr[i].feed_poly_info(s.max_mult, s.nv); // mod.rs:54
+        if (job.poly_info) tr[i].feed_poly_info(job.max_mult, job.n_rounds); // mod.rs:54
     }
     auto post = [&](uint32_t i, uint32_t tag, uint32_t slot_ix, const sch::Fr &vm) { // tail_post_challenge's two forms, into the instance's own slots
         if (vram) {
@@ -439,14 +451,14 @@ int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_nu
                 }
                 continue;
             }
-            uint64_t *pm = out_proofs + ((size_t)i * s.nv + round[i]) * s.D * 4;
+            uint64_t *pm = out_proofs + ((size_t)i * job.n_rounds + round[i]) * job.D * 4;
             std::memcpy(pm, words, msg_words * 4);
             const auto h0 = trace ? clk::now() : clk::time_point();
-            tr[i].feed_prover_msg(reinterpret_cast<const sch::Fr *>(pm), s.D); // mod.rs:61
+            tr[i].feed_prover_msg(reinterpret_cast<const sch::Fr *>(pm), job.D); // mod.rs:61
             const sch::Fr vm = tr[i].sample_fr();                              // mod.rs:63
             if (trace) hash_us += std::chrono::duration<double, std::micro>(clk::now() - h0).count();
-            if (out_rand_or_null) std::memcpy(out_rand_or_null + ((size_t)i * s.nv + round[i]) * 4, &vm, 32);
-            if (++round[i] < s.nv) {
+            if (out_rand_or_null) std::memcpy(out_rand_or_null + ((size_t)i * job.n_rounds + round[i]) * 4, &vm, 32);
+            if (++round[i] < job.n_rounds) {
                 post(i, tag, (round[i] - 1) & 1u, vm);
             } else {
                 state[i] = kDone;
@@ -483,8 +495,8 @@ int run_batched(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_nu
         if (trace) {
             uint32_t gave_up = 0;
             for (uint32_t i = 0; i < n; ++i) gave_up += state[i] == kGaveUp;
-            std::fprintf(stderr, "[sc] batch: n %u, nv %u, plan batch.one_block, grid %d (%d per CU), mailbox %s, total %.1f us, kernel %.1f us, host hash %.1f us, gave up %u\n", n, s.nv,
-                         grid, per_cu, vram ? "vram" : "host", std::chrono::duration<double, std::micro>(clk::now() - t_begin).count(), ms * 1e3, hash_us, gave_up);
+            std::fprintf(stderr, "[sc] batch: n %u, %s %u, plan %s, grid %d (%d per CU), mailbox %s, total %.1f us, kernel %.1f us, host hash %.1f us, gave up %u\n", n, job.size_name,
+                         job.size, job.plan_name, grid, per_cu, vram ? "vram" : "host", std::chrono::duration<double, std::micro>(clk::now() - t_begin).count(), ms * 1e3, hash_us, gave_up);
         }
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -540,7 +552,67 @@ extern "C" int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *
         if (s.fits_args && scd::batch_shape_fits(s.nv, s.U, (int)s.K, (int)s.D, s.max_mult) && (pol == 2 || n >= batch_min_n(s))) {
             for (uint32_t k = 0; k < s.K; ++k) s.unit.push_back(unit_matrix(s.M[k], s.D));
             std::fill(state.begin(), state.end(), (uint8_t)kInFlight);
-            int rc = run_batched(descs, n, rngs_or_null, out_proofs, out_randomness_or_null, s, state, &took);
+            // the uploaded image: table pointers | per-instance weights | host tables
+            const bool host_tables = !(descs[0].flags & SC_TABLES_ON_DEVICE);
+            const size_t table_bytes = (size_t)32 << s.nv;
+            const size_t ptr_bytes = round_up((size_t)n * s.U * sizeof(void *), 256), w_bytes = round_up((size_t)n * s.w_elems * 32, 256);
+            BatchJob job;
+            job.n = n;
+            job.n_rounds = s.nv;
+            job.D = s.D;
+            job.poly_info = true;
+            job.max_mult = s.max_mult;
+            job.inputs_on_device = !host_tables;
+            job.occ_key = ((uint64_t)s.nv << 48) | ((uint64_t)s.U << 32) | ((uint64_t)s.K << 16) | s.D;
+            job.plan = scd::kPlanBatchOneBlock;
+            job.plan_name = "batch.one_block";
+            job.size = s.nv;
+            job.up_bytes = ptr_bytes + w_bytes + (host_tables ? (size_t)n * s.U * table_bytes : 0);
+            job.blocks_per_cu = [&](int dev) { return scd::batch_blocks_per_cu(dev, s.nv, s.U, (int)s.K, (int)s.D); };
+            job.fill = [&](char *h_up, char *d_up) -> int {
+                const void **h_ptrs = reinterpret_cast<const void **>(h_up);
+                sch::Fr *h_w = reinterpret_cast<sch::Fr *>(h_up + ptr_bytes);
+                for (uint32_t i = 0; i < n; ++i) {
+                    for (uint32_t k = 0; k < s.K; ++k) {
+                        sch::Fr c;
+                        std::memcpy(&c, descs[i].coeffs + 4 * k, 32);
+                        if (sch::geq_p(c)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: coefficient %u is not a canonical field element", i, k);
+                    }
+                    instance_weights(s, descs[i].coeffs, h_w + (size_t)i * s.w_elems);
+                    for (uint32_t u = 0; u < s.U; ++u) {
+                        if (host_tables) {
+                            const size_t off = ptr_bytes + w_bytes + ((size_t)i * s.U + u) * table_bytes;
+                            std::memcpy(h_up + off, descs[i].tables[u], table_bytes);
+                            h_ptrs[(size_t)i * s.U + u] = d_up + off;
+                        } else {
+                            h_ptrs[(size_t)i * s.U + u] = descs[i].tables[u];
+                        }
+                    }
+                }
+                return SC_OK;
+            };
+            job.launch = [&](const BatchPages &pg, int grid, hipStream_t stream) -> hipError_t {
+                scd::BatchArgs A;
+                std::memset(&A, 0, sizeof(A));
+                A.tables = reinterpret_cast<const uint4 *const *>(pg.d_up);
+                A.Wm = reinterpret_cast<const uint4 *>(pg.d_up + ptr_bytes);
+                A.w_stride = s.w_elems;
+                A.n = n;
+                A.n_tables = s.U;
+                A.nv = s.nv;
+                A.n_combos = s.n_combos;
+                A.K = (int)s.K;
+                A.D = (int)s.D;
+                A.ticket = pg.ticket;
+                A.h_msg = pg.h_msg;
+                A.h_giveup = pg.h_giveup;
+                A.mail = pg.mail;
+                A.mail_local = pg.mail_local;
+                A.tag0 = pg.tag0;
+                A.max_spins = pg.max_spins;
+                return scd::launch_batch_proofs(A, s.combo, s.fin, grid, stream);
+            };
+            int rc = run_batched(job, rngs_or_null, out_proofs, out_randomness_or_null, state, &took);
             if (rc) return rc;
             if (!took) std::fill(state.begin(), state.end(), (uint8_t)kGaveUp);
         }
@@ -571,6 +643,193 @@ extern "C" int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *
     }
     if (trace)
         std::fprintf(stderr, "[sc] batch: n %u, nv %u, plan batch.serial (%u instances%s), total %.1f us\n", n, nv, todo, took ? ", after an expired device-side wait" : "",
+                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    return SC_OK;
+}
+
+// ---- sc_gkr_prove_batch ---------------------------------------------------------------------------------------------------------------
+namespace {
+// The smallest n the batched kernel takes under policy "batch" = 1 (profiles/gkr_batch_bench.json; compare batch_min_n).  Measured
+// at dim 6 / 8 / 9 with nnz = 2 x 2^dim, device-resident inputs: ONE sc_gkr_prove costs 261 / 337 / 390 us (two initialisations with their
+// launches and synchronisations, 2 x dim latency-bound rounds), a batched call of one instance 165 / 207 / 245 us (upload, the index check's
+// round trip, the launch, 2 x dim round trips, the drain), and every further instance adds 13 / 17 / 20 us -- the host's one-thread
+// transcript at 0.85 us per instance and round.  The kernel is ahead from n = 1 on at every dim of its envelope: there is no crossover.
+uint32_t gkr_batch_min_n(uint32_t dim) {
+    (void)dim;
+    return 1;
+}
+} // namespace
+
+extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
+                                  const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags, uint64_t *out_proofs, uint64_t *out_uv_or_null) {
+    if (n == 0) return SC_OK;
+    // ---- everything the host can check, before any HIP call (sc_gkr_prove's checks, per instance: the lowest failing instance decides) ----
+    if (!rngs || !f1_idx || !f1_vals || !nnz || !f2 || !f3 || !g || !out_proofs) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: null argument");
+    if (dim == 0) return sc_internal_fail(SC_ERR_CONSTANT_POLY, "instance 0: Attempt to prove a constant.");
+    if (dim > 21) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim %u: 3*dim index bits do not fit 64-bit indices", dim);
+    const bool dev_in = flags & SC_TABLES_ON_DEVICE;
+    uint64_t nnz_max = 0;
+    {
+        std::unordered_set<const sc_rng *> seen;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!rngs[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null rng", i);
+            if (!seen.insert(rngs[i]).second) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: its rng is also an earlier instance's: every instance continues a transcript of its own", i);
+            if (nnz[i] >= (1ULL << 32)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz too large", i);
+            if ((nnz[i] && (!f1_idx[i] || !f1_vals[i])) || !f2[i] || !f3[i] || !g[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null argument", i);
+            for (uint32_t k = 0; k < dim; ++k) {
+                sch::Fr e;
+                std::memcpy(&e, g[i] + 4 * k, 32);
+                if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: g[%u] is not a canonical field element", i, k);
+            }
+            if (!dev_in)
+                for (uint64_t k = 0; k < nnz[i]; ++k)
+                    if ((f1_idx[i][k] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 index %llu out of range", i, (unsigned long long)k);
+            nnz_max = std::max(nnz_max, nnz[i]);
+        }
+    }
+    if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
+    static const bool trace = std::getenv("SC_HOST_TRACE") != nullptr;
+    const size_t N = (size_t)1 << dim;
+    std::vector<uint8_t> state(n, kGaveUp); // (what the serial plan below proves)
+    bool took = false;
+    const int64_t pol = scd::policy(scd::kPolBatch);
+    if (pol != 0 && scd::gkr_batch_shape_fits(dim, nnz_max) && (pol == 2 || n >= gkr_batch_min_n(dim))) {
+        // both phases are one product of two tables with a coefficient of one (start_phase{1,2}_sumcheck, mod.rs:45-54, 66-82)
+        const uint32_t offs[2] = {0, 2}, idx2[2] = {0, 1};
+        sc_poly_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.num_vars = dim;
+        d.max_multiplicands = 2;
+        d.n_products = 1;
+        d.coeffs = sch::kOne.l;
+        d.prod_offsets = offs;
+        d.prod_indices = idx2;
+        d.n_tables = 2;
+        SharedMeta s;
+        build_shared(&d, s);
+        s.unit.push_back(unit_matrix(2, 3));
+        // the uploaded image: instance records | the matrices | the index check's flags | the points g | host inputs, each distinct array once
+        // (one wiring predicate for many data instances is the usual case)
+        const size_t rec_bytes = round_up((size_t)n * sizeof(scd::GkrBatchInst), 256), w_bytes = round_up((size_t)s.w_elems * 32, 256);
+        const size_t flag_bytes = round_up((size_t)n * 4, 256), g_bytes = round_up((size_t)n * dim * 32, 256);
+        const size_t rec_off = 0, w_off = rec_bytes, flag_off = w_off + w_bytes, g_off = flag_off + flag_bytes, stage_off = g_off + g_bytes;
+        struct Staged {
+            const void *src;
+            size_t bytes, off;
+        };
+        std::vector<Staged> staged;
+        std::map<std::pair<const void *, size_t>, size_t> where;
+        size_t stage_bytes = 0;
+        auto stage = [&](const void *src, size_t bytes) -> size_t { // offset of the array's copy in the image
+            auto it = where.find({src, bytes});
+            if (it != where.end()) return it->second;
+            const size_t off = stage_off + stage_bytes;
+            staged.push_back({src, bytes, off});
+            where.emplace(std::make_pair(src, bytes), off);
+            stage_bytes += round_up(bytes, 32);
+            return off;
+        };
+        std::vector<size_t> offs_in; // per instance: idx, vals, f2, f3 (host inputs)
+        if (!dev_in) {
+            offs_in.resize((size_t)n * 4);
+            for (uint32_t i = 0; i < n; ++i) {
+                offs_in[4 * (size_t)i + 0] = nnz[i] ? stage(f1_idx[i], (size_t)nnz[i] * 8) : stage_off;
+                offs_in[4 * (size_t)i + 1] = nnz[i] ? stage(f1_vals[i], (size_t)nnz[i] * 32) : stage_off;
+                offs_in[4 * (size_t)i + 2] = stage(f2[i], N * 32);
+                offs_in[4 * (size_t)i + 3] = stage(f3[i], N * 32);
+            }
+        }
+        BatchJob job;
+        job.n = n;
+        job.n_rounds = 2 * dim;
+        job.D = 3;
+        job.poly_info = false;
+        job.inputs_on_device = dev_in;
+        job.occ_key = (1ULL << 63) | dim;
+        job.plan = scd::kPlanBatchGkrOneBlock;
+        job.plan_name = "batch.gkr_one_block";
+        job.size_name = "dim";
+        job.size = dim;
+        job.up_bytes = stage_off + stage_bytes;
+        job.blocks_per_cu = [&](int dv) { return scd::gkr_batch_blocks_per_cu(dv, dim); };
+        job.fill = [&](char *h_up, char *d_up) -> int {
+            scd::GkrBatchInst *rec = reinterpret_cast<scd::GkrBatchInst *>(h_up + rec_off);
+            instance_weights(s, sch::kOne.l, reinterpret_cast<sch::Fr *>(h_up + w_off));
+            std::memset(h_up + flag_off, 0, flag_bytes);
+            for (const Staged &st : staged) std::memcpy(h_up + st.off, st.src, st.bytes);
+            for (uint32_t i = 0; i < n; ++i) {
+                std::memcpy(h_up + g_off + (size_t)i * dim * 32, g[i], (size_t)dim * 32);
+                scd::GkrBatchInst &r = rec[i];
+                r.nnz = nnz[i];
+                r.g = reinterpret_cast<const uint4 *>(d_up + g_off + (size_t)i * dim * 32);
+                if (dev_in) {
+                    r.idx = f1_idx[i];
+                    r.vals = reinterpret_cast<const uint4 *>(f1_vals[i]);
+                    r.f2 = reinterpret_cast<const uint4 *>(f2[i]);
+                    r.f3 = reinterpret_cast<const uint4 *>(f3[i]);
+                } else {
+                    r.idx = reinterpret_cast<const uint64_t *>(d_up + offs_in[4 * (size_t)i + 0]);
+                    r.vals = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 1]);
+                    r.f2 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 2]);
+                    r.f3 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 3]);
+                }
+            }
+            return SC_OK;
+        };
+        if (dev_in) // the lists are device memory: their indices are checked there, in front of the launch (the kernel itself masks every index it uses)
+            job.check_on_device = [&](char *h_up, char *d_up, hipStream_t stream) -> int {
+                HIP_TRY(scd::launch_batch_gkr_idx_range(reinterpret_cast<const scd::GkrBatchInst *>(d_up + rec_off), n, dim, reinterpret_cast<uint32_t *>(d_up + flag_off), stream));
+                HIP_TRY(hipMemcpyAsync(h_up + flag_off, d_up + flag_off, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                const uint32_t *fl = reinterpret_cast<const uint32_t *>(h_up + flag_off);
+                for (uint32_t i = 0; i < n; ++i)
+                    if (fl[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
+                return SC_OK;
+            };
+        job.launch = [&](const BatchPages &pg, int grid, hipStream_t stream) -> hipError_t {
+            scd::BatchGkrArgs A;
+            std::memset(&A, 0, sizeof(A));
+            A.inst = reinterpret_cast<const scd::GkrBatchInst *>(pg.d_up + rec_off);
+            A.Wm = reinterpret_cast<const uint4 *>(pg.d_up + w_off);
+            A.n = n;
+            A.dim = dim;
+            A.ticket = pg.ticket;
+            A.h_msg = pg.h_msg;
+            A.h_giveup = pg.h_giveup;
+            A.mail = pg.mail;
+            A.mail_local = pg.mail_local;
+            A.tag0 = pg.tag0;
+            A.max_spins = pg.max_spins;
+            return scd::launch_batch_gkr(A, s.combo, s.fin, grid, stream);
+        };
+        std::fill(state.begin(), state.end(), (uint8_t)kInFlight);
+        int rc = run_batched(job, rngs, out_proofs, out_uv_or_null, state, &took);
+        if (rc) return rc;
+        if (!took) std::fill(state.begin(), state.end(), (uint8_t)kGaveUp);
+    }
+    // ---- the serial plan: everything (nothing ran batched), or the instances whose block gave up waiting -- those with device-side waits
+    // off.  The callers' transcripts are worked on as copies and written back once every instance has been proved.
+    uint32_t todo = 0;
+    for (uint32_t i = 0; i < n; ++i) todo += state[i] != kDone;
+    if (todo == 0) return SC_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!took) scd::plan_hit(scd::kPlanBatchGkrSerial);
+    std::vector<std::pair<uint32_t, sc_rng>> work;
+    work.reserve(todo);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (state[i] == kDone) continue;
+        work.emplace_back(i, *rngs[i]);
+        int rc = sc_internal_gkr_prove(&work.back().second, f1_idx[i], f1_vals[i], nnz[i], dim, f2[i], f3[i], g[i], flags, out_proofs + (size_t)i * 2 * dim * 12,
+                                       out_uv_or_null ? out_uv_or_null + (size_t)i * 2 * dim * 4 : nullptr, took);
+        if (rc) {
+            const std::string why = sc_last_error();
+            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+        }
+        if (took) g_stat[kStatProofRetries].fetch_add(1, std::memory_order_relaxed);
+    }
+    for (auto &w : work) rngs[w.first]->rng = w.second.rng;
+    if (trace)
+        std::fprintf(stderr, "[sc] batch: n %u, dim %u, plan batch.gkr_serial (%u instances%s), total %.1f us\n", n, dim, todo, took ? ", after an expired device-side wait" : "",
                      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
     return SC_OK;
 }

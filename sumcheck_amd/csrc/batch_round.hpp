@@ -1,0 +1,187 @@
+// batch_round.hpp -- the round body of the batched kernels: one block holds ALL tables of an instance in LDS as nine 29-bit limbs and
+// runs a sumcheck round out of them -- the poll of the instance's own mailbox slot (the poll is the fetch), the bind in place, the sums
+// per (product, node) combination, the block reduction, finalize_message from the instance's matrices and the publication as
+// self-validating words (limb | tag << 32).  Used by k_batch_proofs (kernels_batch.hip: sc_ml_prove_batch) and by k_batch_gkr
+// (kernels_batch_gkr.hip: sc_gkr_prove_batch), which runs it twice per instance over tables it has built in LDS itself.
+#pragma once
+#include "finalize_device.hpp"
+#include "kernel_common.hpp"
+
+namespace scd {
+
+// (an element in LDS: k_tail_slices' 48-byte slot)
+constexpr int kBtEnt = 12;
+constexpr size_t kBtLdsMax = 144 * 1024; // k_tail_slices' budget (kTsLdsMax): of the CU's 160 KB
+__device__ __forceinline__ Fe bt_lds_load(const int32_t *t) {
+    const int4 a = *reinterpret_cast<const int4 *>(t), b = *reinterpret_cast<const int4 *>(t + 4), c = *reinterpret_cast<const int4 *>(t + 8);
+    Fe r;
+    r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+    r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+    r.l[8] = c.x;
+    return r;
+}
+__device__ __forceinline__ void bt_lds_store(int32_t *t, const Fe &v) {
+    *reinterpret_cast<int4 *>(t) = make_int4(v.l[0], v.l[1], v.l[2], v.l[3]);
+    *reinterpret_cast<int4 *>(t + 4) = make_int4(v.l[4], v.l[5], v.l[6], v.l[7]);
+    t[8] = v.l[8];
+}
+__device__ __forceinline__ Fe bt_shfl_down(const Fe &a, const int off) {
+    Fe r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.l[i] = __shfl_down(a.l[i], off, 64);
+    return r;
+}
+
+// what the round body needs of the block and of the instance it holds (every member wave-uniform)
+struct BtBlock {
+    uint4 *fin_lds;              // finalize_message's scratch
+    uint4 *msg_lds;              // the round's message
+    int32_t *tabs;               // [table][cap][kBtEnt]
+    uint64_t *r_sh;              // __shared__, 4 words: the challenge just fetched
+    uint32_t *stop_sh;           // __shared__: the block drops the instance
+    const Combo *combo_sh;       // __shared__ copies of the launch's metadata
+    const int *prod_index_sh;
+    uint32_t cap;                // entries per table as loaded
+    int U, L, n_combos, K, D;
+    uint32_t mail_local, max_spins;
+    // the instance
+    const uint4 *Wm;
+    const uint64_t *mail;
+    uint64_t *h_msg;
+    uint32_t *h_giveup;          // the instance's own marker
+};
+// ... and of the lane: its (product, node) combination
+template <int kSlots>
+struct BtLane {
+    int my_combo, my_q;
+    bool combo_live;
+    int32_t my_nv;
+    uint32_t my_base[kSlots], my_exp[kSlots];
+};
+
+// The challenge behind the message published under `want`: the poll is the fetch (eight tagged words).  false: the wait expired, or the
+// host asked the block to drop the instance -- uniform; the give-up marker is raised (expired wait only) and every lane has passed
+// the barrier behind the stop word.  true: the challenge is in B.r_sh.
+__device__ __forceinline__ bool bt_fetch_challenge(const BtBlock &B, const uint32_t want, const uint32_t slot_ix) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const uint64_t *slot = B.mail + 8 * slot_ix;
+        const uint32_t spins_max = B.mail_local ? (B.max_spins > (0xffffffffu >> 3) ? 0xffffffffu : 8u * B.max_spins) : B.max_spins; // (a local poll is ~10x shorter than one over PCIe: same patience)
+        uint64_t w = 0;
+        bool seen = false;
+        for (uint32_t spin = 0; spin < spins_max; ++spin) {
+            if (tid < 8) w = __hip_atomic_load(slot + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const bool mine = tid >= 8 || (uint32_t)w == want;
+            if (__all(mine)) { seen = true; break; }
+            if (__any(tid == 0 && (uint32_t)w == (want ^ 0x80000000u))) break; // the host asks the block to drop this instance
+            __builtin_amdgcn_s_sleep(1);
+        }
+        if (!seen && tid == 0) {
+            __hip_atomic_store(B.h_giveup, want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            *B.stop_sh = 1;
+        }
+        const uint32_t lo32 = (uint32_t)(w >> 32);
+        const uint32_t hi32 = __shfl_down(lo32, 1, 64);
+        if (tid < 8 && (tid & 1) == 0) B.r_sh[tid >> 1] = (uint64_t)lo32 | ((uint64_t)hi32 << 32);
+    }
+    __syncthreads();
+    if (*B.stop_sh) { // (uniform: the whole block drops the instance and takes the next ticket)
+        __syncthreads(); // every lane has read the word before the ticket step clears it
+        return false;
+    }
+    return true;
+}
+
+// bind in place with the challenge in B.r_sh: entry e <- entries 2e, 2e + 1 of every table.  A pass reads everything it needs before it
+// writes (one barrier); later passes read higher entries than any earlier pass wrote (2 e'' > e for e'' > e).
+__device__ __forceinline__ void bt_bind(const BtBlock &B, uint32_t &E) {
+    const int tid = threadIdx.x;
+    FrHost rh;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rh.l[i] = B.r_sh[i];
+    const FeU r32 = feu_shl5(fru_from_host(rh).v); // the carry-free bind's multiplier: r * 2^5 as 29-bit limbs
+    const uint32_t half = E / 2, total = half * (uint32_t)B.U;
+    const int shH = 31 - __builtin_clz(half);
+    for (uint32_t i0 = 0; i0 < total; i0 += kTsBlock) {
+        const uint32_t i = i0 + tid;
+        const bool live = i < total;
+        const uint32_t u = live ? i >> shH : 0, e = live ? i & (half - 1) : 0;
+        int32_t *const tab = B.tabs + u * B.cap * (uint32_t)kBtEnt; // (32-bit index arithmetic: LDS)
+        Fe v = fe_zero();
+        if (live) {
+            const Fe lo = bt_lds_load(tab + 2 * e * (uint32_t)kBtEnt), hi = bt_lds_load(tab + (2 * e + 1) * (uint32_t)kBtEnt);
+            v = fe_carry_pass(fe_add(lo, fe_mul_u<true>(fe_sub(hi, lo), r32)));
+        }
+        __syncthreads();
+        if (live) bt_lds_store(tab + e * (uint32_t)kBtEnt, v);
+    }
+    E = half;
+    __syncthreads();
+}
+
+// the round's sums over the E entries still held, its message from the instance's matrices, and the message out under `tag`
+template <int kSlots, typename ProdFn>
+__device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kSlots> &ln, const ProdFn &prod_of, const uint32_t E, const uint32_t tag) {
+    const int tid = threadIdx.x;
+    // ---- sums: lane (combination, q) multiplies out the combination's pairs q, q + L, ... ----------------------------------------------
+    const uint32_t pairs_here = E / 2;
+    Fe acc = fe_zero();
+    if (ln.combo_live) {
+        const int32_t nv = ln.my_nv;
+        uint32_t iter = 0;
+        for (uint32_t pr = (uint32_t)ln.my_q; pr < pairs_here; pr += (uint32_t)B.L, ++iter) {
+            Fe prod = fe_zero();
+            bool first = true;
+#pragma unroll
+            for (int sl = 0; sl < kSlots; ++sl) {
+                if (ln.my_exp[sl] == 0) break; // (slots are dense: the first empty one ends the list)
+                const int32_t *lo_p = B.tabs + (ln.my_base[sl] + 2 * pr) * (uint32_t)kBtEnt;
+                Fe val;
+                if (nv == 0) val = bt_lds_load(lo_p);
+                else if (nv == 1) val = bt_lds_load(lo_p + kBtEnt);
+                else val = fe_line(bt_lds_load(lo_p), bt_lds_load(lo_p + kBtEnt), nv);
+                uint32_t k = 0;
+                if (first) { prod = val; k = 1; first = false; }
+                for (const uint32_t e = ln.my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
+            }
+            acc = fe_carry_pass(fe_add(acc, prod));
+            if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31; never reached here)
+        }
+    }
+    for (int off = B.L >> 1; off >= 1; off >>= 1) acc = fe_carry_pass(fe_add(acc, bt_shfl_down(acc, off)));
+    if (ln.combo_live && ln.my_q == 0) fr_store(B.fin_lds + 2 * (B.prod_index_sh[ln.my_combo] * B.D + (int)B.combo_sh[ln.my_combo].t), fe_to_fr(acc));
+    __syncthreads();
+    // ---- the message, from the instance's own matrices, into LDS; then out as tagged words: every 8-byte word validates itself --------
+    finalize_message<kTsBlock>(prod_of, B.Wm, B.K, B.D, B.fin_lds, B.msg_lds, (uint64_t *)nullptr, (uint4 *)nullptr, (uint32_t *)nullptr, 0u, 1, (const Fr *)nullptr);
+    __syncthreads();
+    const uint32_t msg_words = (uint32_t)B.D * 8u;
+    if ((uint32_t)tid < msg_words) {
+        const uint32_t limb = reinterpret_cast<const uint32_t *>(B.msg_lds)[tid];
+        __hip_atomic_store(B.h_msg + tid, (uint64_t)limb | ((uint64_t)tag << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __syncthreads(); // (fin_lds and msg_lds are written again by the next round)
+}
+
+// the lane's combination, from the block's copy of the metadata (call behind the barrier that follows the copy)
+template <int kSlots>
+__device__ __forceinline__ BtLane<kSlots> bt_lane(const BtBlock &B, const uint32_t *slot_table_sh, const uint32_t *slot_exp_sh) {
+    BtLane<kSlots> ln;
+    const int tid = threadIdx.x;
+    ln.my_combo = tid / B.L;
+    ln.my_q = tid % B.L;
+    ln.combo_live = ln.my_combo < B.n_combos;
+    const Combo my_c = B.combo_sh[ln.combo_live ? ln.my_combo : 0];
+    ln.my_nv = node_value((int)my_c.t);
+#pragma unroll
+    for (int sl = 0; sl < kSlots; ++sl) {
+        const bool in = (uint32_t)sl < my_c.n_slots;
+        ln.my_base[sl] = in ? slot_table_sh[my_c.slot_off + sl] * B.cap : 0u;
+        ln.my_exp[sl] = in ? slot_exp_sh[my_c.slot_off + sl] : 0u;
+    }
+    return ln;
+}
+
+// finalize scratch | message: the head of a batched kernel's dynamic LDS
+inline size_t bt_fin_bytes(int K, int D) { return (((size_t)K * D * (D + 2) * 32 + 15) & ~(size_t)15) + (size_t)D * 32; }
+
+} // namespace scd

@@ -31,11 +31,13 @@
 #include "host_fr.hpp"
 #include "kernels.h"
 #include "transcript.hpp"
+#include "wide_cell.hpp"
 
 using scd::Fr;
 using scd::FrHost;
 using scd::FrU;
 using scd::kBlock;
+using scd::wide_fold_cell;
 
 int sc_internal_fail(int code, const char *fmt, ...); // abi.hip
 void sc_internal_gate_lock(int device);                // abi.hip: the device gate (serialises the library's HIP calls per device)
@@ -49,6 +51,9 @@ int sc_internal_run_rounds(sc_prover *p, sch::Blake2b512Rng &rng, uint32_t n_rou
 hipStream_t sc_internal_prover_stream(sc_prover *p);                                                  // abi.hip (GKR phase two: see there)
 const void *sc_internal_bound_table(sc_prover *p, uint32_t u);
 int sc_internal_scale_by_bound_table(sc_prover *p, const void *table, const sch::Fr &r_last);
+struct sc_rng;
+int sc_internal_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t *f1_vals, uint64_t nnz, uint32_t dim, const uint64_t *f2, const uint64_t *f3, const uint64_t *g,
+                          uint32_t flags, uint64_t *out_proof, uint64_t *out_uv_or_null, bool no_polling); // below; batch.hip's serial plan
 struct sc_rng {
     sch::Blake2b512Rng rng;
 };
@@ -218,28 +223,6 @@ __global__ __launch_bounds__(kBlock) void k_scatter_dense(const uint64_t *__rest
 // one workgroup per bucket of 2^c cells keeps the cells in LDS as eight uint64 lanes of 32-bit limbs each (the wide format of
 // the sharded path), adds every term with LDS integer atomics and reduces each cell mod p once at the end.  Global 64-bit atomics
 // on the dense table were measured first: 8.4 M of them take 0.4 ms on this part (profiles/r2d_gkr_init.txt), slower than sorting.
-__device__ __forceinline__ Fr wide_fold_cell(const uint64_t lane[8]) { // V = sum_j lane_j 2^(32 j) (lanes < 2^63) -> V mod p
-    Fr lo;
-    uint64_t carry = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint64_t t = lane[j] + carry; // < 2^63 + 2^32: no wrap
-        lo.v[j] = (uint32_t)t;
-        carry = t >> 32;
-    }
-    lo = scd::fr_reduce_once(scd::fr_reduce_once(lo)); // lo < 2^256 < 3p
-    // V = lo + carry * 2^256 and carry * 2^256 mod p = mont_mul(carry, R^2)
-    Fr hi = scd::fr_zero(), r2;
-    hi.v[0] = (uint32_t)carry;
-    hi.v[1] = (uint32_t)(carry >> 32);
-    const uint64_t R2[4] = {0xc999e990f3f29c6dULL, 0x2b6cedcb87925c23ULL, 0x05d314967254398fULL, 0x0748d9d99f59ff11ULL};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        r2.v[2 * q] = (uint32_t)R2[q];
-        r2.v[2 * q + 1] = (uint32_t)(R2[q] >> 32);
-    }
-    return scd::fr_add(lo, scd::fr_mul(hi, r2));
-}
 // eq(point, b) as the product of two small tables (k_eq_halves): b's low kl bits and the rest.  2 x 2^11 entries at most stay in
 // L2, where a 2^dim-entry table is a random 32-byte read from memory per non-zero.
 struct EqSplit {
@@ -1242,7 +1225,7 @@ extern "C" int sc_sparse_evaluate(const uint64_t *idx, const uint64_t *vals, uin
 // of prove_round / feed / sample (mod.rs:111-119,126-133).  The handle (stream, ping-pong buffers, pinned result page) is
 // created for phase one and rewound onto phase two's tables, so the second phase allocates nothing.
 static int run_phase(sch::Blake2b512Rng &rng, sc_prover **handle, const Fr *dA, const Fr *dB, uint32_t dim, uint64_t *out_msgs,
-                     sch::Fr *challenges, const std::function<int(sc_prover *)> *after_reset = nullptr) {
+                     sch::Fr *challenges, const std::function<int(sc_prover *)> *after_reset = nullptr, bool no_polling = false) {
     const uint64_t *tabs[2] = {reinterpret_cast<const uint64_t *>(dA), reinterpret_cast<const uint64_t *>(dB)};
     int rc;
     if (*handle == nullptr) {
@@ -1263,6 +1246,7 @@ static int run_phase(sch::Blake2b512Rng &rng, sc_prover **handle, const Fr *dA, 
         rc = sc_prover_reset(*handle, tabs, SC_TABLES_ON_DEVICE);
     }
     if (rc) return rc;
+    if (no_polling && (rc = sc_prover_set_polling(*handle, 0))) return rc; // (sc_gkr_prove_batch's retry of an instance whose device-side wait expired)
     if (after_reset && (rc = (*after_reset)(*handle))) return rc; // (phase two: the coefficient f2(u), on the handle's stream)
     return sc_internal_run_rounds(*handle, rng, dim, out_msgs, challenges); // prove_round / feed / sample x dim (late rounds pipelined)
 }
@@ -1368,6 +1352,7 @@ struct ProverGuard { // declared AFTER the DevBuf it pairs with, so it is destro
     sc_prover *p = nullptr;
     uint32_t dim = 0;
     bool cacheable = false;
+    bool polling_off = false; // the call switched the handle's device-side waits off: the next owner starts with them on
     void take_cached(uint32_t d, bool leased) {
         dim = d;
         cacheable = leased;
@@ -1378,6 +1363,7 @@ struct ProverGuard { // declared AFTER the DevBuf it pairs with, so it is destro
     }
     ~ProverGuard() {
         if (!p) return;
+        if (polling_off) (void)sc_prover_set_polling(p, 1);
         if (cacheable && t_holds_cache) {
             if (g_cache.prover) sc_prover_free(g_cache.prover);
             g_cache.prover = p;
@@ -1391,6 +1377,11 @@ struct ProverGuard { // declared AFTER the DevBuf it pairs with, so it is destro
 
 extern "C" int sc_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t *f1_vals, uint64_t nnz, uint32_t dim, const uint64_t *f2,
                             const uint64_t *f3, const uint64_t *g, uint32_t flags, uint64_t *out_proof, uint64_t *out_uv_or_null) {
+    return sc_internal_gkr_prove(rng, f1_idx, f1_vals, nnz, dim, f2, f3, g, flags, out_proof, out_uv_or_null, false);
+}
+// no_polling: every round of both phases launched after its challenge (batch.hip: the serial plan's retry of an instance whose block gave up waiting)
+int sc_internal_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t *f1_vals, uint64_t nnz, uint32_t dim, const uint64_t *f2, const uint64_t *f3, const uint64_t *g,
+                          uint32_t flags, uint64_t *out_proof, uint64_t *out_uv_or_null, bool no_polling) {
     if (!rng || (nnz && (!f1_idx || !f1_vals)) || !f2 || !f3 || !g || !out_proof) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
     GkrGate gate_;
     int rc = check_gkr_args(nnz, dim);
@@ -1485,11 +1476,12 @@ extern "C" int sc_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t 
     std::vector<sch::Fr> u(dim), v(dim);
     ProverGuard pg;
     pg.take_cached(dim, mem.leased);
+    pg.polling_off = no_polling;
     // (phase one's sumcheck runs on the prover's stream, which is not ordered behind `s`: the host waits.  Ordering the prover's stream behind an
     // event on `s` instead was measured in round 6: the cross-queue dependency costs more than the wake-up it saves, 1.02 against 0.98 ms)
     G_TRY(hipStreamSynchronize(s));
     lap("phase one init");
-    if ((rc = run_phase(rng->rng, &pg.p, d_hg, d_f2, dim, out_proof, u.data()))) return rc; // mod.rs:107-119
+    if ((rc = run_phase(rng->rng, &pg.p, d_hg, d_f2, dim, out_proof, u.data(), nullptr, no_polling))) return rc; // mod.rs:107-119
     lap("phase one sumcheck");
     // f2.evaluate(&u) (mod.rs:122) is not recomputed: phase one's prover has bound f2 at u_0..u_{dim-2} (prover.rs:84-89), its final table {lo, hi}
     // gives f2(u) = lo + u_last (hi - lo); and f3 is not multiplied by it (mod.rs:71-75): the scalar becomes phase two's coefficient, on the
@@ -1529,7 +1521,7 @@ extern "C" int sc_gkr_prove(sc_rng *rng, const uint64_t *f1_idx, const uint64_t 
         scd::plan_hit(scd::kPlanGkrCoeffFromBound);
         return sc_internal_scale_by_bound_table(hp, f2_bound, u_last);
     };
-    if ((rc = run_phase(rng->rng, &pg.p, d_f1gu, d_f3, dim, out_proof + (size_t)dim * 12, v.data(), &coeff))) return rc; // mod.rs:122-133
+    if ((rc = run_phase(rng->rng, &pg.p, d_f1gu, d_f3, dim, out_proof + (size_t)dim * 12, v.data(), &coeff, no_polling))) return rc; // mod.rs:122-133
     lap("phase two sumcheck");
     if (out_uv_or_null) {
         std::memcpy(out_uv_or_null, u.data(), (size_t)dim * 32);

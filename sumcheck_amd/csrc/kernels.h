@@ -237,6 +237,37 @@ struct BatchArgs {
 bool batch_shape_fits(uint32_t nv, uint32_t n_tables, int K, int D, uint32_t max_multiplicands); // the envelope: one block's LDS, products of <= kMaxFusedM
 int batch_blocks_per_cu(int device, uint32_t nv, uint32_t n_tables, int K, int D);             // occupancy of k_batch_proofs at that LDS size (0: unknown)
 hipError_t launch_batch_proofs(BatchArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream);
+// Batched GKR round proofs (kernels_batch_gkr.hip: k_batch_gkr): n independent instances of GKRRoundSumcheck::prove of one dim, ONE block per
+// instance: both initialisations into LDS (wide integer cells, LDS atomics), then 2 x dim rounds of k_batch_proofs' round body
+// (batch_round.hpp) over one product of two tables.  The envelope: dim <= kGkrBatchMaxDim (tables 2 x 48 B, eq(g, .) and eq(u, .) 2 x 32 B, the
+// accumulator 64 B per cell: 208 B x 2^dim + finalize scratch <= 144 KB; dim = 10 does not fit even with the eq tables as halves), and
+// nnz <= kGkrBatchMaxNnzPerCell x 2^dim per instance (one block of 256 lanes walks the list twice: beyond that sc_gkr_prove's grids win).
+constexpr int kGkrBatchMaxDim = 9;
+constexpr uint64_t kGkrBatchMaxNnzPerCell = 64;
+struct GkrBatchInst { // device memory, one per instance; every pointer is device memory that is only read
+    const uint64_t *idx; // nnz indices (z, x, y): z in the low dim bits
+    const uint4 *vals;   // nnz values
+    const uint4 *f2, *f3; // 2^dim entries each
+    const uint4 *g;      // dim elements
+    uint64_t nnz;
+};
+struct BatchGkrArgs {
+    const GkrBatchInst *inst;
+    const uint4 *Wm;            // device: the node -> message matrices of one product of two tables with a coefficient of one (both copies)
+    uint32_t n, dim;
+    uint32_t *ticket;           // the rest as in BatchArgs; an instance publishes 2 x dim messages under tag0 .. tag0 + 2 dim - 1, and the
+    uint64_t *h_msg;            // challenge behind EVERY message but the last is fetched (the block needs u_{dim-1} to build phase two)
+    const uint64_t *mail;
+    uint32_t mail_local;
+    uint32_t *h_giveup;
+    uint32_t tag0;
+    uint32_t max_spins;
+    uint32_t fin_bytes;         // (filled in by the launcher)
+};
+bool gkr_batch_shape_fits(uint32_t dim, uint64_t nnz_max);
+int gkr_batch_blocks_per_cu(int device, uint32_t dim); // occupancy of k_batch_gkr at that LDS size (0: unknown)
+hipError_t launch_batch_gkr_idx_range(const GkrBatchInst *inst, uint32_t n, uint32_t dim, uint32_t *flags, hipStream_t stream); // flags[i] |= 1: an index of instance i has a bit at or above 3 dim
+hipError_t launch_batch_gkr(BatchGkrArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -254,7 +285,7 @@ enum PolicyKey {
     kPolWaitSpins,        // "wait_spins"         bound of a device-side wait for a challenge, in polls (default 2^22)
     kPolTail,             // "tail"               1: the persistent tail kernels; 0: latency-bound rounds as pipelined launches (what sharded RCCL rounds use)
     kPolStagedInit,       // "staged_init"        1: sc_prover_init over HOST tables copies them in chunks and computes round 1 under the copy (shapes of the merged big-round kernel, >= 2^18 entries)
-    kPolBatch,            // "batch"              sc_ml_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
+    kPolBatch,            // "batch"              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
     kPolCount
 };
 int64_t policy(int key);
@@ -302,6 +333,8 @@ enum Plan {
     kPlanFoldMulti,           // sc_poly_evaluate / sc_fix_variables (k_fold_multi)
     kPlanBatchOneBlock,       // sc_ml_prove_batch: k_batch_proofs, one block per instance, every round out of LDS
     kPlanBatchSerial,         // ... instance after instance on the kept prover (shapes beyond the envelope, small n, slot busy, device-side waits off)
+    kPlanBatchGkrOneBlock,    // sc_gkr_prove_batch: k_batch_gkr, one block per instance, both initialisations and 2 x dim rounds out of LDS
+    kPlanBatchGkrSerial,      // ... instance after instance through sc_gkr_prove (dim or nnz beyond the envelope, small n, slot busy, device-side waits off)
     kPlanCount
 };
 void plan_hit(int plan);

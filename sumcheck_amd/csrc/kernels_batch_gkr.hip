@@ -1,0 +1,222 @@
+// kernels_batch_gkr.hip -- many small GKR round proofs in one launch (k_batch_gkr): sc_gkr_prove_batch.
+//
+// GKRRoundSumcheck::prove (reference src/gkr_round_sumcheck/mod.rs:93-139) of a small instance is two initialisations and 2 x dim
+// latency-bound rounds; a caller with many small layers (or many copies of a sub-circuit) gains nothing from proving them one after the
+// other.  Here ONE block proves a whole instance out of LDS, every instance of the call in flight at once, the host only hashes and
+// answers (batch.hip) -- k_batch_proofs' scheme (kernels_batch.hip, the round body is shared: batch_round.hpp), with the two tables of
+// each phase BUILT in LDS by the block itself:
+//   load        f2 -> table 1 as nine 29-bit limbs; eq(g, .) over the 2^dim cells (two half tables by doubling, then their outer product);
+//   phase one   h_g[x] = sum over non-zeros (z, x, y) of eq(g,z) * v * f3[y]   (mod.rs:30-38): lanes stride over the non-zeros, each term
+//               is added into cell x of an LDS accumulator of eight uint64 lanes of 32-bit limbs with LDS atomic adds (k_bucket_accumulate's
+//               form, gkr.hip: exact in any order), the cells are folded mod p into table 0; then dim rounds over (h_g, f2);
+//   between     the LAST challenge of phase one is fetched as well and bound: the two remaining entries of f2 give f2(u) (what
+//               gkr.coeff_from_bound_table does on the host path); f3 is read again, scaled by f2(u) (mod.rs:71-75, literally), into table 1;
+//               eq(u, .) is built;
+//   phase two   f1_gu[y] = sum of eq(g,z) * eq(u,x) * v   (mod.rs:62) through the same accumulator into table 0; dim rounds over
+//               (f1_gu, f2(u) f3) under the tags tag0 + dim ..
+// Every index is masked to dim bits per component before it addresses LDS or f3: whatever the list holds, no access leaves the
+// instance's tables.  (An index with a bit at or above 3 dim is an argument error: k_batch_gkr_idx_range reports it in front of the launch.)
+#include <algorithm>
+
+#include "batch_round.hpp"
+#include "wide_cell.hpp"
+
+namespace scd {
+
+// eq(point, .) over dim variables into out[2^dim] (32-byte elements in LDS): precompute_eq's doubling (ark-poly: dp[b + 2^i] = dp[b] * g_i ;
+// dp[b] -= dp[b + 2^i]) on the two halves of the variables at once -- wavefront 0 the low kl, wavefront 1 the high kh -- then the outer
+// product.  Depth ceil(dim / 2) + 1 dependent products instead of dim.  tmp: 2^kl + 2^kh elements of scratch.  Ends behind a barrier.
+__device__ __forceinline__ void bg_build_eq(uint4 *out, uint4 *tmp, const uint4 *point, const uint32_t dim) {
+    const uint32_t tid = threadIdx.x, kl = (dim + 1) / 2, kh = dim - kl;
+    uint4 *lo = tmp, *hi = tmp + 2 * ((size_t)1 << kl);
+    if (tid == 0) fr_store(lo, fr_one());
+    if (tid == 64) fr_store(hi, fr_one());
+    __syncthreads();
+    for (uint32_t i = 0; i < kl; ++i) {
+        const uint32_t w = tid >> 6, t = tid & 63u;
+        if (w < 2 && t < (1u << i) && (w == 0 || i < kh)) {
+            uint4 *tab = w == 0 ? lo : hi;
+            const Fr a = fr_load(tab + 2 * t), m = fr_mul(a, fr_load(point + 2 * (w == 0 ? i : kl + i)));
+            fr_store(tab + 2 * (t + (1u << i)), m);
+            fr_store(tab + 2 * t, fr_sub(a, m));
+        }
+        __syncthreads();
+    }
+    for (uint32_t b = tid; b < (1u << dim); b += kTsBlock) {
+        const Fr l = fr_load(lo + 2 * (b & ((1u << kl) - 1u)));
+        fr_store(out + 2 * b, kh ? fr_mul(l, fr_load(hi + 2 * (b >> kl))) : l);
+    }
+    __syncthreads();
+}
+
+// kPhase 1: cell x, term eq(g,z) * v * f3[y]; kPhase 2: cell y, term eq(g,z) * eq(u,x) * v.  The cells (lane-major: cell[j << dim | c],
+// neighbouring cells in neighbouring banks) are zeroed, filled and folded into table `dst`.  Ends behind a barrier.
+template <int kPhase>
+__device__ __forceinline__ void bg_accumulate(uint64_t *cell, int32_t *dst, const GkrBatchInst &I, const uint32_t dim, const uint4 *eq_g, const uint4 *eq_u) {
+    const uint32_t tid = threadIdx.x, cap = 1u << dim, mask = cap - 1u;
+    for (uint32_t i = tid; i < 8u * cap; i += kTsBlock) cell[i] = 0;
+    __syncthreads();
+    for (uint64_t i = tid; i < I.nnz; i += kTsBlock) {
+        const uint64_t id = I.idx[i];
+        const uint32_t z = (uint32_t)id & mask, x = (uint32_t)(id >> dim) & mask, y = (uint32_t)(id >> (2 * dim)) & mask; // (masked: see the head of the file)
+        const Fr a = fr_mul(fr_load(eq_g + 2 * z), fr_load(I.vals + 2 * i));
+        const Fr t = kPhase == 1 ? fr_mul(a, fr_load(I.f3 + 2 * (size_t)y)) : fr_mul(a, fr_load(eq_u + 2 * x));
+        const uint32_t c = kPhase == 1 ? x : y;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) __hip_atomic_fetch_add(cell + (((uint32_t)j << dim) | c), (uint64_t)t.v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    for (uint32_t c = tid; c < cap; c += kTsBlock) {
+        uint64_t lane[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lane[j] = cell[((uint32_t)j << dim) | c];
+        bt_lds_store(dst + c * (uint32_t)kBtEnt, fe_from_fr(wide_fold_cell(lane)));
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, const ComboMeta meta, const FinMeta fin) {
+    constexpr int kSlots = 2; // one product of two tables
+    extern __shared__ uint4 dyn_lds[];
+    __shared__ uint64_t r_sh[4];
+    __shared__ uint32_t stop_sh, inst_sh;
+    __shared__ Combo combo_sh[kMetaCombos];
+    __shared__ uint32_t slot_table_sh[kMetaSlots], slot_exp_sh[kMetaSlots];
+    __shared__ int prod_index_sh[kMetaCombos];
+    __shared__ uint4 g_sh[2 * kGkrBatchMaxDim], u_sh[2 * kGkrBatchMaxDim]; // the points g and u
+    const int tid = threadIdx.x;
+    const uint32_t dim = A.dim, cap = 1u << dim;
+    for (int i = tid; i < kMetaCombos; i += kTsBlock) {
+        combo_sh[i] = meta.combo[i];
+        prod_index_sh[i] = 0; // (one product)
+    }
+    for (int i = tid; i < kMetaSlots; i += kTsBlock) {
+        slot_table_sh[i] = meta.slot_table[i];
+        slot_exp_sh[i] = meta.slot_exp[i];
+    }
+    auto prod_of = [&](int k) -> FinProd { return fin.prod[k]; };
+    // dynamic LDS: finalize scratch | message | tables 0, 1 (48 B per entry) | eq(g, .) | eq(u, .) (32 B per cell) | the accumulator (64 B per cell)
+    char *const lds = reinterpret_cast<char *>(dyn_lds);
+    BtBlock B;
+    B.fin_lds = dyn_lds;
+    B.msg_lds = reinterpret_cast<uint4 *>(lds + A.fin_bytes - 3u * 32u);
+    B.tabs = reinterpret_cast<int32_t *>(lds + A.fin_bytes);
+    uint4 *const eq_g = reinterpret_cast<uint4 *>(lds + A.fin_bytes + 2u * cap * (uint32_t)(kBtEnt * 4));
+    uint4 *const eq_u = eq_g + 2 * (size_t)cap;
+    uint64_t *const cell = reinterpret_cast<uint64_t *>(eq_u + 2 * (size_t)cap);
+    B.r_sh = r_sh;
+    B.stop_sh = &stop_sh;
+    B.combo_sh = combo_sh;
+    B.prod_index_sh = prod_index_sh;
+    B.cap = cap;
+    B.U = 2;
+    B.n_combos = 3;
+    B.K = 1;
+    B.D = 3;
+    B.L = 64; // three combinations of 64 lanes
+    B.mail_local = A.mail_local;
+    B.max_spins = A.max_spins;
+    B.Wm = A.Wm; // a coefficient of one: the same matrices for every instance
+    __syncthreads(); // (the metadata above)
+    const BtLane<kSlots> ln = bt_lane<kSlots>(B, slot_table_sh, slot_exp_sh);
+    int32_t *const tab0 = B.tabs, *const tab1 = B.tabs + cap * (uint32_t)kBtEnt;
+
+    for (;;) {
+        // ---- the next instance (the barrier also ends the previous instance's use of LDS) ----------------------------------------------
+        if (tid == 0) {
+            inst_sh = __hip_atomic_fetch_add(A.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            stop_sh = 0;
+        }
+        __syncthreads();
+        const uint32_t inst = inst_sh;
+        if (inst >= A.n) return;
+        const GkrBatchInst I = A.inst[inst];
+        B.mail = A.mail + (size_t)inst * 16;
+        B.h_msg = A.h_msg + (size_t)inst * 24;
+        B.h_giveup = A.h_giveup + inst;
+        // ---- f2 -> table 1, g, eq(g, .), phase one's table (mod.rs:30-38) ----------------------------------------------------------------
+        for (uint32_t e = tid; e < cap; e += kTsBlock) bt_lds_store(tab1 + e * (uint32_t)kBtEnt, fe_from_fr(fr_load(I.f2 + 2 * (size_t)e)));
+        if ((uint32_t)tid < 2 * dim) g_sh[tid] = I.g[tid];
+        __syncthreads();
+        bg_build_eq(eq_g, reinterpret_cast<uint4 *>(cell), g_sh, dim);
+        bg_accumulate<1>(cell, tab0, I, dim, eq_g, eq_u);
+        // ---- phase one: dim rounds over (h_g, f2); EVERY challenge is fetched, the last one too ------------------------------------------
+        uint32_t E = cap;
+        bool dropped = false;
+        for (uint32_t j = 0; j <= dim && !dropped; ++j) {
+            if (j > 0) {
+                if (!bt_fetch_challenge(B, A.tag0 + j - 1u, (j - 1u) & 1u)) {
+                    dropped = true;
+                    break;
+                }
+                if (tid < 4) reinterpret_cast<uint64_t *>(u_sh)[4 * (j - 1u) + tid] = r_sh[tid];
+                bt_bind(B, E); // (the barriers inside also publish u_sh)
+            }
+            if (j < dim) bt_sum_publish<kSlots>(B, ln, prod_of, E, A.tag0 + j);
+        }
+        if (dropped) continue;
+        // ---- between the phases: f2(u) is what is left of table 1; f3 * f2(u) -> table 1 (mod.rs:71-75); eq(u, .); f1(g, u, .) -> table 0 --
+        const Fr f2u = fe_to_fr(bt_lds_load(tab1));
+        __syncthreads(); // (every lane has read it)
+        for (uint32_t e = tid; e < cap; e += kTsBlock) bt_lds_store(tab1 + e * (uint32_t)kBtEnt, fe_from_fr(fr_mul(fr_load(I.f3 + 2 * (size_t)e), f2u)));
+        bg_build_eq(eq_u, reinterpret_cast<uint4 *>(cell), u_sh, dim);
+        bg_accumulate<2>(cell, tab0, I, dim, eq_g, eq_u);
+        // ---- phase two: dim rounds over (f1_gu, f2(u) f3), messages dim .. 2 dim - 1 -----------------------------------------------------
+        E = cap;
+        for (uint32_t r = 0; r < dim; ++r) {
+            const uint32_t j = dim + r;
+            if (r > 0) {
+                if (!bt_fetch_challenge(B, A.tag0 + j - 1u, (j - 1u) & 1u)) break;
+                bt_bind(B, E);
+            }
+            bt_sum_publish<kSlots>(B, ln, prod_of, E, A.tag0 + j);
+        }
+    }
+}
+
+// flags[i] |= 1 if instance i's list holds an index with a bit at or above 3 dim (device-resident lists: the check in front of the launch)
+__global__ __launch_bounds__(kBlock) void k_batch_gkr_idx_range(const GkrBatchInst *__restrict__ inst, const uint32_t n, const uint32_t bits, uint32_t *__restrict__ flags) {
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint64_t *idx = inst[i].idx;
+        const uint64_t nnz = inst[i].nnz;
+        bool bad = false;
+        for (uint64_t k = threadIdx.x; k < nnz; k += kBlock) bad |= (idx[k] >> bits) != 0;
+        if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags + i, 1u);
+    }
+}
+
+static size_t bg_lds_bytes(uint32_t dim) { return bt_fin_bytes(1, 3) + ((size_t)1 << dim) * (2 * kBtEnt * 4 + 2 * 32 + 64); }
+
+bool gkr_batch_shape_fits(uint32_t dim, uint64_t nnz_max) {
+    if (dim == 0 || dim > (uint32_t)kGkrBatchMaxDim) return false;
+    if (nnz_max > ((uint64_t)kGkrBatchMaxNnzPerCell << dim)) return false; // (one block walks the whole list twice)
+    return bg_lds_bytes(dim) <= kBtLdsMax;
+}
+static hipError_t batch_gkr_attr() { // (more dynamic LDS than the default 64 KB limit of a launch)
+    static bool done[64] = {};
+    return ensure_dynamic_lds(reinterpret_cast<const void *>(k_batch_gkr), (int)kBtLdsMax, done);
+}
+int gkr_batch_blocks_per_cu(int device, uint32_t dim) {
+    (void)device;
+    int per_cu = 0;
+    if (batch_gkr_attr() != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_gkr, kTsBlock, bg_lds_bytes(dim)) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return per_cu;
+}
+hipError_t launch_batch_gkr_idx_range(const GkrBatchInst *inst, uint32_t n, uint32_t dim, uint32_t *flags, hipStream_t stream) {
+    if (n == 0 || dim == 0 || 3 * dim >= 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_gkr_idx_range, dim3(std::min<uint32_t>(n, 1024u)), dim3(kBlock), 0, stream, inst, n, 3 * dim, flags);
+    return hipGetLastError();
+}
+hipError_t launch_batch_gkr(BatchGkrArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream) {
+    if (grid < 1 || args.n == 0 || !gkr_batch_shape_fits(args.dim, 0)) return hipErrorInvalidValue;
+    hipError_t e = batch_gkr_attr();
+    if (e != hipSuccess) return e;
+    args.fin_bytes = (uint32_t)bt_fin_bytes(1, 3);
+    hipLaunchKernelGGL(k_batch_gkr, dim3(grid), dim3(kTsBlock), bg_lds_bytes(args.dim), stream, args, meta, fin);
+    return hipGetLastError();
+}
+
+} // namespace scd

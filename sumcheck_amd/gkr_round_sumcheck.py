@@ -225,6 +225,45 @@ class GKRRoundSumcheck:
         return GKRProof([ProverMsg(proof[0, i].copy()) for i in range(dim)], [ProverMsg(proof[1, i].copy()) for i in range(dim)])
 
     @staticmethod
+    def prove_batch(rngs: Sequence[Blake2b512Rng], f1s: Sequence[SparseMultilinearExtension], f2s: Sequence[DenseMultilinearExtension],
+                    f3s: Sequence[DenseMultilinearExtension], gs, return_uv: bool = False):
+        """n independent GKRRoundSumcheck.prove of one dim in one library call (sc_gkr_prove_batch) -> a list of GKRProof, proof i bit for
+        bit prove(rngs[i], f1s[i], f2s[i], f3s[i], gs[i]) with rngs[i] continued accordingly -- with return_uv also the (n, 2, dim, 4)
+        array of the sampled (u, v).  The same object may stand for several instances (one wiring predicate f1 for many data instances).
+        Small instances (dim <= 9) are proved concurrently, a workgroup each, inside one kernel."""
+        n = len(rngs)
+        assert len(f1s) == n and len(f2s) == n and len(f3s) == n and len(gs) == n, "one f1, f2, f3 and g per rng"
+        if n == 0:
+            check(lib().sc_gkr_prove_batch(0, 0, None, None, None, None, None, None, None, 0, None, None))
+            return ([], np.zeros((0, 2, 0, 4), np.uint64)) if return_uv else []
+        dim = f2s[0].num_vars
+        ons = [m.on_device for m in list(f1s) + list(f2s) + list(f3s)]
+        dev = all(ons)
+        assert dev or not any(ons), "mixing host and device inputs is not supported"
+        g_arr = []
+        for i in range(n):
+            assert f2s[i].num_vars == dim and f3s[i].num_vars == dim and f1s[i].num_vars == 3 * dim, f"instance {i}: a batch has one dim"
+            g_arr.append(_np64(gs[i]).reshape(-1, 4))
+            assert g_arr[i].shape[0] == dim
+        if dev:
+            import torch
+            torch.cuda.current_stream(f2s[0].evaluations.device).synchronize()  # the library works on its own stream
+
+        def ptrs(vals):
+            return (C.c_void_p * n)(*[C.cast(v, C.c_void_p) for v in vals])
+
+        f1p = [f._ptrs() for f in f1s]
+        nnz = (C.c_uint64 * n)(*[f.nnz for f in f1s])
+        rows = max(dim, 1)
+        proofs = np.empty((n, 2, rows, 3, 4), dtype=np.uint64)
+        uv = np.empty((n, 2, rows, 4), dtype=np.uint64)
+        check(lib().sc_gkr_prove_batch(n, dim, ptrs([r._h for r in rngs]), ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz,
+                                       ptrs([_dense_ptr(m) for m in f2s]), ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]),
+                                       SC_TABLES_ON_DEVICE if dev else 0, _ptr(proofs), _ptr(uv)))
+        out = [GKRProof([ProverMsg(proofs[i, 0, j].copy()) for j in range(dim)], [ProverMsg(proofs[i, 1, j].copy()) for j in range(dim)]) for i in range(n)]
+        return (out, uv[:, :, :dim].copy()) if return_uv else out
+
+    @staticmethod
     def verify(rng: Blake2b512Rng, f2_num_vars: int, proof: GKRProof, claimed_sum) -> GKRRoundSumcheckSubClaim:
         """mod.rs:147-192"""
         dim = f2_num_vars
