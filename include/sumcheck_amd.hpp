@@ -12,6 +12,8 @@
 // binding itself is rust-shim/).  The reference's panic!s surface as sumcheck::Panic carrying the same message;
 // verifier rejection as sumcheck::Reject.  All prove_round work happens on the GPU inside the library.
 #pragma once
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -380,6 +382,38 @@ inline Fr evaluate(const ListOfProductsOfPolynomials &poly, const std::vector<Fr
     return out;
 }
 
+// n x ListOfProductsOfPolynomials::evaluate in one library call (sc_poly_evaluate_batch): polynomials of ONE structure, points[i] the
+// num_variables-element point of polynomial i (what its proof's subclaim ended on).  Value i is bit for bit evaluate(*polynomials[i],
+// points[i]); table_values_or_null: per instance the U table evaluations T_j(point).  After MLSumcheck::prove_batch a caller finishes
+// with this one call, not n.
+inline std::vector<Fr> evaluate_batch(const std::vector<const ListOfProductsOfPolynomials *> &polynomials, const std::vector<std::vector<Fr>> &points,
+                                      std::vector<std::vector<Fr>> *table_values_or_null = nullptr) {
+    const size_t n = polynomials.size();
+    if (points.size() != n) throw Panic(SC_ERR_BAD_ARG, "one point per polynomial");
+    std::vector<Fr> out(n);
+    if (table_values_or_null) table_values_or_null->assign(n, {});
+    if (n == 0) {
+        check(sc_poly_evaluate_batch(nullptr, 0, nullptr, nullptr, nullptr));
+        return out;
+    }
+    std::vector<std::unique_ptr<ListOfProductsOfPolynomials::Desc>> keep;
+    std::vector<sc_poly_desc> descs;
+    if (!polynomials[0]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+    const size_t nv = polynomials[0]->num_variables, U = polynomials[0]->flattened_ml_extensions.size();
+    std::vector<Fr> pts(std::max<size_t>(n * nv, 1)), tv(std::max<size_t>(n * U, 1));
+    for (size_t i = 0; i < n; ++i) {
+        if (!polynomials[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+        if (points[i].size() != nv) throw Panic(SC_ERR_BAD_ARG, "assertion failed: point.len() == num_variables");
+        keep.push_back(polynomials[i]->desc());
+        descs.push_back(keep.back()->d);
+        std::copy(points[i].begin(), points[i].end(), pts.begin() + i * nv);
+    }
+    check(sc_poly_evaluate_batch(descs.data(), (uint32_t)n, pts[0].l, out[0].l, tv[0].l));
+    if (table_values_or_null)
+        for (size_t i = 0; i < n; ++i) (*table_values_or_null)[i].assign(tv.begin() + i * U, tv.begin() + (i + 1) * U);
+    return out;
+}
+
 struct SparseMultilinearExtension {
     size_t num_vars = 0;
     std::vector<uint64_t> indices; // distinct
@@ -436,6 +470,54 @@ struct GKRRoundSumcheckSubClaim {
         check(sc_fr_elementwise(0, ab.l, c.l, abc.l, 1));
         return abc == expected_evaluation;
     }
+    // f1(g,u,v), f2(u), f3(v) and their product for n instances of ONE dim in one library call (sc_gkr_subclaim_batch): four elements per
+    // instance.  uv[i]: u then v (2 dim elements), as GKRRoundSumcheck::prove_batch returns them.  Pointers may repeat.
+    static std::vector<std::array<Fr, 4>> evaluate_subclaims_batch(const std::vector<const SparseMultilinearExtension *> &f1s,
+                                                                   const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                                   const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                                                                   const std::vector<std::vector<Fr>> &uv) {
+        const size_t n = f1s.size();
+        if (f2s.size() != n || f3s.size() != n || gs.size() != n || uv.size() != n) throw Panic(SC_ERR_BAD_ARG, "one f1, f2, f3, g and (u, v) per instance");
+        std::vector<std::array<Fr, 4>> out(n);
+        if (n == 0) {
+            check(sc_gkr_subclaim_batch(0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+            return out;
+        }
+        if (!f2s[0]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+        const size_t dim = f2s[0]->num_vars;
+        std::vector<const uint64_t *> idx(n), vals(n), p2(n), p3(n), pg(n);
+        std::vector<uint64_t> nnz(n);
+        std::vector<Fr> flat_uv(std::max<size_t>(n * 2 * dim, 1));
+        for (size_t i = 0; i < n; ++i) {
+            if (!f1s[i] || !f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f1s[i]->num_vars != 3 * dim || f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim || uv[i].size() != 2 * dim)
+                throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            idx[i] = f1s[i]->indices.data();
+            vals[i] = f1s[i]->values.empty() ? nullptr : f1s[i]->values[0].l;
+            nnz[i] = f1s[i]->indices.size();
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+            pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+            std::copy(uv[i].begin(), uv[i].end(), flat_uv.begin() + i * 2 * dim);
+        }
+        check(sc_gkr_subclaim_batch((uint32_t)n, (uint32_t)dim, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), flat_uv[0].l, 0, out[0][0].l));
+        return out;
+    }
+    // verify_subclaim of n subclaims of ONE dim in one library call: element i is subclaims[i].verify_subclaim(*f1s[i], *f2s[i], *f3s[i], gs[i])
+    static std::vector<bool> verify_subclaim_batch(const std::vector<GKRRoundSumcheckSubClaim> &subclaims, const std::vector<const SparseMultilinearExtension *> &f1s,
+                                                   const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s,
+                                                   const std::vector<std::vector<Fr>> &gs) {
+        std::vector<std::vector<Fr>> uv;
+        for (const GKRRoundSumcheckSubClaim &c : subclaims) {
+            uv.push_back(c.u);
+            uv.back().insert(uv.back().end(), c.v.begin(), c.v.end());
+        }
+        if (f1s.size() != subclaims.size()) throw Panic(SC_ERR_BAD_ARG, "one f1, f2, f3 and g per subclaim");
+        const auto ev = evaluate_subclaims_batch(f1s, f2s, f3s, gs, uv);
+        std::vector<bool> ok(subclaims.size());
+        for (size_t i = 0; i < subclaims.size(); ++i) ok[i] = ev[i][3] == subclaims[i].expected_evaluation;
+        return ok;
+    }
 };
 
 struct GKRRoundSumcheck {
@@ -478,6 +560,13 @@ struct GKRRoundSumcheck {
             pr.phase2_sumcheck_msgs.push_back(ProverMsg{std::vector<Fr>(flat.begin() + 3 * (dim + i), flat.begin() + 3 * (dim + i) + 3)});
         }
         return pr;
+    }
+    // the oracle queries behind prove_batch, in one library call (GKRRoundSumcheckSubClaim::evaluate_subclaims_batch)
+    static std::vector<std::array<Fr, 4>> evaluate_subclaims_batch(const std::vector<const SparseMultilinearExtension *> &f1s,
+                                                                   const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                                   const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                                                                   const std::vector<std::vector<Fr>> &uv) {
+        return GKRRoundSumcheckSubClaim::evaluate_subclaims_batch(f1s, f2s, f3s, gs, uv);
     }
     // n independent GKRRoundSumcheck::prove of ONE dim in one library call (sc_gkr_prove_batch): proof i is bit for bit
     // prove(*rngs[i], *f1s[i], *f2s[i], *f3s[i], gs[i]), and rngs[i] is continued accordingly.  Pointers may repeat (one wiring predicate f1

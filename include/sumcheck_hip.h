@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch and sc_gkr_prove_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch and sc_gkr_subclaim_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -368,6 +368,35 @@ SC_API int sc_poly_evaluate(const sc_poly_desc *desc, const uint64_t *point, uin
 SC_API int sc_sparse_evaluate(const uint64_t *idx, const uint64_t *vals, uint64_t nnz, uint32_t num_vars, const uint64_t *point,
                               uint64_t *out);
 
+/* ---- the oracle queries behind a batch of proofs ---------------------------------------------------------------------------------
+ * What a caller of sc_ml_prove_batch / sc_gkr_prove_batch does next -- evaluate every instance at the point its proof ended on -- in
+ * ONE call instead of n (or 3 n).  Within the envelope below the whole batch is one upload, one kernel launch (two for GKR, back to back),
+ * one copy back and one synchronisation; no kernel waits for the host.  Both calls are TOTAL over shapes: beyond the envelope, with policy
+ * "batch" = 0, or while a concurrent call holds the batch work areas, the instances run one after the other through sc_poly_evaluate /
+ * sc_sparse_evaluate inside the call, with the same bits.  Only argument errors fail: n == 0 is SC_OK and touches nothing; everything the
+ * host can check (null arrays or entries, non-canonical points / coefficients / g / uv, product indices out of range, structure
+ * mismatch, dim out of range, a host-resident f1 index with a bit at or above 3 dim) is checked before any HIP call, the lowest failing
+ * instance decides the status and sc_last_error() starts with "instance %u: ".  Work areas are sc_ml_prove_batch's (sc_release_caches). */
+/* n x ListOfProductsOfPolynomials::evaluate (data_structures.rs:99-109), one point per instance.  descs[i]: n descriptors of ONE
+ * structure (sc_ml_prove_batch's rule, check and error text); tables host or device per descs[0].flags, only read; a table pointer may
+ * repeat inside an instance or across instances.  points: n x num_vars x 4 limbs, instance-major; out_values: n x 4;
+ * out_table_values_or_null: n x U x 4.  num_vars == 0 is allowed.  Instance i's outputs are bit for bit what
+ * sc_poly_evaluate(&descs[i], points + i * num_vars * 4, ...) returns.  One workgroup per (instance, table) up to num_vars = 14. */
+SC_API int sc_poly_evaluate_batch(const sc_poly_desc *descs, uint32_t n, const uint64_t *points,
+                                  uint64_t *out_values, uint64_t *out_table_values_or_null);
+/* n x the three oracle queries of GKRRoundSumcheckSubClaim::verify_subclaim (data_structures.rs:33-56).  The input arrays are exactly
+ * sc_gkr_prove_batch's (pointers may repeat: one f1 may serve many instances; flags: SC_TABLES_ON_DEVICE as there); uv is the
+ * n x 2 x dim x 4 array sc_gkr_prove_batch writes as out_uv (host).  out_evals: n x 4 x 4 limbs -- f1(g,u,v), f2(u), f3(v) and their
+ * product, which is what the caller compares with expected_evaluation.  f1 as in sc_gkr_prove_batch: repeated indices add up, any order,
+ * zero values, nnz = 0 gives zero; for distinct indices f1(g,u,v) is bit for bit sc_sparse_evaluate at the point g | u | v, and f2(u),
+ * f3(v) are bit for bit sc_poly_evaluate of the one-table polynomial.  1 <= dim <= 21, else SC_ERR_BAD_ARG.  One workgroup per instance for
+ * dim <= 9 and nnz[i] <= 64 x 2^dim.  An out-of-range index in a device-resident list is found on the device in front of the launch
+ * (SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range"), never followed. */
+SC_API int sc_gkr_subclaim_batch(uint32_t n, uint32_t dim,
+                                 const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
+                                 const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
+                                 const uint64_t *uv, uint32_t flags, uint64_t *out_evals);
+
 /* The GKR entry points keep their device scratch (about 1 GB at dim = 20) and a two-table prover handle in a process-wide
  * cache between calls (allocating and freeing them costs more than a millisecond per call), sc_poly_evaluate / sc_fix_variables keep
  * their work areas (an eighth of the tables) and stream, and sc_ml_prove keeps the last prover it built (bound-table buffers of
@@ -401,7 +430,7 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "wait_spins" (2^22)      bound of a device-side wait for a challenge, in polls (tests shorten it to exercise the give-up path)
  *   "staged_init" (1)        0: sc_prover_init over HOST tables copies them whole before round 1 instead of in chunks with round 1 computed
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
- *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
+ *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
  *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);

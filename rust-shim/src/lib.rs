@@ -97,6 +97,9 @@ extern "C" {
     pub fn sc_prover_set_resident(p: *mut sc_prover, patience_polls: u32) -> c_int;
     pub fn sc_fix_variables(input: *const u64, nv: u32, point: *const u64, k: u32, out: *mut u64, flags: u32) -> c_int;
     pub fn sc_poly_evaluate(desc: *const sc_poly_desc, point: *const u64, out_value: *mut u64, out_table_values_or_null: *mut u64) -> c_int;
+    pub fn sc_poly_evaluate_batch(descs: *const sc_poly_desc, n: u32, points: *const u64, out_values: *mut u64, out_table_values_or_null: *mut u64) -> c_int;
+    pub fn sc_gkr_subclaim_batch(n: u32, dim: u32, f1_idx: *const *const u64, f1_vals: *const *const u64, nnz: *const u64, f2: *const *const u64,
+                                 f3: *const *const u64, g: *const *const u64, uv: *const u64, flags: u32, out_evals: *mut u64) -> c_int;
     pub fn sc_sparse_evaluate(idx: *const u64, vals: *const u64, nnz: u64, num_vars: u32, point: *const u64, out: *mut u64) -> c_int;
     pub fn sc_ml_prove(desc: *const sc_poly_desc, rng_or_null: *mut sc_rng, out_proof: *mut u64, out_state_or_null: *mut *mut sc_prover) -> c_int;
     pub fn sc_ml_prove_batch(descs: *const sc_poly_desc, n: u32, rngs_or_null: *const *mut sc_rng, out_proofs: *mut u64,
@@ -370,6 +373,27 @@ pub fn evaluate<F: Limbs4>(polynomial: &ListOfProductsOfPolynomials<F>, point: &
     F::from_limbs(out)
 }
 
+/// `polys.iter().zip(points).map(|(p, x)| p.evaluate(x))` for polynomials of ONE structure in one FFI call (`sc_poly_evaluate_batch`):
+/// what follows [`prove_batch`] -- one more call, not n.  `points[i]` is the point polynomial i's proof ended on.  Every value is bit for
+/// bit what [`evaluate`] returns for that polynomial and point.
+pub fn evaluate_batch<F: Limbs4>(polynomials: &[ListOfProductsOfPolynomials<F>], points: &[Vec<F>]) -> Vec<F> {
+    assert_eq!(polynomials.len(), points.len(), "one point per polynomial");
+    if polynomials.is_empty() {
+        return Vec::new();
+    }
+    let nv = polynomials[0].num_variables;
+    let flats: Vec<Flattened> = polynomials.iter().map(flatten).collect();
+    let descs: Vec<sc_poly_desc> = flats.iter().zip(polynomials).map(|(f, p)| f.desc(p.num_variables, p.max_multiplicands, 0)).collect();
+    let mut pts: Vec<[u64; 4]> = Vec::with_capacity(points.len() * nv);
+    for x in points {
+        assert_eq!(x.len(), nv, "wrong number of variables");
+        pts.extend(x.iter().map(|e| e.to_limbs()));
+    }
+    let mut out = vec![[0u64; 4]; polynomials.len()];
+    check(unsafe { sc_poly_evaluate_batch(descs.as_ptr(), descs.len() as u32, pts.as_ptr() as *const u64, out.as_mut_ptr() as *mut u64, core::ptr::null_mut()) });
+    out.into_iter().map(F::from_limbs).collect()
+}
+
 // ---- GKR round sumcheck (reference src/gkr_round_sumcheck/mod.rs) ------------------------------------------------------------
 /// `SparseMultilinearExtension.evaluations` (a map index -> value) as the two parallel arrays the C ABI takes
 fn sparse_arrays<F: Limbs4>(f: &SparseMultilinearExtension<F>) -> (Vec<u64>, Vec<[u64; 4]>) {
@@ -525,6 +549,55 @@ pub fn gkr_prove_batch<F: Limbs4>(instances: &mut [GkrInstance<F>]) -> Vec<HipGK
             }
         })
         .collect()
+}
+
+/// One instance of [`gkr_verify_subclaim_batch`]: the oracles of a GKR round, the point `g`, and what `GKRRoundSumcheck::verify`
+/// returned for its proof.
+pub struct GkrSubclaimInstance<'a, F: Limbs4> {
+    pub f1: &'a SparseMultilinearExtension<F>,
+    pub f2: &'a DenseMultilinearExtension<F>,
+    pub f3: &'a DenseMultilinearExtension<F>,
+    pub g: &'a [F],
+    pub u: &'a [F],
+    pub v: &'a [F],
+    pub expected_evaluation: F,
+}
+
+/// `GKRRoundSumcheckSubClaim::verify_subclaim` (reference `src/gkr_round_sumcheck/data_structures.rs:33-56`) for instances of ONE `dim`
+/// in one FFI call (`sc_gkr_subclaim_batch`): `f1(g,u,v) * f2(u) * f3(v) == expected_evaluation` per instance.  What follows
+/// [`gkr_prove_batch`] and the verifier -- one more call, not 3 n.
+pub fn gkr_verify_subclaim_batch<F: Limbs4>(instances: &[GkrSubclaimInstance<F>]) -> Vec<bool> {
+    if instances.is_empty() {
+        return Vec::new();
+    }
+    let dim = instances[0].f2.num_vars;
+    let n = instances.len();
+    let mut arrays = Vec::with_capacity(n);
+    let mut gls: Vec<Vec<[u64; 4]>> = Vec::with_capacity(n);
+    let mut uv: Vec<[u64; 4]> = Vec::with_capacity(n * 2 * dim);
+    for inst in instances.iter() {
+        assert_eq!(inst.f1.num_vars, 3 * dim);
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        assert_eq!(inst.u.len(), dim);
+        assert_eq!(inst.v.len(), dim);
+        arrays.push(sparse_arrays(inst.f1));
+        gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+        uv.extend(inst.u.iter().chain(inst.v.iter()).map(|x| x.to_limbs()));
+    }
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let f2: Vec<*const u64> = instances.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = instances.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = gls.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let mut evals = vec![[[0u64; 4]; 4]; n];
+    check(unsafe {
+        sc_gkr_subclaim_batch(n as u32, dim as u32, idx.as_ptr(), vals.as_ptr(), nnz.as_ptr(), f2.as_ptr(), f3.as_ptr(), g.as_ptr(), uv.as_ptr() as *const u64, 0,
+                              evals.as_mut_ptr() as *mut u64)
+    });
+    instances.iter().zip(&evals).map(|(inst, e)| e[3] == inst.expected_evaluation.to_limbs()).collect()
 }
 
 // ---- multi-GPU ------------------------------------------------------------------------------------------------------------------

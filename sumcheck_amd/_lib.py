@@ -107,6 +107,8 @@ SIGNATURES = {
     "sc_gkr_prove": (C.c_int, [_V, _V, _V, C.c_uint64, C.c_uint32, _V, _V, _V, C.c_uint32, _V, _V]),
     "sc_gkr_prove_batch": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V),
                                      C.c_uint32, _V, _V]),
+    "sc_poly_evaluate_batch": (C.c_int, [C.POINTER(PolyDesc), C.c_uint32, _V, _V, _V]),
+    "sc_gkr_subclaim_batch": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V), _V, C.c_uint32, _V]),
     "sc_dense_scale": (C.c_int, [_V, C.c_uint64, _V, _V, C.c_uint32]),
     "sc_gkr_phase_one_sharded": (C.c_int, [_V, _V, _V, C.c_uint64, C.c_uint32, _V, _V, C.c_uint32, _V, _V, _V, _V, u64p]),
     "sc_gkr_phase_two_sharded": (C.c_int, [_V, _V, _V, C.c_uint64, C.c_uint32, _V, C.c_uint32, _V, _V]),

@@ -1155,6 +1155,7 @@ constexpr const char *kPlanNames[scd::kPlanCount] = {
     "small.launched", "small.combos_table", "small.ptrs", "small.pipelined", "tail.slices8", "tail.slices12", "tail.rounds", "resident.slices",
     "resident.rounds", "sharded.rccl_direct", "sharded.rccl_publish", "sharded.host", "sharded.p2p", "sharded.gather_tail", "gkr.bucketed_grouped",
     "gkr.bucketed_counted", "gkr.list_form", "gkr.coeff_from_bound_table", "gkr.sharded", "fold_multi",
+    "batch.eval_one_block", "batch.eval_serial", "batch.gkr_eval_one_block", "batch.gkr_eval_serial",
     "batch.one_block", "batch.serial", "batch.gkr_one_block", "batch.gkr_serial",
 };
 } // namespace

@@ -114,6 +114,39 @@ struct AreaLease {
     }
 };
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the area on the calling thread's device, with its stream (the caller holds the lease and the device gate)
+int area_open(BatchArea &a, int dev) {
+    HIP_TRY(hipSetDevice(dev));
+    if (a.device != dev) {
+        a.free_all();
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        HIP_TRY(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
+        a.device = dev;
+        a.n_cus = prop.multiProcessorCount;
+        a.owner.device = dev;
+        a.owner.stream = a.stream;
+    }
+    return SC_OK;
+}
+// at least d_bytes of device memory and up_bytes of pinned host memory
+int area_reserve(BatchArea &a, size_t d_bytes, size_t up_bytes) {
+    if (a.d_cap < d_bytes) {
+        if (a.d_buf) (void)hipFree(a.d_buf);
+        a.d_buf = nullptr;
+        a.d_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.d_buf), d_bytes));
+        a.d_cap = d_bytes;
+    }
+    if (a.up_cap < up_bytes) {
+        if (a.h_up) (void)hipHostFree(a.h_up);
+        a.h_up = nullptr;
+        a.up_cap = 0;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a.h_up), up_bytes, hipHostMallocDefault));
+        a.up_cap = up_bytes;
+    }
+    return SC_OK;
+}
 
 // the structure every instance shares, as the kernels take it (prover_build's records: abi.hip)
 struct SharedMeta {
@@ -285,17 +318,7 @@ int run_batched(const BatchJob &job, sc_rng *const *rngs_or_null, uint64_t *out_
     BatchArea &a = g_area;
     const int dev = sc_internal_device_ref();
     GateHold gate(dev);
-    HIP_TRY(hipSetDevice(dev));
-    if (a.device != dev) {
-        a.free_all();
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, dev));
-        HIP_TRY(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
-        a.device = dev;
-        a.n_cus = prop.multiProcessorCount;
-        a.owner.device = dev;
-        a.owner.stream = a.stream;
-    }
+    if (int rc = area_open(a, dev)) return rc;
     if (!device_waits_allowed(a)) return SC_OK;
     if (a.occ_key != job.occ_key) {
         a.occ_val = job.blocks_per_cu(dev);
@@ -312,20 +335,7 @@ int run_batched(const BatchJob &job, sc_rng *const *rngs_or_null, uint64_t *out_
     const size_t up_bytes = job.up_bytes, d_bytes = 256 + up_bytes;
     const size_t msg_bytes = round_up((size_t)n * msg_words * 8, 256), giveup_bytes = round_up((size_t)n * 4, 256), mail_bytes = (size_t)n * 128;
     const size_t page_bytes = msg_bytes + giveup_bytes + mail_bytes;
-    if (a.d_cap < d_bytes) {
-        if (a.d_buf) (void)hipFree(a.d_buf);
-        a.d_buf = nullptr;
-        a.d_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.d_buf), d_bytes));
-        a.d_cap = d_bytes;
-    }
-    if (a.up_cap < up_bytes) {
-        if (a.h_up) (void)hipHostFree(a.h_up);
-        a.h_up = nullptr;
-        a.up_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a.h_up), up_bytes, hipHostMallocDefault));
-        a.up_cap = up_bytes;
-    }
+    if (int rc = area_reserve(a, d_bytes, up_bytes)) return rc;
     if (a.page_cap < page_bytes) {
         if (a.h_page) (void)hipHostFree(a.h_page);
         a.h_page = nullptr;
@@ -831,5 +841,360 @@ extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
     if (trace)
         std::fprintf(stderr, "[sc] batch: n %u, dim %u, plan batch.gkr_serial (%u instances%s), total %.1f us\n", n, dim, todo, took ? ", after an expired device-side wait" : "",
                      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    return SC_OK;
+}
+
+// ---- sc_poly_evaluate_batch, sc_gkr_subclaim_batch: the oracle queries behind a batch of proofs -------------------------------------------
+// What a caller of the two entry points above does next: evaluate every instance at the point its proof ended on.  Two plans, same bits:
+//   batch.eval_one_block / batch.gkr_eval_one_block   kernels_batch_eval.hip: the whole batch in one launch (GKR: two, back to back) over the
+//                    batch work areas -- one upload (pointers, points, host inputs: every distinct array once), the launch, one copy back,
+//                    one synchronisation; the K x M (GKR: two) scalar products per instance that combine the values are host work, as in
+//                    sc_poly_evaluate.  No kernel waits for the host: no mailbox, no tail slot;
+//   batch.eval_serial / batch.gkr_eval_serial         instance after instance through sc_poly_evaluate / sc_sparse_evaluate inside the call:
+//                    shapes beyond the kernels' envelope, policy "batch" = 0, the work areas held by a concurrent call.
+namespace {
+// The smallest n the kernels take under policy "batch" = 1 (profiles/eval_batch_bench.json; medians, us).  A batched call is one
+// upload, one or two launches, one copy back and one synchronisation whatever n: 27-39 us for ONE instance of the c2 / config-3 shapes at
+// 2^6 .. 2^10 entries (host or device tables) against 35-78 us for one sc_poly_evaluate, and 65 / 73 / 82 us for one GKR triple at dim 6 / 8 / 9
+// against 130 / 144 / 170 us for sc_sparse_evaluate + 2 x sc_poly_evaluate: ahead by more than both spreads from n = 1 on, there is no
+// handshake with the host to amortise.  Beyond 2^10 entries a lone table no longer hides behind the call's fixed cost -- ONE block per table
+// walks 2^14 entries in 65 us where sc_poly_evaluate's grids take 55 -- so a lone instance above nv = 10 goes to the serial plan (at nv = 12
+// the kernel's median is ahead, 37 against 49 us, but not by more than the spreads); at n = 16, the next measured size, the kernel is 13-20x
+// ahead there too (a whole call of 16 at nv = 14 costs 67 us, what the loop pays for little more than one instance).
+uint32_t eval_batch_min_n(uint32_t nv) { return nv <= 10 ? 1 : 16; }
+uint32_t gkr_eval_batch_min_n() { return 1; }
+
+struct StageMap { // host arrays behind one another in the image, every distinct (pointer, size) once
+    struct Item {
+        const void *src;
+        size_t bytes, off;
+    };
+    std::vector<Item> items;
+    std::map<std::pair<const void *, size_t>, size_t> where;
+    size_t base = 0, bytes = 0;
+    size_t add(const void *src, size_t n_bytes) { // -> offset of the array's copy in the image
+        auto it = where.find({src, n_bytes});
+        if (it != where.end()) return it->second;
+        const size_t off = base + bytes;
+        items.push_back({src, n_bytes, off});
+        where.emplace(std::make_pair(src, n_bytes), off);
+        bytes += round_up(n_bytes, 32);
+        return off;
+    }
+    void copy_into(char *h_up) const {
+        for (const Item &it : items) std::memcpy(h_up + it.off, it.src, it.bytes);
+    }
+};
+
+// One batched call over the work areas: `fill` writes the image into pinned memory (pointers into it are d_up + offset), one copy uploads
+// it, `launch` enqueues the kernels (it may synchronise to report an argument error found on the device), the image's out_bytes at out_off
+// come back, `collect` reads them.  *took = false: the work areas are another call's -- nothing was done.
+int run_eval_batched(size_t image_bytes, size_t out_off, size_t out_bytes, bool inputs_on_device, int plan, const std::function<void(char *, char *)> &fill,
+                     const std::function<int(char *, char *, hipStream_t)> &launch, const std::function<void(const char *)> &collect, bool *took) {
+    *took = false;
+    AreaLease lease;
+    if (!lease.held) return SC_OK;
+    BatchArea &a = g_area;
+    const int dev = sc_internal_device_ref();
+    GateHold gate(dev);
+    if (int rc = area_open(a, dev)) return rc;
+    if (int rc = area_reserve(a, 256 + image_bytes, image_bytes)) return rc;
+    if (inputs_on_device) HIP_TRY(hipDeviceSynchronize()); // the inputs are read in place: their producers are waited for, as a copy would
+    char *d_up = a.d_buf + 256;
+    fill(a.h_up, d_up);
+    HIP_TRY(hipMemcpyAsync(d_up, a.h_up, out_off, hipMemcpyHostToDevice, a.stream));
+    if (int rc = launch(a.h_up, d_up, a.stream)) return rc;
+    scd::plan_hit(plan);
+    HIP_TRY(hipMemcpyAsync(a.h_up + out_off, d_up + out_off, out_bytes, hipMemcpyDeviceToHost, a.stream));
+    HIP_TRY(hipStreamSynchronize(a.stream));
+    gate.release();
+    collect(a.h_up + out_off);
+    *took = true;
+    return SC_OK;
+}
+
+// sc_poly_evaluate's argument checks on one descriptor of a batch (no HIP call)
+int check_eval_desc(const sc_poly_desc *d, uint32_t i) {
+    if (d->num_vars > 40) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: num_vars %u too large", i, d->num_vars);
+    if (d->n_tables == 0 || !d->tables) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: no tables", i);
+    if (d->n_products && (!d->coeffs || !d->prod_offsets || !d->prod_indices)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null product arrays", i);
+    for (uint32_t k = 0; k < d->n_products; ++k) {
+        if (d->prod_offsets[k + 1] <= d->prod_offsets[k]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: product %u is empty", i, k);
+        for (uint32_t q = d->prod_offsets[k]; q < d->prod_offsets[k + 1]; ++q)
+            if (d->prod_indices[q] >= d->n_tables)
+                return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: product %u refers to table %u >= %u", i, k, d->prod_indices[q], d->n_tables);
+        sch::Fr c;
+        std::memcpy(&c, d->coeffs + 4 * k, 32);
+        if (sch::geq_p(c)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: coefficient %u is not a canonical field element", i, k);
+    }
+    for (uint32_t u = 0; u < d->n_tables; ++u)
+        if (!d->tables[u]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: table %u is null", i, u);
+    return SC_OK;
+}
+int check_canonical(const uint64_t *elems, uint32_t n_elems, uint32_t i, const char *what) {
+    for (uint32_t k = 0; k < n_elems; ++k) {
+        sch::Fr e;
+        std::memcpy(&e, elems + 4 * (size_t)k, 32);
+        if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: %s[%u] is not a canonical field element", i, what, k);
+    }
+    return SC_OK;
+}
+int prefix_instance(int rc, uint32_t i) {
+    const std::string why = sc_last_error();
+    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+}
+constexpr size_t kEvalImageMax = (size_t)1 << 30; // a batch whose staged inputs exceed this goes instance by instance
+} // namespace
+
+extern "C" int sc_poly_evaluate_batch(const sc_poly_desc *descs, uint32_t n, const uint64_t *points, uint64_t *out_values, uint64_t *out_table_values_or_null) {
+    if (n == 0) return SC_OK;
+    // ---- everything the host can check, before any HIP call: the lowest failing instance decides --------------------------------------
+    if (!descs || !out_values || (descs[0].num_vars && !points)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: null argument");
+    const uint32_t nv = descs[0].num_vars, U = descs[0].n_tables, K = descs[0].n_products;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int rc = check_eval_desc(&descs[i], i)) return rc;
+        if (const char *field = i ? first_structure_difference(descs[0], descs[i]) : nullptr)
+            return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u differs from instance 0 in %s: a batch has one structure", i, field);
+        if (int rc = check_canonical(points + (size_t)i * nv * 4, nv, i, "point")) return rc;
+    }
+    if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
+    auto combine = [&](uint32_t i, const sch::Fr *tv) { // sum_k c_k prod_j T_j(point): sc_poly_evaluate's K x M host products
+        const sc_poly_desc &d = descs[i];
+        sch::Fr acc = sch::zero();
+        for (uint32_t k = 0; k < K; ++k) {
+            sch::Fr pr;
+            std::memcpy(&pr, d.coeffs + 4 * k, 32);
+            for (uint32_t q = d.prod_offsets[k]; q < d.prod_offsets[k + 1]; ++q) pr = sch::mul(pr, tv[d.prod_indices[q]]);
+            acc = sch::add(acc, pr);
+        }
+        std::memcpy(out_values + 4 * (size_t)i, &acc, 32);
+        if (out_table_values_or_null) std::memcpy(out_table_values_or_null + (size_t)i * U * 4, tv, (size_t)U * 32);
+    };
+    const int64_t pol = scd::policy(scd::kPolBatch);
+    const bool host_tables = !(descs[0].flags & SC_TABLES_ON_DEVICE);
+    if (pol != 0 && scd::eval_batch_shape_fits(nv) && (uint64_t)n * U < (1ULL << 31) && (pol == 2 || n >= eval_batch_min_n(nv))) {
+        // the image: table pointers | points | host tables, each distinct array once | the n x U values
+        const size_t table_bytes = (size_t)32 << nv, blocks = (size_t)n * U;
+        const size_t ptr_bytes = round_up(blocks * sizeof(void *), 256), pt_bytes = round_up((size_t)n * nv * 32, 256);
+        StageMap st;
+        st.base = ptr_bytes + pt_bytes;
+        std::vector<size_t> tab_off;
+        if (host_tables) {
+            tab_off.resize(blocks);
+            for (uint32_t i = 0; i < n; ++i)
+                for (uint32_t u = 0; u < U; ++u) tab_off[(size_t)i * U + u] = st.add(descs[i].tables[u], table_bytes);
+        }
+        const size_t out_off = round_up(st.base + st.bytes, 256), out_bytes = blocks * 32;
+        if (out_off + out_bytes <= kEvalImageMax) {
+            bool took = false;
+            int rc = run_eval_batched(
+                out_off + out_bytes, out_off, out_bytes, !host_tables, scd::kPlanBatchEvalOneBlock,
+                [&](char *h_up, char *d_up) {
+                    const void **h_ptrs = reinterpret_cast<const void **>(h_up);
+                    for (uint32_t i = 0; i < n; ++i)
+                        for (uint32_t u = 0; u < U; ++u) h_ptrs[(size_t)i * U + u] = host_tables ? d_up + tab_off[(size_t)i * U + u] : (const void *)descs[i].tables[u];
+                    if (nv) std::memcpy(h_up + ptr_bytes, points, (size_t)n * nv * 32);
+                    st.copy_into(h_up);
+                },
+                [&](char *, char *d_up, hipStream_t stream) -> int {
+                    scd::EvalBatchArgs A;
+                    std::memset(&A, 0, sizeof(A));
+                    A.tables = reinterpret_cast<const uint4 *const *>(d_up);
+                    A.points = reinterpret_cast<const uint4 *>(d_up + ptr_bytes);
+                    A.out = reinterpret_cast<uint4 *>(d_up + out_off);
+                    A.nv = nv;
+                    A.group_size = U;
+                    A.pt_stride = nv;
+                    A.out_stride = U;
+                    HIP_TRY(scd::launch_batch_eval(A, (uint32_t)blocks, stream));
+                    return SC_OK;
+                },
+                [&](const char *h_out) {
+                    for (uint32_t i = 0; i < n; ++i) combine(i, reinterpret_cast<const sch::Fr *>(h_out) + (size_t)i * U);
+                },
+                &took);
+            if (rc) return rc;
+            if (took) return SC_OK;
+        }
+    }
+    // ---- the serial plan: sc_poly_evaluate, instance after instance ----------------------------------------------------------------------
+    scd::plan_hit(scd::kPlanBatchEvalSerial);
+    for (uint32_t i = 0; i < n; ++i) {
+        int rc = sc_poly_evaluate(&descs[i], nv ? points + (size_t)i * nv * 4 : nullptr, out_values + 4 * (size_t)i,
+                                  out_table_values_or_null ? out_table_values_or_null + (size_t)i * U * 4 : nullptr);
+        if (rc) return prefix_instance(rc, i);
+    }
+    return SC_OK;
+}
+
+extern "C" int sc_gkr_subclaim_batch(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2,
+                                     const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *uv, uint32_t flags, uint64_t *out_evals) {
+    if (n == 0) return SC_OK;
+    // ---- everything the host can check, before any HIP call: the lowest failing instance decides --------------------------------------
+    if (!f1_idx || !f1_vals || !nnz || !f2 || !f3 || !g || !uv || !out_evals) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: null argument");
+    if (dim == 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim 0: a GKR round has at least one variable per component");
+    if (dim > 21) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim %u: 3*dim index bits do not fit 64-bit indices", dim);
+    const bool dev_in = flags & SC_TABLES_ON_DEVICE;
+    uint64_t nnz_max = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (nnz[i] >= (1ULL << 32)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz too large", i);
+        if ((nnz[i] && (!f1_idx[i] || !f1_vals[i])) || !f2[i] || !f3[i] || !g[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null argument", i);
+        if (int rc = check_canonical(g[i], dim, i, "g")) return rc;
+        if (int rc = check_canonical(uv + (size_t)i * 2 * dim * 4, 2 * dim, i, "uv")) return rc;
+        if (!dev_in)
+            for (uint64_t k = 0; k < nnz[i]; ++k)
+                if ((f1_idx[i][k] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 index %llu out of range", i, (unsigned long long)k);
+        nnz_max = std::max(nnz_max, nnz[i]);
+    }
+    if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
+    const size_t N = (size_t)1 << dim;
+    auto finish = [&](uint32_t i, const sch::Fr &a1, const sch::Fr &a2, const sch::Fr &a3) { // f1(g,u,v), f2(u), f3(v), their product (data_structures.rs:53-55)
+        const sch::Fr e[4] = {a1, a2, a3, sch::mul(sch::mul(a1, a2), a3)};
+        std::memcpy(out_evals + (size_t)i * 16, e, 128);
+    };
+    const int64_t pol = scd::policy(scd::kPolBatch);
+    if (pol != 0 && scd::gkr_eval_batch_shape_fits(dim, nnz_max) && scd::eval_batch_shape_fits(dim) && (pol == 2 || n >= gkr_eval_batch_min_n())) {
+        // the image: instance records | the index check's flags | g | u | v per instance | (f2, f3) pointers | host inputs, each distinct array
+        // once (one wiring predicate for many data instances is the usual case) | the n x 3 values
+        const size_t rec_bytes = round_up((size_t)n * sizeof(scd::GkrBatchInst), 256), flag_bytes = round_up((size_t)n * 4, 256);
+        const size_t pt_bytes = round_up((size_t)n * 3 * dim * 32, 256), ptr_bytes = round_up((size_t)n * 2 * sizeof(void *), 256);
+        const size_t flag_off = rec_bytes, pt_off = flag_off + flag_bytes, ptr_off = pt_off + pt_bytes;
+        StageMap st;
+        st.base = ptr_off + ptr_bytes;
+        std::vector<size_t> offs_in; // per instance: idx, vals, f2, f3 (host inputs)
+        if (!dev_in) {
+            offs_in.resize((size_t)n * 4);
+            for (uint32_t i = 0; i < n; ++i) {
+                offs_in[4 * (size_t)i + 0] = nnz[i] ? st.add(f1_idx[i], (size_t)nnz[i] * 8) : st.base;
+                offs_in[4 * (size_t)i + 1] = nnz[i] ? st.add(f1_vals[i], (size_t)nnz[i] * 32) : st.base;
+                offs_in[4 * (size_t)i + 2] = st.add(f2[i], N * 32);
+                offs_in[4 * (size_t)i + 3] = st.add(f3[i], N * 32);
+            }
+        }
+        const size_t out_off = round_up(st.base + st.bytes, 256), out_bytes = (size_t)n * 3 * 32;
+        if (out_off + out_bytes <= kEvalImageMax) {
+            bool took = false;
+            int rc = run_eval_batched(
+                out_off + out_bytes, out_off, out_bytes, dev_in, scd::kPlanBatchGkrEvalOneBlock,
+                [&](char *h_up, char *d_up) {
+                    scd::GkrBatchInst *rec = reinterpret_cast<scd::GkrBatchInst *>(h_up);
+                    const void **h_ptrs = reinterpret_cast<const void **>(h_up + ptr_off);
+                    std::memset(h_up + flag_off, 0, flag_bytes);
+                    st.copy_into(h_up);
+                    for (uint32_t i = 0; i < n; ++i) {
+                        char *pt = h_up + pt_off + (size_t)i * 3 * dim * 32;
+                        std::memcpy(pt, g[i], (size_t)dim * 32);
+                        std::memcpy(pt + (size_t)dim * 32, uv + (size_t)i * 2 * dim * 4, (size_t)2 * dim * 32);
+                        scd::GkrBatchInst &r = rec[i];
+                        r.nnz = nnz[i];
+                        r.g = reinterpret_cast<const uint4 *>(d_up + pt_off + (size_t)i * 3 * dim * 32);
+                        if (dev_in) {
+                            r.idx = f1_idx[i];
+                            r.vals = reinterpret_cast<const uint4 *>(f1_vals[i]);
+                            r.f2 = reinterpret_cast<const uint4 *>(f2[i]);
+                            r.f3 = reinterpret_cast<const uint4 *>(f3[i]);
+                        } else {
+                            r.idx = reinterpret_cast<const uint64_t *>(d_up + offs_in[4 * (size_t)i + 0]);
+                            r.vals = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 1]);
+                            r.f2 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 2]);
+                            r.f3 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 3]);
+                        }
+                        h_ptrs[2 * (size_t)i] = r.f2;
+                        h_ptrs[2 * (size_t)i + 1] = r.f3;
+                    }
+                },
+                [&](char *h_up, char *d_up, hipStream_t stream) -> int {
+                    const scd::GkrBatchInst *d_rec = reinterpret_cast<const scd::GkrBatchInst *>(d_up);
+                    if (dev_in) { // the lists are device memory: their indices are checked there, in front of the launch (the kernel itself masks every index it uses)
+                        HIP_TRY(scd::launch_batch_gkr_idx_range(d_rec, n, dim, reinterpret_cast<uint32_t *>(d_up + flag_off), stream));
+                        HIP_TRY(hipMemcpyAsync(h_up + flag_off, d_up + flag_off, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+                        HIP_TRY(hipStreamSynchronize(stream));
+                        const uint32_t *fl = reinterpret_cast<const uint32_t *>(h_up + flag_off);
+                        for (uint32_t i = 0; i < n; ++i)
+                            if (fl[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
+                    }
+                    uint4 *d_out = reinterpret_cast<uint4 *>(d_up + out_off);
+                    HIP_TRY(scd::launch_batch_gkr_eval(d_rec, n, dim, d_out, 3, stream));
+                    scd::EvalBatchArgs A; // f2 at u and f3 at v: 2 n tables of dim variables, points inside the instance's g | u | v
+                    std::memset(&A, 0, sizeof(A));
+                    A.tables = reinterpret_cast<const uint4 *const *>(d_up + ptr_off);
+                    A.points = reinterpret_cast<const uint4 *>(d_up + pt_off);
+                    A.out = d_out;
+                    A.nv = dim;
+                    A.group_size = 2;
+                    A.pt_stride = 3 * dim;
+                    A.pt_base = dim;
+                    A.pt_step = dim;
+                    A.out_stride = 3;
+                    A.out_base = 1;
+                    HIP_TRY(scd::launch_batch_eval(A, 2 * n, stream));
+                    return SC_OK;
+                },
+                [&](const char *h_out) {
+                    const sch::Fr *v = reinterpret_cast<const sch::Fr *>(h_out);
+                    for (uint32_t i = 0; i < n; ++i) finish(i, v[3 * (size_t)i], v[3 * (size_t)i + 1], v[3 * (size_t)i + 2]);
+                },
+                &took);
+            if (rc) return rc;
+            if (took) return SC_OK;
+        }
+    }
+    // ---- the serial plan: sc_sparse_evaluate at g | u | v (a host list: a device-resident one is copied, each distinct list once, and its
+    // indices checked before anything is written) and sc_poly_evaluate of the one-table polynomials, instance after instance ---------------
+    scd::plan_hit(scd::kPlanBatchGkrEvalSerial);
+    std::map<const void *, std::vector<uint64_t>> host_copy; // device pointer -> its host copy (indices, values)
+    auto on_host = [&](const uint64_t *src, size_t words, const uint64_t **out) -> int {
+        if (!dev_in || words == 0) {
+            *out = src;
+            return SC_OK;
+        }
+        auto it = host_copy.find(src);
+        if (it == host_copy.end() || it->second.size() < words) {
+            std::vector<uint64_t> buf(words);
+            const int dev = sc_internal_device_ref();
+            DeviceGate gate_(dev);
+            HIP_TRY(hipSetDevice(dev));
+            HIP_TRY(hipMemcpy(buf.data(), src, words * 8, hipMemcpyDeviceToHost)); // (waits for whatever produced the list, as a copy does)
+            it = host_copy.insert_or_assign(src, std::move(buf)).first;
+        }
+        *out = it->second.data();
+        return SC_OK;
+    };
+    if (dev_in)
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint64_t *idx = nullptr;
+            if (int rc = on_host(f1_idx[i], (size_t)nnz[i], &idx)) return rc;
+            for (uint64_t k = 0; k < nnz[i]; ++k)
+                if ((idx[k] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
+        }
+    const uint32_t offs[2] = {0, 1}, idx0[1] = {0};
+    std::vector<uint64_t> guv((size_t)3 * dim * 4);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t *u = uv + (size_t)i * 2 * dim * 4, *v = u + (size_t)dim * 4, *idx = nullptr, *vals = nullptr;
+        std::memcpy(guv.data(), g[i], (size_t)dim * 32);
+        std::memcpy(guv.data() + (size_t)dim * 4, u, (size_t)2 * dim * 32);
+        int rc = on_host(f1_idx[i], (size_t)nnz[i], &idx);
+        if (!rc) rc = on_host(f1_vals[i], (size_t)nnz[i] * 4, &vals);
+        if (rc) return rc;
+        sch::Fr a[3];
+        rc = sc_sparse_evaluate(idx, vals, nnz[i], 3 * dim, guv.data(), a[0].l);
+        for (int t = 0; t < 2 && !rc; ++t) {
+            const uint64_t *tab[1] = {t == 0 ? f2[i] : f3[i]};
+            sc_poly_desc d;
+            std::memset(&d, 0, sizeof(d));
+            d.num_vars = dim;
+            d.max_multiplicands = 1;
+            d.n_products = 1;
+            d.coeffs = sch::kOne.l; // one x T(point) is T(point), bit for bit
+            d.prod_offsets = offs;
+            d.prod_indices = idx0;
+            d.n_tables = 1;
+            d.tables = tab;
+            d.flags = dev_in ? (uint32_t)SC_TABLES_ON_DEVICE : 0u;
+            rc = sc_poly_evaluate(&d, t == 0 ? u : v, a[1 + t].l, nullptr);
+        }
+        if (rc) return prefix_instance(rc, i);
+        finish(i, a[0], a[1], a[2]);
+    }
     return SC_OK;
 }

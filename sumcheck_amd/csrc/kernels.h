@@ -268,6 +268,26 @@ bool gkr_batch_shape_fits(uint32_t dim, uint64_t nnz_max);
 int gkr_batch_blocks_per_cu(int device, uint32_t dim); // occupancy of k_batch_gkr at that LDS size (0: unknown)
 hipError_t launch_batch_gkr_idx_range(const GkrBatchInst *inst, uint32_t n, uint32_t dim, uint32_t *flags, hipStream_t stream); // flags[i] |= 1: an index of instance i has a bit at or above 3 dim
 hipError_t launch_batch_gkr(BatchGkrArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream);
+// Batched oracle queries (kernels_batch_eval.hip): what a caller of the two batched provers asks for at the point a proof ended on.  Plain
+// launches: nothing here waits for the host.
+//   k_batch_eval      one block per table: the first three variables bound on the fly from global memory (k_fold_multi's pass), the rest
+//                     in LDS (bt_bind's pass); block b = group x group_size + member reads tables[b] and the nv-element point at element
+//                     group x pt_stride + pt_base + member x pt_step of `points`, and writes out[group x out_stride + out_base + member].
+//                     sc_poly_evaluate_batch: a group is an instance's U tables at the instance's point (pt_stride = nv, pt_step = 0);
+//                     sc_gkr_subclaim_batch: a group is (f2, f3) of an instance at (u, v) of its g | u | v record.
+//   k_batch_gkr_eval  one block per instance: eq(g, .), eq(u, .), eq(v, .) in LDS, three products per non-zero, exact integer lanes;
+//                     GkrBatchInst::g is the instance's g | u | v (3 x dim elements), f2 / f3 are not read; writes out[instance x out_stride].
+constexpr uint32_t kEvalBatchMaxNv = 14; // 2^11 entries of 48 B in LDS behind the first pass
+struct EvalBatchArgs {
+    const uint4 *const *tables; // device: [blocks] pointers, 2^nv entries each, only read
+    const uint4 *points;        // device: canonical Montgomery elements
+    uint4 *out;                 // device
+    uint32_t nv, group_size, pt_stride, pt_base, pt_step, out_stride, out_base;
+};
+bool eval_batch_shape_fits(uint32_t nv);
+hipError_t launch_batch_eval(const EvalBatchArgs &args, uint32_t blocks, hipStream_t stream);
+bool gkr_eval_batch_shape_fits(uint32_t dim, uint64_t nnz_max); // sc_gkr_prove_batch's envelope: dim <= kGkrBatchMaxDim, nnz <= kGkrBatchMaxNnzPerCell x 2^dim
+hipError_t launch_batch_gkr_eval(const GkrBatchInst *inst, uint32_t n, uint32_t dim, uint4 *out, uint32_t out_stride, hipStream_t stream);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -331,6 +351,10 @@ enum Plan {
     kPlanGkrCoeffFromBound,   // phase two's coefficient f2(u) from phase one's bound table
     kPlanGkrSharded,          // sc_gkr_prove_sharded
     kPlanFoldMulti,           // sc_poly_evaluate / sc_fix_variables (k_fold_multi)
+    kPlanBatchEvalOneBlock,   // sc_poly_evaluate_batch: k_batch_eval, one block per (instance, table), one launch for the whole batch
+    kPlanBatchEvalSerial,     // ... instance after instance through sc_poly_evaluate (num_vars beyond the envelope, policy "batch" = 0, work areas taken)
+    kPlanBatchGkrEvalOneBlock, // sc_gkr_subclaim_batch: k_batch_gkr_eval (one block per instance) and k_batch_eval over (f2, f3)
+    kPlanBatchGkrEvalSerial,  // ... instance after instance through sc_sparse_evaluate and sc_poly_evaluate (dim or nnz beyond the envelope, policy "batch" = 0)
     kPlanBatchOneBlock,       // sc_ml_prove_batch: k_batch_proofs, one block per instance, every round out of LDS
     kPlanBatchSerial,         // ... instance after instance on the kept prover (shapes beyond the envelope, small n, slot busy, device-side waits off)
     kPlanBatchGkrOneBlock,    // sc_gkr_prove_batch: k_batch_gkr, one block per instance, both initialisations and 2 x dim rounds out of LDS

@@ -23,32 +23,6 @@
 
 namespace scd {
 
-// eq(point, .) over dim variables into out[2^dim] (32-byte elements in LDS): precompute_eq's doubling (ark-poly: dp[b + 2^i] = dp[b] * g_i ;
-// dp[b] -= dp[b + 2^i]) on the two halves of the variables at once -- wavefront 0 the low kl, wavefront 1 the high kh -- then the outer
-// product.  Depth ceil(dim / 2) + 1 dependent products instead of dim.  tmp: 2^kl + 2^kh elements of scratch.  Ends behind a barrier.
-__device__ __forceinline__ void bg_build_eq(uint4 *out, uint4 *tmp, const uint4 *point, const uint32_t dim) {
-    const uint32_t tid = threadIdx.x, kl = (dim + 1) / 2, kh = dim - kl;
-    uint4 *lo = tmp, *hi = tmp + 2 * ((size_t)1 << kl);
-    if (tid == 0) fr_store(lo, fr_one());
-    if (tid == 64) fr_store(hi, fr_one());
-    __syncthreads();
-    for (uint32_t i = 0; i < kl; ++i) {
-        const uint32_t w = tid >> 6, t = tid & 63u;
-        if (w < 2 && t < (1u << i) && (w == 0 || i < kh)) {
-            uint4 *tab = w == 0 ? lo : hi;
-            const Fr a = fr_load(tab + 2 * t), m = fr_mul(a, fr_load(point + 2 * (w == 0 ? i : kl + i)));
-            fr_store(tab + 2 * (t + (1u << i)), m);
-            fr_store(tab + 2 * t, fr_sub(a, m));
-        }
-        __syncthreads();
-    }
-    for (uint32_t b = tid; b < (1u << dim); b += kTsBlock) {
-        const Fr l = fr_load(lo + 2 * (b & ((1u << kl) - 1u)));
-        fr_store(out + 2 * b, kh ? fr_mul(l, fr_load(hi + 2 * (b >> kl))) : l);
-    }
-    __syncthreads();
-}
-
 // kPhase 1: cell x, term eq(g,z) * v * f3[y]; kPhase 2: cell y, term eq(g,z) * eq(u,x) * v.  The cells (lane-major: cell[j << dim | c],
 // neighbouring cells in neighbouring banks) are zeroed, filled and folded into table `dst`.  Ends behind a barrier.
 template <int kPhase>

@@ -182,6 +182,18 @@ class GKRRoundSumcheckSubClaim:  # data_structures.rs:22-31
         actual = field.to_int(f1.evaluate(guv)) * field.to_int(f2.evaluate(self.u)) % field.P * field.to_int(f3.evaluate(self.v)) % field.P
         return actual == field.to_int(self.expected_evaluation)
 
+    @staticmethod
+    def verify_subclaim_batch(subclaims: Sequence["GKRRoundSumcheckSubClaim"], f1s, f2s, f3s, gs) -> List[bool]:
+        """verify_subclaim of n subclaims of one dim in one library call (GKRRoundSumcheck.evaluate_subclaims_batch): element i is
+        subclaims[i].verify_subclaim(f1s[i], f2s[i], f3s[i], gs[i])"""
+        n = len(subclaims)
+        assert len(f1s) == n and len(f2s) == n and len(f3s) == n and len(gs) == n, "one f1, f2, f3 and g per subclaim"
+        if n == 0:
+            return []
+        uv = np.stack([np.concatenate([_np64(c.u).reshape(-1, 4), _np64(c.v).reshape(-1, 4)]) for c in subclaims])
+        ev = GKRRoundSumcheck.evaluate_subclaims_batch(f1s, f2s, f3s, gs, uv)
+        return [bool(np.array_equal(ev[i, 3], _np64(c.expected_evaluation).reshape(4))) for i, c in enumerate(subclaims)]
+
 
 def _verify_phase(rng: Blake2b512Rng, msgs: Sequence[ProverMsg], dim: int, asserted_sum):
     """verifier_init{max_multiplicands: 2} + verify_round x dim + check_and_generate_subclaim (mod.rs:157-166)"""
@@ -262,6 +274,44 @@ class GKRRoundSumcheck:
                                        SC_TABLES_ON_DEVICE if dev else 0, _ptr(proofs), _ptr(uv)))
         out = [GKRProof([ProverMsg(proofs[i, 0, j].copy()) for j in range(dim)], [ProverMsg(proofs[i, 1, j].copy()) for j in range(dim)]) for i in range(n)]
         return (out, uv[:, :, :dim].copy()) if return_uv else out
+
+    @staticmethod
+    def evaluate_subclaims_batch(f1s: Sequence[SparseMultilinearExtension], f2s: Sequence[DenseMultilinearExtension],
+                                 f3s: Sequence[DenseMultilinearExtension], gs, uv) -> np.ndarray:
+        """The three oracle queries of verify_subclaim (data_structures.rs:33-56) for n instances of one dim in one library call
+        (sc_gkr_subclaim_batch) -> (n, 4, 4): f1(g,u,v), f2(u), f3(v) and their product, the value a caller compares with
+        expected_evaluation.  uv: (n, 2, dim, 4), what prove_batch(..., return_uv=True) returns.  Inputs all on the host or all on the GPU,
+        as for prove_batch; the same object may stand for several instances.  After prove_batch a caller finishes with this one call,
+        not 3 n."""
+        n = len(f1s)
+        assert len(f2s) == n and len(f3s) == n and len(gs) == n, "one f1, f2, f3 and g per instance"
+        if n == 0:
+            check(lib().sc_gkr_subclaim_batch(0, 0, None, None, None, None, None, None, None, 0, None))
+            return np.zeros((0, 4, 4), np.uint64)
+        dim = f2s[0].num_vars
+        ons = [m.on_device for m in list(f1s) + list(f2s) + list(f3s)]
+        dev = all(ons)
+        assert dev or not any(ons), "mixing host and device inputs is not supported"
+        g_arr = []
+        for i in range(n):
+            assert f2s[i].num_vars == dim and f3s[i].num_vars == dim and f1s[i].num_vars == 3 * dim, f"instance {i}: a batch has one dim"
+            g_arr.append(_np64(gs[i]).reshape(-1, 4))
+            assert g_arr[i].shape[0] == dim
+        uv_arr = np.ascontiguousarray(_np64(uv).reshape(n, 2, dim, 4))
+        if dev:
+            import torch
+            torch.cuda.current_stream(f2s[0].evaluations.device).synchronize()  # the library works on its own stream
+
+        def ptrs(vals):
+            return (C.c_void_p * n)(*[C.cast(v, C.c_void_p) for v in vals])
+
+        f1p = [f._ptrs() for f in f1s]
+        nnz = (C.c_uint64 * n)(*[f.nnz for f in f1s])
+        out = np.zeros((n, 4, 4), dtype=np.uint64)
+        check(lib().sc_gkr_subclaim_batch(n, dim, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
+                                          ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), _ptr(uv_arr) if uv_arr.size else None,
+                                          SC_TABLES_ON_DEVICE if dev else 0, _ptr(out)))
+        return out
 
     @staticmethod
     def verify(rng: Blake2b512Rng, f2_num_vars: int, proof: GKRProof, claimed_sum) -> GKRRoundSumcheckSubClaim:

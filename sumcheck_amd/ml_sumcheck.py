@@ -139,6 +139,37 @@ class ListOfProductsOfPolynomials:
         del keep
         return out, tv[: len(self.flattened_ml_extensions)]
 
+    @staticmethod
+    def evaluate_batch(polys: Sequence["ListOfProductsOfPolynomials"], points, return_table_values: bool = False):
+        """n x evaluate in one library call (sc_poly_evaluate_batch): polynomials of ONE structure (the same num_variables and product
+        lists; tables and coefficients per instance, all on the host or all on the GPU), points (n, num_variables, 4) -- the point each
+        proof's subclaim ended on.  -> (n, 4) values, value i bit for bit polys[i].evaluate(points[i]); with return_table_values also the
+        (n, U, 4) per-table evaluations.  After MLSumcheck.prove_batch a caller finishes with this one call, not n."""
+        n = len(polys)
+        if n == 0:
+            check(lib().sc_poly_evaluate_batch(None, 0, None, None, None))
+            return (np.zeros((0, 4), np.uint64), np.zeros((0, 0, 4), np.uint64)) if return_table_values else np.zeros((0, 4), np.uint64)
+        nv, U = polys[0].num_variables, len(polys[0].flattened_ml_extensions)
+        pts = np.ascontiguousarray(_np64(points).reshape(n, nv, 4))
+        descs = (PolyDesc * n)()
+        keep = []
+        on = []
+        for i, poly in enumerate(polys):
+            d, k = poly._desc(False)
+            C.memmove(C.byref(descs, i * C.sizeof(PolyDesc)), C.byref(d), C.sizeof(PolyDesc))
+            keep.append(k)
+            on.append(bool(d.flags & SC_TABLES_ON_DEVICE))
+        if any(on):
+            if not all(on):
+                raise ValueError("mixing host and device tables in one batch is not supported")
+            import torch
+            torch.cuda.current_stream(polys[0].flattened_ml_extensions[0].evaluations.device).synchronize()  # the library works on its own stream
+        out = np.zeros((n, 4), dtype=np.uint64)
+        tv = np.zeros((n, max(U, 1), 4), dtype=np.uint64)
+        check(lib().sc_poly_evaluate_batch(descs, n, _ptr(pts) if pts.size else None, _ptr(out), _ptr(tv)))
+        del keep
+        return (out, tv[:, :U].copy()) if return_table_values else out
+
     # ---- marshalling -----------------------------------------------------------------------------
     def _desc(self, borrow: bool = False):
         K = len(self.products)
