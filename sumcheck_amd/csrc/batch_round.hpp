@@ -119,36 +119,52 @@ __device__ __forceinline__ void bt_bind(const BtBlock &B, uint32_t &E) {
     __syncthreads();
 }
 
-// the round's sums over the E entries still held, its message from the instance's matrices, and the message out under `tag`
+// One combination's sum: lane q of the combination's L (a power of two, in one wavefront) adds the products of pairs q, q + L, ... lazily,
+// then a shuffle tree adds the L lanes; lane q == 0 returns the total (the others partial sums).  prod_at(pair) is the product.
+// reduce_lanes (wave-uniform, lazy_sum_needs_reduce(pairs, worst product in units of p)): the int32 top limb of ONE accumulator would not
+// hold the combination's whole sum (kernels.h: kLazySumMaxP), so every lane's sum is made canonical before the tree -- L <= 64 values
+// below p then.  Within a lane the sum is reduced every 32 terms: terms of up to 8 p each stay inside fe_to_fr's range.
+template <typename ProdAt>
+__device__ __forceinline__ Fe bt_combo_sum(const bool live, const uint32_t q, const int L, const uint32_t pairs_here, const bool reduce_lanes, const ProdAt &prod_at) {
+    Fe acc = fe_zero();
+    if (live) {
+        uint32_t iter = 0;
+        for (uint32_t pr = q; pr < pairs_here; pr += (uint32_t)L, ++iter) {
+            acc = fe_carry_pass(fe_add(acc, prod_at(pr)));
+            if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31; reached only beyond 32 L pairs)
+        }
+    }
+    if (reduce_lanes) acc = fe_from_fr(fe_to_fr(acc));
+    for (int off = L >> 1; off >= 1; off >>= 1) acc = fe_carry_pass(fe_add(acc, bt_shfl_down(acc, off)));
+    return acc;
+}
+
+// the round's sums over the E entries still held, its message from the instance's matrices, and the message out under `tag`.
+// worst_p: a bound on the magnitude of one product in units of p (round j of tables loaded canonical: entries in (-j p, p), products of
+// two or more within (1 + j^2 / 70) p -- j + 1 covers both)
 template <int kSlots, typename ProdFn>
-__device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kSlots> &ln, const ProdFn &prod_of, const uint32_t E, const uint32_t tag) {
+__device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kSlots> &ln, const ProdFn &prod_of, const uint32_t E, const uint32_t tag, const uint32_t worst_p) {
     const int tid = threadIdx.x;
     // ---- sums: lane (combination, q) multiplies out the combination's pairs q, q + L, ... ----------------------------------------------
     const uint32_t pairs_here = E / 2;
-    Fe acc = fe_zero();
-    if (ln.combo_live) {
-        const int32_t nv = ln.my_nv;
-        uint32_t iter = 0;
-        for (uint32_t pr = (uint32_t)ln.my_q; pr < pairs_here; pr += (uint32_t)B.L, ++iter) {
-            Fe prod = fe_zero();
-            bool first = true;
+    const int32_t nv = ln.my_nv;
+    const Fe acc = bt_combo_sum(ln.combo_live, (uint32_t)ln.my_q, B.L, pairs_here, lazy_sum_needs_reduce(pairs_here, worst_p), [&](const uint32_t pr) -> Fe {
+        Fe prod = fe_zero();
+        bool first = true;
 #pragma unroll
-            for (int sl = 0; sl < kSlots; ++sl) {
-                if (ln.my_exp[sl] == 0) break; // (slots are dense: the first empty one ends the list)
-                const int32_t *lo_p = B.tabs + (ln.my_base[sl] + 2 * pr) * (uint32_t)kBtEnt;
-                Fe val;
-                if (nv == 0) val = bt_lds_load(lo_p);
-                else if (nv == 1) val = bt_lds_load(lo_p + kBtEnt);
-                else val = fe_line(bt_lds_load(lo_p), bt_lds_load(lo_p + kBtEnt), nv);
-                uint32_t k = 0;
-                if (first) { prod = val; k = 1; first = false; }
-                for (const uint32_t e = ln.my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
-            }
-            acc = fe_carry_pass(fe_add(acc, prod));
-            if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31; never reached here)
+        for (int sl = 0; sl < kSlots; ++sl) {
+            if (ln.my_exp[sl] == 0) break; // (slots are dense: the first empty one ends the list)
+            const int32_t *lo_p = B.tabs + (ln.my_base[sl] + 2 * pr) * (uint32_t)kBtEnt;
+            Fe val;
+            if (nv == 0) val = bt_lds_load(lo_p);
+            else if (nv == 1) val = bt_lds_load(lo_p + kBtEnt);
+            else val = fe_line(bt_lds_load(lo_p), bt_lds_load(lo_p + kBtEnt), nv);
+            uint32_t k = 0;
+            if (first) { prod = val; k = 1; first = false; }
+            for (const uint32_t e = ln.my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
         }
-    }
-    for (int off = B.L >> 1; off >= 1; off >>= 1) acc = fe_carry_pass(fe_add(acc, bt_shfl_down(acc, off)));
+        return prod;
+    });
     if (ln.combo_live && ln.my_q == 0) fr_store(B.fin_lds + 2 * (B.prod_index_sh[ln.my_combo] * B.D + (int)B.combo_sh[ln.my_combo].t), fe_to_fr(acc));
     __syncthreads();
     // ---- the message, from the instance's own matrices, into LDS; then out as tagged words: every 8-byte word validates itself --------

@@ -25,9 +25,12 @@
 // product's coefficient before k_finalize multiplies by it.  Field arithmetic is exact, so the round polynomial
 // is bit-identical to the reference's.
 //
-// Bounds (|limb| of the two operands of fe_mul): one operand <= 2^30 (a normalised value plus one lazy add or
-// sub), the other <= 2^29 (normalised, or a difference of two normalised values).  Then every column is below
-// 9*2^59 + 8*2^58 + carry < 2^63 in magnitude.  Values (not limbs) stay below 2^259 in magnitude, results below 2^257 + p.
+// Bounds (|limb| of the two operands of fe_mul, all nine limbs; the call-site audit is DESIGN 4.6): one operand <= 2^30 (a carry-passed
+// value plus one lazy add or sub), the other <= 2^29 + 16 (carry-passed, limbs in [-4, 2^29 + 4), or a difference of two such values).
+// Then every column is below 9*2^30*(2^29+16) + 8*2^58 + carry < 6.6*2^60 < 2^63 in magnitude.  The result is exact for ANY operands inside
+// these limb bounds (values up to 2^262 and 2^261: its top limb then reaches 2^30); the kernels' values stay within a few p.
+// Lazy SUMS are bounded separately: no carry pass reduces limb 8, and an int32 top limb holds 282 terms of magnitude p (kernels.h:
+// kLazySumMaxP).
 #pragma once
 #include <utility>
 #include "fr_device.hpp"
@@ -123,8 +126,9 @@ __device__ __forceinline__ Fe fe_normalize(const Fe &a) {
 }
 
 // One parallel carry-save pass: every limb sheds its bits above 2^29 into the next limb at once (no ripple, three
-// independent ops per limb).  For |limbs| < 2^31 the result has limbs 0..7 in [-4, 2^29 + 4): as good as normalised
-// for the product bounds, at a latency of three instructions instead of a 24-deep dependent chain.  Value unchanged.
+// independent ops per limb).  For any int32 in limbs 0..7 the result has limb 0 in [0, 2^29) and limbs 1..7 in [-4, 2^29 + 4): as good as
+// normalised for the product bounds, at a latency of three instructions instead of a 24-deep dependent chain.  Value unchanged.  Limb 8
+// takes limb 7's carry and is NOT reduced (it must have room for a carry of [-4, 3]): a lazy sum's whole magnitude collects there.
 __device__ __forceinline__ Fe fe_carry_pass(const Fe &a) {
     Fe r;
     r.l[0] = a.l[0] & kFeMask;
@@ -285,7 +289,8 @@ __device__ __forceinline__ Fe fe_mul2_chain_cols(const Fe &a, const Fe &b, const
     return r;
 }
 
-// a * b / 2^261 (mod p), result value in (a b / 2^261 - p, a b / 2^261], i.e. |.| < 2^257 + p; result limbs 0..7 in [0, 2^29), limb 8 signed and small.
+// a * b / 2^261 (mod p), result value in (a b / 2^261 - p, a b / 2^261] -- (-p, 2^251] for canonical operands, (-p - 2^251, 2^251 + j^2 p / 70) for
+// entries of round j; result limbs 0..7 in [0, 2^29), limb 8 signed: floor(value / 2^232), |.| <= 2^30 + 1 at the operands' limb bounds.
 template <typename B, bool kChain = kChainDefault>
 __device__ __forceinline__ Fe fe_mul_t(const Fe &a, const B &b) {
     if constexpr (kChain && kChainColumns) return fe_mul_chain_cols<B>(a, b, std::make_integer_sequence<int, 17>{});
@@ -439,17 +444,19 @@ __device__ __forceinline__ void fe_pin3(Fe &a, Fe &b, Fe &c) {
                  : "memory");
 }
 
-// Exact canonical conversion: any value with |v| < 2^260 -> the representative in [0, p) as 8 x u32.
+// Exact canonical conversion: limbs with room for normalize's carries and ANY int32 top limb after it (|v| < 2^263, about 282 p: the
+// whole range a lazy sum can hold, kernels.h: kLazySumMaxP) -> the representative in [0, p) as 8 x u32.
 __device__ __forceinline__ Fr fe_to_fr(const Fe &a) {
     // 1. normalise, estimate the quotient by p from the top limb (= floor(v / 2^232))
     Fe n = fe_normalize(a);
     constexpr int32_t PH = 0x0073eda7; // floor(p / 2^232)
-    // q = floor(top / (PH + 1)) for top >= 0, and -(floor((-top - 1) / PH) + 1) for top < 0, by float reciprocal
-    // (|top| < 2^28; the estimate only has to leave a remainder in [0, 2p), the exact step below finishes).
+    // q = floor(top / (PH + 1)) for top >= 0, and -ceil(-top / PH) for top < 0, in 32-bit unsigned division (the negation is made in unsigned arithmetic,
+    // so -2^31 is an operand like any other).  The estimate only has to leave a remainder in [0, 2p), the exact step below finishes: v - q p < (PH + 1) 2^232 +
+    // |q| (PH + 1 - p / 2^232) 2^232 < p + 193 * 2^232 for |q| <= 283, and >= 0 because q (PH + 1) <= top resp. |q| PH >= |top|.
     const int32_t top = n.l[8];
     int32_t q;
     if (top >= 0) q = (int32_t)((uint32_t)top / (uint32_t)(PH + 1));
-    else q = -(int32_t)(((uint32_t)(-top) + (uint32_t)PH - 1u) / (uint32_t)PH);
+    else q = -(int32_t)((0u - (uint32_t)top + (uint32_t)PH - 1u) / (uint32_t)PH);
     // 2. v -= q * p  (64-bit per limb, then carry-normalise)
     int64_t c = 0;
     uint32_t w[9];

@@ -192,6 +192,12 @@ struct TailArgs {
 // The same rounds with the tables resident in LDS (kernels_tail.hip: k_tail_slices): block g of B owns a contiguous range of every
 // table for the whole launch; one hand-over per round (its sums -> block 0) as self-validating words in `xw`.
 constexpr int kTsBlock = 256, kTsMaxBlocks = 256;
+// Lazy sums of carry-free elements (fe_carry_pass(fe_add(acc, x)), lane by lane and down a shuffle tree) never reduce limb 8: the int32
+// top limb holds floor(sum / 2^232).  A term of magnitude p puts p >> 232 = 7597479 there (7597480 for a negative one), and
+// 2^31 / 7597479 = 282.6: at most 282 terms of magnitude p may meet in one accumulator before it has to be reduced
+// (fe_from_fr(fe_to_fr(acc)), exact for every int32 top limb).  The rule, wave-uniform: terms x (worst magnitude of a term in units of p).
+constexpr uint32_t kLazySumMaxP = 282;
+__host__ __device__ constexpr bool lazy_sum_needs_reduce(uint64_t terms, uint32_t worst_p) { return terms * (uint64_t)worst_p > (uint64_t)kLazySumMaxP; }
 constexpr uint64_t kTsMaxPairs = 1u << 16; // it takes over from the first latency-bound round (kSmallRoundPairs) where the slices fit LDS, and up to two
                                            // rounds earlier for shapes with few multiplications per pair (tail_slices_blocks)
 // hand-over area (64-bit words): a ring of four accumulator sets (8 groups x kMetaCombos x 8 words) | the last entries of merging blocks
@@ -207,11 +213,18 @@ struct TailSlicesArgs {
     uint32_t fin_bytes;   // (filled in by the launcher: LDS layout)
     uint32_t lds_entries;
     uint32_t stage_off;
+    uint32_t worst_p;     // a bound on one product's magnitude in this launch's first round, in units of p (tail_worst_p); round j: + j
 };
 // blocks for a tail that starts with `first_pairs` pairs, or 0 when the slices do not fit LDS (the caller then takes k_tail_rounds)
 // max_blocks: how many blocks of the kernel the DEVICE holds at once (tail_slices_max_blocks): the blocks wait for each other, so a grid that is
 // not co-resident (a CPX / DPX partition, masked CUs) would stall until its waits expire -- fewer, larger slices then, or 0 if those do not fit
-int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_combos, int max_multiplicands, int max_blocks);
+// worst_p: tail_worst_p of the tables the tail starts from -- a lane adds up to 32 products (33 terms with its reduced sum) between two
+// reductions, which has to stay inside kLazySumMaxP too
+int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_combos, int max_multiplicands, int max_blocks, uint32_t worst_p);
+// The magnitude, in units of p, that the LDS-resident tail counts for one product of its first round.  Tables in the internal format have
+// been bound `lazy_binds` times with fe_mul_bind and a carry pass, never reduced: fe_mul_bind's term lies in (-p - 2^230, 2^230), so an
+// entry lies in (-(lazy_binds + 1) p, p) and sinks by about p / 2 a round on average; canonical tables bound on the way in: (-p, p).
+constexpr uint32_t tail_worst_p(uint32_t lazy_binds) { return lazy_binds + 2; }
 int tail_slices_max_blocks(int device, int max_multiplicands); // occupancy of k_tail_slices<.> at its LDS limit x the device's CUs (0: unknown)
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, DEVICE): thread ranks of one process drive several GPUs
 hipError_t ensure_dynamic_lds(const void *kernel, int bytes, bool (&done)[64]);

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_proofs(const BatchArgs A, co
                 if (!bt_fetch_challenge(B, tag - 1u, (j - 1u) & 1u)) break;
                 bt_bind(B, E);
             }
-            bt_sum_publish<kSlots>(B, ln, prod_of, E, tag);
+            bt_sum_publish<kSlots>(B, ln, prod_of, E, tag, j + 1u);
         }
     }
 }

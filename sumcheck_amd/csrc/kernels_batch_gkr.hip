@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, co
                 if (tid < 4) reinterpret_cast<uint64_t *>(u_sh)[4 * (j - 1u) + tid] = r_sh[tid];
                 bt_bind(B, E); // (the barriers inside also publish u_sh)
             }
-            if (j < dim) bt_sum_publish<kSlots>(B, ln, prod_of, E, A.tag0 + j);
+            if (j < dim) bt_sum_publish<kSlots>(B, ln, prod_of, E, A.tag0 + j, j + 1u);
         }
         if (dropped) continue;
         // ---- between the phases: f2(u) is what is left of table 1; f3 * f2(u) -> table 1 (mod.rs:71-75); eq(u, .); f1(g, u, .) -> table 0 --
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, co
                 if (!bt_fetch_challenge(B, A.tag0 + j - 1u, (j - 1u) & 1u)) break;
                 bt_bind(B, E);
             }
-            bt_sum_publish<kSlots>(B, ln, prod_of, E, A.tag0 + j);
+            bt_sum_publish<kSlots>(B, ln, prod_of, E, A.tag0 + j, r + 1u);
         }
     }
 }

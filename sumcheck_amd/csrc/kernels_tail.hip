@@ -330,9 +330,12 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
                     for (const uint32_t e = my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
                 }
                 acc = fe_carry_pass(fe_add(acc, prod));
-                if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31; never reached here)
+                if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31: reached where a lane has 32 pairs or more, L <= 8 at 256 pairs a block)
             }
         }
+        // one accumulator takes the block's whole sum of a combination after the tree: every lane's sum is made canonical first where pairs x
+        // (worst product in p) would leave its int32 top limb (kernels.h: kLazySumMaxP; wave-uniform; the bound grows by p with every bind)
+        if (lazy_sum_needs_reduce(pairs_here, S.worst_p + (uint32_t)j)) acc = fe_from_fr(fe_to_fr(acc));
         for (int off = L >> 1; off >= 1; off >>= 1) acc = fe_carry_pass(fe_add(acc, fe_shfl_down(acc, off)));
         TS_STAMP(j, 3); // this block's sums
         if (B == 1) {
@@ -341,7 +344,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
             // ---- this block's sums -> block 0.  The canonical 32-bit words are ADDED, by the memory system, into 64-bit accumulators:
             // (1 << 44 | word) per block, so that a word whose top bits read the number of its contributors IS complete -- block 0's poll
             // of the accumulators is the fetch of the sums (a few hundred words whatever the number of blocks).  Eight groups of blocks
-            // (g & 7) keep a sum below 32 p (fe_to_fr's range); a ring of four accumulator sets, the one of round j + 2 zeroed by block 0.
+            // (g & 7) keep a sum below 32 p (fe_to_fr takes up to 282 p); a ring of four accumulator sets, the one of round j + 2 zeroed by block 0.
             if (combo_live && my_q == 0) {
                 const Fr sv = fe_to_fr(acc);
 #pragma unroll
@@ -445,7 +448,7 @@ static size_t ts_fin_bytes(int K, int D) { return ((size_t)K * D * (D + 2) * 32 
 static size_t ts_stage_bytes(int n_combos, int B) { return B > 1 ? 8 * (size_t)n_combos * 64 + 8 * (size_t)n_combos * 32 + 16 : 0; }
 constexpr size_t kTsLdsMax = 144 * 1024; // of the CU's 160 KB (one block per CU; its static LDS is ~3 KB)
 
-int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_combos, int max_multiplicands, int max_blocks) {
+int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_combos, int max_multiplicands, int max_blocks, uint32_t worst_p) {
     if (max_blocks < 1) return 0;
     if (first_pairs == 0 || (first_pairs & (first_pairs - 1)) != 0 || first_pairs > kTsMaxPairs) return 0;
     if (first_pairs > kSmallRoundPairs) {
@@ -462,6 +465,14 @@ int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_c
     while (B > 1 && (uint64_t)B > first_pairs / 2) B >>= 1;
     if (first_pairs <= 32) B = 1;
     while (B > max_blocks) B >>= 1; // (every block must be resident: they hand over to each other)
+    // a lane adds its share of a combination's products lazily and reduces its sum every 32 of them (and, by lazy_sum_needs_reduce, in front
+    // of the shuffle tree): up to 33 terms of worst_p p each meet in its int32 top limb, which holds kLazySumMaxP p
+    {
+        int L = 64;
+        while (L * n_combos > kTsBlock) L >>= 1;
+        const uint64_t passes = (first_pairs / (uint64_t)B + L - 1) / L;
+        if (lazy_sum_needs_reduce(std::min<uint64_t>(passes, 32) + 1, worst_p)) return 0;
+    }
     const size_t bytes = ts_fin_bytes(K, D) + ts_lds_entries(first_pairs, B) * (size_t)n_tables * (kTsEnt * 4) + ts_stage_bytes(n_combos, B);
     return bytes <= kTsLdsMax ? B : 0; // (more blocks than kTsMaxBlocks would be needed: the caller runs this round as launches and asks again)
 }

@@ -961,10 +961,16 @@ bool tail_possible(sc_prover *p, bool slices = false) {
 // r_or_null = the challenge the first of them binds; max_spins = how long block 0 waits for each later challenge.
 // The tables resident in LDS for the whole tail (kernels_tail.hip: k_tail_slices) where the shape allows: every product in carry-free
 // arithmetic, the slices within a CU's LDS.  sc_set_policy("tail_slices", 0): k_tail_rounds everywhere (A/B runs, tests of the older path).
+// tail_worst_p of the tables as they stand: every round so far may have bound a table in the internal format lazily
+static uint32_t tail_tables_worst_p(sc_prover *p) {
+    bool f29 = false;
+    for (uint32_t u = 0; u < p->U; ++u) f29 = f29 || p->tabs[u].cur_top != nullptr;
+    return scd::tail_worst_p(f29 ? p->round : 0);
+}
 int tail_slices_blocks_for(sc_prover *p) {
     if (scd::policy(scd::kPolTailSlices) == 0 || p->max_mult > (uint32_t)(p->wide_tree ? scd::kMaxWideM : scd::kMaxFusedM) || p->round >= p->nv) return 0;
     const int B = scd::tail_slices_blocks(1ULL << (p->nv - (p->round + 1)), (int)p->U, (int)p->K, (int)p->D, p->n_combos, (int)p->max_mult,
-                                          scd::tail_slices_max_blocks(p->device, (int)p->max_mult));
+                                          scd::tail_slices_max_blocks(p->device, (int)p->max_mult), tail_tables_worst_p(p));
     if (B <= 0) return 0;
     if (!p->d_tail_xw) { // tagged hand-over words, owned by the handle: zero once, tags only ever grow
         if (hipMalloc(reinterpret_cast<void **>(&p->d_tail_xw), scd::kTsXwWords * 8) != hipSuccess ||
@@ -1038,6 +1044,7 @@ int tail_launch(sc_prover *p, uint32_t n_rounds, const sch::Fr *r_or_null, uint3
         S.xw = p->d_tail_xw;
         S.tag0 = p->ts_tag;
         S.mail_vram = host_mailbox_only ? nullptr : p->d_vram_mail;
+        S.worst_p = tail_tables_worst_p(p);
         p->ts_tag += n_rounds;
         grid = slices_B;
         HIP_TRY(scd::launch_tail_slices(S, p->meta, fm, (int)p->max_mult, p->stream));

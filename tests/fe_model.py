@@ -1,0 +1,253 @@
+"""Exact integer model of the carry-free field arithmetic (sumcheck_amd/csrc/fe_device.hpp and what is built on it), and the operand
+vectors that pin every primitive at the limb and value ranges its call sites can reach.
+
+Plain Python integers.  Nothing here walks limbs the way the kernels do: a Montgomery product is DEFINED as the integer
+(T - M p) / 2^k with M = T p^-1 mod 2^k, and its limb form (limbs 0..7 in [0, 2^29), limb 8 the signed rest) is unique, so the device's
+limbs compare bit for bit.  The lazy primitives (carry pass, line, combinations) are checked by value and by the limb ranges their
+comments promise.
+"""
+import functools
+import random
+
+P = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+W = 29                      # bits per limb
+NL = 9                      # limbs
+K = W * NL                  # 261: the carry-free Montgomery radix is 2^261
+MASK = (1 << W) - 1
+PH = P >> 232               # 7597479: what a value of p puts into the top limb
+R256 = (1 << 256) % P       # the tables' Montgomery radix
+SEED = 0x5C20241008
+N_RANDOM = 2000
+I32_MAX = (1 << 31) - 1
+
+# sc_debug_fe_op's op numbers (kernels_selftest.hip: FeOp)
+OP_NORMALIZE, OP_CARRY_PASS, OP_TO_FR, OP_ROUND_TRIP, OP_FROM_FR = 0, 1, 2, 3, 4
+OP_MUL, OP_MUL_CHAIN, OP_MUL_U, OP_MUL_U_CHAIN, OP_MUL2, OP_MUL2_CHAIN, OP_BIND, OP_BIND_CHAIN = 5, 6, 7, 8, 9, 10, 11, 12
+OP_SHL5_MUL_U, OP_LINE, OP_ACCUM, OP_FOLD_CELL, OP_WIDE_VALUE, OP_WIDE_EXT = 13, 14, 15, 16, 17, 18
+
+NODE_INF = 0x7FFFFFFF
+MAX_FUSED_M = 8
+LAZY_SUM_MAX_P = 282        # kernels.h: kLazySumMaxP = floor(2^31 / 7597479)
+
+
+def node_value(s: int) -> int:
+    """kernels.h: the evaluation nodes in the kernels' order 0, 1, inf, -1, 2, -2, 3, ..."""
+    if s < 3:
+        return (0, 1, NODE_INF)[s]
+    return -((s - 3) // 2 + 1) if (s - 3) % 2 == 0 else (s - 3) // 2 + 2
+
+
+# ---- limbs <-> integers -------------------------------------------------------------------------------------------------------------------
+def value(limbs) -> int:
+    return sum(int(l) << (W * i) for i, l in enumerate(limbs))
+
+
+def limbs_of(v: int):
+    """the unique form with limbs 0..7 in [0, 2^29) and limb 8 the signed rest"""
+    return [(v >> (W * i)) & MASK for i in range(8)] + [v >> (W * 8)]
+
+
+def words_of(v: int):
+    """8 x u32 of a value in [0, 2^256)"""
+    assert 0 <= v < (1 << 256)
+    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+
+
+def fits_i32(limbs) -> bool:
+    return all(-(1 << 31) <= l <= I32_MAX for l in limbs)
+
+
+# ---- the model ------------------------------------------------------------------------------------------------------------------------------
+def mont_exact(T: int, k: int = K) -> int:
+    """(T - M p) / 2^k with M = T p^-1 mod 2^k, 0 <= M < 2^k: the subtractive Montgomery reduction as one exact division"""
+    M = (T * pow(P, -1, 1 << k)) % (1 << k)
+    q, r = divmod(T - M * P, 1 << k)
+    assert r == 0
+    return q
+
+
+def fe_mul(a, b):
+    return limbs_of(mont_exact(value(a) * value(b)))
+
+
+def fe_mul2_sum(a, b, c, d):
+    return limbs_of(mont_exact(value(a) * value(b) + value(c) * value(d)))
+
+
+def bind_rows(r_std: int):
+    """BindConst: row i = (r 2^(29 i + 58)) mod p as a plain integer, r the challenge's standard value"""
+    return [(r_std << (W * i + 58)) % P for i in range(NL)]
+
+
+def fe_mul_bind(d, r_std: int):
+    S = sum(int(d[i]) * Ri for i, Ri in enumerate(bind_rows(r_std)))
+    return limbs_of(mont_exact(S, 58))
+
+
+def fe_shl5_mul_u(a, x: int):
+    """fe_mul_u(a, feu_shl5(x)): the multiplier is the integer 32 x, not reduced"""
+    return limbs_of(mont_exact(value(a) * (32 * x)))
+
+
+def wide_fold(lanes) -> int:
+    return sum(int(l) << (32 * j) for j, l in enumerate(lanes)) % P
+
+
+@functools.lru_cache(maxsize=None)
+def lagrange_weights(m: int, x: int):
+    """a polynomial of degree m from its values at the consecutive integers -((m-1)//2) .. m//2 and its leading coefficient, at x:
+    {node j: weight}, and the leading coefficient's weight (wide_tree.hpp: wide_lagrange, wide_lead) -- derived here from the definition"""
+    from fractions import Fraction
+    nodes = list(range(-((m - 1) // 2), m // 2 + 1))
+    w = {}
+    for j in nodes:
+        f = Fraction(1)
+        for n in nodes:
+            if n != j:
+                f *= Fraction(x - n, j - n)
+        assert f.denominator == 1
+        w[j] = int(f)
+    lead = 1
+    for n in nodes:
+        lead *= x - n
+    return w, lead
+
+
+def wide_expected(m: int, t: int, vals) -> int:
+    """the value at node index t of the degree-m polynomial held as vals[s] = value at node index s (s = 2: leading coefficient)"""
+    x = node_value(t)
+    w, lead = lagrange_weights(m, x)
+    tot = lead * value(vals[2])
+    for s in range(len(vals)):
+        if s == 2:
+            continue
+        j = node_value(s)
+        if j in w and s <= max(m, 2):
+            tot += w[j] * value(vals[s])
+    return tot
+
+
+# ---- operand vectors ------------------------------------------------------------------------------------------------------------------------
+def limb_corners(lo: int, hi: int, top_lo: int = None, top_hi: int = None):
+    """the limb-level corners of the box [lo, hi]^8 x [top_lo, top_hi]"""
+    top_lo = lo if top_lo is None else top_lo
+    top_hi = hi if top_hi is None else top_hi
+    out = [[hi] * 8 + [top_hi], [lo] * 8 + [top_lo]]
+    out.append([(hi if i % 2 == 0 else lo) for i in range(8)] + [top_hi])
+    out.append([(lo if i % 2 == 0 else hi) for i in range(8)] + [top_lo])
+    for i in range(NL):
+        for bound in ((lo, hi) if i < 8 else (top_lo, top_hi)):
+            v = [0] * NL
+            v[i] = bound
+            out.append(v)
+    return out
+
+
+def value_corners(bound: int, max_p: int):
+    """value-level extremes as canonical limbs: +-(bound - 1), 0, +-1, p, p - 1, and multiples of p up to max_p (both signs)"""
+    vals = [bound - 1, -(bound - 1), 0, 1, -1, P, P - 1, 1 - P, -P]
+    k = 2
+    while k <= max_p:
+        vals += [k * P, -k * P, k * P - 1, 1 - k * P]
+        k *= 2
+    if max_p >= 1:
+        vals += [max_p * P, -max_p * P]
+    return [limbs_of(v) for v in vals if abs(v) < bound]
+
+
+def random_limbs(rng: random.Random, n: int, lo: int, hi: int, top_lo: int = None, top_hi: int = None):
+    top_lo = lo if top_lo is None else top_lo
+    top_hi = hi if top_hi is None else top_hi
+    return [[rng.randint(lo, hi) for _ in range(8)] + [rng.randint(top_lo, top_hi)] for _ in range(n)]
+
+
+def box(lo, hi, top_lo=None, top_hi=None, value_bound=None, max_p=0):
+    """a description of an operand's audited range"""
+    return dict(lo=lo, hi=hi, top_lo=lo if top_lo is None else top_lo, top_hi=hi if top_hi is None else top_hi, value_bound=value_bound, max_p=max_p)
+
+
+def in_box(limbs, bx) -> bool:
+    return all(bx["lo"] <= l <= bx["hi"] for l in limbs[:8]) and bx["top_lo"] <= limbs[8] <= bx["top_hi"]
+
+
+def corners_of(bx):
+    out = limb_corners(bx["lo"], bx["hi"], bx["top_lo"], bx["top_hi"])
+    if bx["value_bound"] is not None:
+        out += [v for v in value_corners(bx["value_bound"], bx["max_p"]) if in_box(v, bx)]
+    return out
+
+
+def operand_sets(boxes, rng: random.Random, n_random: int = N_RANDOM):
+    """rows of operands (one list of 9 limbs per box): the corners of every operand against the corners of the others (cyclically
+    shifted, so that every corner of every operand meets several corners of the rest), then uniform draws inside the boxes"""
+    cs = [corners_of(b) for b in boxes]
+    n = max(len(c) for c in cs)
+    rows = []
+    for shift in range(n if len(boxes) > 1 else 1):
+        for i in range(n):
+            rows.append([cs[k][(i + k * shift) % len(cs[k])] for k in range(len(boxes))])
+    rnd = [random_limbs(rng, n_random, b["lo"], b["hi"], b["top_lo"], b["top_hi"]) for b in boxes]
+    rows += [[rnd[k][i] for k in range(len(boxes))] for i in range(n_random)]
+    return rows
+
+
+# The audited ranges.  T29 = 2^29.
+T29 = 1 << W
+# fe_mul / fe_mul_u, first operand: a value plus one lazy add or sub of carry-passed values -- |limb| <= 2^30 on all nine limbs
+BOX_MUL_A = box(-(1 << 30), 1 << 30)
+# fe_mul, second operand: a carry-passed value or a difference of two (wide_quad: fe_sub(h, l) of entries in [-4, 2^29 + 4)) -- |limb| <= 2^29 + 16
+BOX_MUL_B = box(-(T29 + 16), T29 + 16)
+# fe_mul_u's uniform operand: normalised limbs (feu_shl5's result, a challenge)
+BOX_FEU = box(0, MASK)
+# fe_mul2_sum: four carry-passed operands
+BOX_MUL2 = box(-(T29 + 4), T29 + 4)
+# fe_mul_bind: the lazy difference of two table entries
+BOX_BIND_D = box(-(T29 + 16), T29 + 16)
+# fe_carry_pass: any int32 in limbs 0..7 (sums of four carry-passed values, wide_quad_m1); limb 8 must take a carry of [-4, 3]
+BOX_CARRY = box(-(1 << 31), I32_MAX, -(1 << 31) + 8, I32_MAX - 8)
+# fe_normalize: limbs that take a carry of [-4, 3] without leaving int32
+BOX_NORM = box(-(1 << 31) + 8, I32_MAX - 8)
+# fe_to_fr: carry-passed limbs, ANY top limb (a lazy sum of 282 products of magnitude p fills the int32: kLazySumMaxP)
+BOX_TO_FR = box(-8, T29 + 8, -(1 << 31) + 8, I32_MAX - 8, value_bound=LAZY_SUM_MAX_P * P, max_p=LAZY_SUM_MAX_P - 1)
+# fe_line: two table entries as the LDS-resident kernels hold them -- carry-passed, the value a lazy sum within (-16 p, 16 p)
+BOX_LINE = box(-4, T29 + 3, -16 * PH - 16, 16 * PH + 16, value_bound=16 * P, max_p=15)
+# fe_comb5: a half's values -- fe_mul results and carry-passed sums of five of them (wide_quad_m1 / _p2)
+BOX_COMB5 = box(-8, T29 + 8, -8 * PH - 8, 8 * PH + 8, value_bound=8 * P, max_p=7)
+# wide_ext: a product tree's values -- fe_mul results of operands within 2 p
+BOX_WIDE_EXT = box(0, MASK, -2 * PH - 2, 2 * PH + 2, value_bound=2 * P, max_p=1)
+
+LINE_NODES = [node_value(t) for t in range(MAX_FUSED_M + 1)]  # 0, 1, inf, -1, 2, -2, 3, -3, 4
+# wide_value<m, t> as the trees of five to eight instantiate it (m = 1: the single factor's line through fe_comb5)
+WIDE_VALUE_CASES = [(4, t) for t in range(5, 9)] + [(3, t) for t in range(4, 8)] + [(2, t) for t in range(3, 7)] + [(1, t) for t in range(3, 6)]
+# wide_ext<m, t> as the trees of nine to twelve instantiate it
+WIDE_EXT_CASES = [(8, t) for t in range(9, 13)] + [(mb, t) for mb in range(1, 5) for t in range(max(mb, 2) + 1, mb + 9)]
+
+
+def to_fr_vectors(rng: random.Random):
+    """fe_to_fr: the box's corners, and the top limb on both sides of every quotient step out to the int32's end"""
+    rows = corners_of(BOX_TO_FR) + random_limbs(rng, N_RANDOM, BOX_TO_FR["lo"], BOX_TO_FR["hi"], BOX_TO_FR["top_lo"], BOX_TO_FR["top_hi"])
+    lows = [[0] * 8, [MASK] * 8, [T29 + 8] * 8, [-8] * 8]
+    for k in range(1, LAZY_SUM_MAX_P + 1):
+        for top in (k * (PH + 1) - 1, k * (PH + 1), -k * PH, -k * PH - 1):
+            if BOX_TO_FR["top_lo"] <= top <= BOX_TO_FR["top_hi"]:
+                rows.append(lows[k % 4] + [top])
+                rows.append([rng.randint(0, MASK) for _ in range(8)] + [top])
+    return rows
+
+
+def fold_cell_vectors(rng: random.Random):
+    top = (1 << 63) - 1
+    rows = [[top] * 8, [0] * 8, [1] + [0] * 7, [0] * 7 + [top], [top] + [0] * 7, [0xFFFFFFFF] * 8, [1 << 32] * 8]
+    for j in range(8):
+        v = [0] * 8
+        v[j] = top
+        rows.append(v)
+    rows += [[rng.randint(0, top) for _ in range(8)] for _ in range(N_RANDOM)]
+    # sums the GKR initialisations make: up to 2^31 canonical words per lane
+    rows += [[rng.randint(0, (1 << 63) - 1) >> rng.randint(0, 40) for _ in range(8)] for _ in range(200)]
+    return rows
+
+
+def product_regimes():
+    """the accumulate op's terms: the ends of fe_mul's window on canonical operands -- 1 - p (limb 8 = -7597480) and p - 1 (limb 8 = 7597479)"""
+    return {"1-p": limbs_of(1 - P), "p-1": limbs_of(P - 1)}

@@ -93,3 +93,45 @@ def hip_poly_from(nv, shapes, tabs, coefs, device=None):
     for k, sh in enumerate(shapes):
         poly.add_product([mles[i] for i in sh], coefs[k])
     return poly, mles
+
+
+# ---- sc_debug_fe_op (kernels_selftest.hip): one lane per element through one primitive of the carry-free arithmetic -------------------------
+FE_DEV = "cuda:0"
+
+
+def fe_dev_limbs(rows):
+    """rows of int32 limbs (any row length that is a multiple of 9) -> device tensor"""
+    import torch
+    return torch.from_numpy(np.asarray(rows, dtype=np.int64).astype(np.int32)).contiguous().to(FE_DEV)
+
+
+def fe_dev_words(vals):
+    """values in [0, 2^256) as 8 words in a 9-int row"""
+    import torch
+    rows = np.asarray([[(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)] + [0] for v in vals], dtype=np.uint32)
+    return torch.from_numpy(rows.view(np.int32)).contiguous().to(FE_DEV)
+
+
+def fe_run_op(op, n, a, b=None, c=None, d=None, params=(), aux_tail=None):
+    """sc_debug_fe_op(op) over n elements -> (n, 9) int32 on the host; params: aux[0..3], aux_tail: the u64 words behind them"""
+    import ctypes as C
+    import torch
+    import sumcheck_amd as sc
+    f = sc.lib().sc_debug_fe_op  # (a debug entry: exported, not declared in _lib.SIGNATURES)
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_uint64]
+    aux = list(params) + [0] * (4 - len(params))
+    aux_np = np.asarray([x & 0xFFFFFFFFFFFFFFFF for x in aux], dtype=np.uint64)
+    if aux_tail is not None:
+        aux_np = np.concatenate([aux_np, np.asarray(aux_tail, dtype=np.uint64).reshape(-1)])
+    aux_t = torch.from_numpy(aux_np.view(np.int64)).to(FE_DEV)
+    out = torch.full((n, 9), 0x5A5A5A5A, dtype=torch.int32, device=FE_DEV)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    torch.cuda.synchronize()
+    rc = f(op, ptr(a), ptr(b), ptr(c), ptr(d), ptr(aux_t), ptr(out), n)
+    assert rc == 0, f"sc_debug_fe_op({op}) returned {rc}"
+    return out.cpu().numpy()
+
+
+def fe_as_fr(out_row) -> int:
+    return sum(int(np.uint32(w)) << (32 * i) for i, w in enumerate(out_row[:8]))

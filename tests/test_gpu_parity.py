@@ -25,23 +25,52 @@ def _torch_dev():
     return torch.device("cuda:0")
 
 
-@pytest.mark.parametrize("op,name", [(0, "mul"), (1, "add"), (2, "sub"), (3, "mul"), (4, "mul"), (5, "mulu")])
+FE = "fe"  # not an op of sc_fr_elementwise: the production carry-free product, through sc_debug_fe_op (kernels_selftest.hip)
+
+
+def _dmul(op, x, y):
+    """x * y on the device, Montgomery limbs in and out.  op 0 / 3 / 4: sc_fr_elementwise's saturated products (0 is fr_mul, which is the
+    Comba product, the same function as op 4; 3 is CIOS).  FE: the carry-free 9 x 29-bit path as the LDS-resident kernels' bind runs it,
+    fe_to_fr(fe_mul_u<true>(fe_from_fr(x), feu_shl5(y))) -- the 2^5 on the multiplier makes it an ordinary Montgomery product."""
+    if op != FE:
+        out = np.empty_like(x)
+        _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data), C.c_void_p(out.ctypes.data), x.shape[0]))
+        return out
+    import torch
+    from tests import fe_model as fm
+    run_op = H.fe_run_op
+    n = x.shape[0]
+
+    def rows(v):  # (n, 4) u64 -> 8 words in a 9-int row, on the device
+        r = np.zeros((n, 9), dtype=np.uint32)
+        r[:, :8] = np.ascontiguousarray(v).view(np.uint32).reshape(n, 8)
+        return torch.from_numpy(r.view(np.int32)).to("cuda:0")
+    limbs = torch.from_numpy(run_op(fm.OP_FROM_FR, n, rows(x))).to("cuda:0")
+    prod = torch.from_numpy(run_op(fm.OP_SHL5_MUL_U, n, limbs, rows(y))).to("cuda:0")
+    out = run_op(fm.OP_TO_FR, n, prod)
+    return np.ascontiguousarray(out[:, :8]).view(np.uint32).view(np.uint64).reshape(n, 4)
+
+
+@pytest.mark.parametrize("op,name", [(0, "mul"), (1, "add"), (2, "sub"), (3, "mul"), (4, "mul"), (5, "mulu"), (FE, "mul")])
 def test_field_arithmetic_every_implementation(op, name):
-    """each device implementation of Fr mul/add/sub against the oracle on edge values and 100k random pairs"""
+    """each device implementation of Fr mul/add/sub against the oracle on edge values and 100k random pairs (FE: the carry-free product)"""
     from oracle import pyoracle as po
-    rng = np.random.default_rng(op)
+    stream = 6 if op == FE else op
     edge = [0, 1, 2, po.P - 1, po.P - 2, (po.P - 1) // 2, (po.P + 1) // 2, po.R, po.R2, (1 << 255) % po.P, 0xFFFFFFFF, 1 << 32,
             (1 << 64) - 1, 1 << 64, po.P - (1 << 32), po.P - (1 << 224)]
     ea = cref.ints_to_mont([x for x in edge for _ in edge])
     eb = cref.ints_to_mont([y for _ in edge for y in edge])
     n = 100_000
-    a = np.concatenate([ea, cref.synth_table(1, 2 * op, n)])
-    b = np.concatenate([eb, cref.synth_table(1, 2 * op + 1, n)])
+    a = np.concatenate([ea, cref.synth_table(1, 2 * stream, n)])
+    b = np.concatenate([eb, cref.synth_table(1, 2 * stream + 1, n)])
     if name == "mulu":
         b = np.repeat(b[len(edge) * 3 + 5][None, :], a.shape[0], axis=0)  # uniform operand
     a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    out = np.empty_like(a)
-    _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_void_p(out.ctypes.data), a.shape[0]))
+    if op == FE:
+        out = _dmul(FE, a, b)
+    else:
+        out = np.empty_like(a)
+        _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_void_p(out.ctypes.data), a.shape[0]))
     # oracle: canonical residues via python ints on a sample + the C oracle on everything
     want = np.empty_like(a)
     fn = {"mul": "mul", "mulu": "mul", "add": "add", "sub": "sub"}[name]
@@ -56,18 +85,17 @@ def test_field_arithmetic_every_implementation(op, name):
     assert oi == [pyf(x, y) for x, y in zip(ai, bi)]
 
 
-@pytest.mark.parametrize("op", [0, 3, 4])
+@pytest.mark.parametrize("op", [0, 3, 4, FE])
 def test_two_adic_root_of_unity_through_the_device_multipliers(op):
     """Published known answer (third-party pin): 7^((p-1)/2^32) is the generator of BLS12-381 Fr's 2^32-th roots of unity,
-    0x16a2...0d2b.  334 DEPENDENT Montgomery products through the device multiplier (op 0: the production carry-free fe_mul;
-    3 / 4: the saturated CIOS and Comba products) must land on it; 31 more squarings give -1, one more 1."""
+    0x16a2...0d2b.  334 DEPENDENT Montgomery products through the device multiplier (op 0: fr_mul, the saturated Comba product,
+    the same function as op 4; 3: the saturated CIOS product; FE: the production carry-free product, 9 x 29-bit limbs and the 2^261
+    radix) must land on it; 31 more squarings give -1, one more 1."""
     from oracle import pyoracle as po
     from tests.test_oracle import TWO_ADIC_ROOT
 
     def dmul(x, y):
-        out = np.empty_like(x)
-        _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data), C.c_void_p(out.ctypes.data), x.shape[0]))
-        return out
+        return _dmul(op, x, y)
 
     base = np.ascontiguousarray(cref.ints_to_mont([7, 7, 7]))
     acc = np.ascontiguousarray(cref.ints_to_mont([1, 1, 1]))
@@ -82,18 +110,18 @@ def test_two_adic_root_of_unity_through_the_device_multipliers(op):
     assert cref.mont_to_ints(dmul(acc, acc)) == [1] * 3
 
 
-@pytest.mark.parametrize("op", [0, 3, 4])
+@pytest.mark.parametrize("op", [0, 3, 4, FE])
 def test_r3_published_constant_through_the_device_multipliers(op):
     """Published known answer: R^3 = 2^768 mod p = 0x6e2a...73af.  mont(R) squared is mont(R^2), whose raw limbs ARE R^3 -- for the
-    production multiplier (op 0) this goes through the 9 x 29-bit representation and its 2^261 radix, so the literal pins the 2^5
-    compensation; two more dependent squarings against Python's pow."""
+    carry-free multiplier (FE) this goes through the 9 x 29-bit representation and its 2^261 radix, so the literal pins the 2^5
+    compensation (ops 0 and 4 are the saturated Comba product, 3 the saturated CIOS product: no compensation there); two more dependent
+    squarings against Python's pow."""
     from oracle import pyoracle as po
     from tests.test_oracle import R3_PUBLISHED
     x = np.ascontiguousarray(cref.ints_to_mont([po.R] * 5))
     e = 1
     for step in range(3):
-        out = np.empty_like(x)
-        _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(x.ctypes.data), C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), x.shape[0]))
+        out = _dmul(op, x, x)
         x, e = out, 2 * e
         raws = [sum(int(v) << (64 * i) for i, v in enumerate(row)) for row in x]
         assert raws == [pow(2, 256 * (e + 1), po.P)] * 5
@@ -103,7 +131,7 @@ def test_r3_published_constant_through_the_device_multipliers(op):
 
 def test_add_sub_mul_edge_identities_on_the_device():
     """literal identities around (p - 1) / 2 and -1 through every device add / sub / mul: the places where a lazy or carry-free
-    representation has to wrap exactly"""
+    representation has to wrap exactly (mul: the saturated products, ops 0 / 3 / 4, and the carry-free one, FE)"""
     from oracle import pyoracle as po
     h, m1 = (po.P - 1) // 2, po.P - 1
     cases = [  # (op name, a, b, expected)
@@ -111,13 +139,16 @@ def test_add_sub_mul_edge_identities_on_the_device():
         ("sub", 0, 1, m1), ("sub", h, h + 1, m1), ("sub", 0, m1, 1), ("sub", m1, m1, 0), ("sub", 1, m1, 2), ("sub", h, m1, h + 1),
         ("mul", m1, m1, 1), ("mul", 2, h + 1, 1), ("mul", m1, h, h + 1), ("mul", m1, 1, m1), ("mul", h + 1, h + 1, pow(4, -1, po.P)),
     ]
-    for ops, name in (((1,), "add"), ((2,), "sub"), ((0, 3, 4), "mul")):
+    for ops, name in (((1,), "add"), ((2,), "sub"), ((0, 3, 4, FE), "mul")):
         sel = [c for c in cases if c[0] == name]
         a = np.ascontiguousarray(cref.ints_to_mont([c[1] for c in sel]))
         b = np.ascontiguousarray(cref.ints_to_mont([c[2] for c in sel]))
         for op in ops:
-            out = np.empty_like(a)
-            _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_void_p(out.ctypes.data), a.shape[0]))
+            if op == FE:
+                out = _dmul(FE, a, b)
+            else:
+                out = np.empty_like(a)
+                _lib.check(sc.lib().sc_fr_elementwise(op, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_void_p(out.ctypes.data), a.shape[0]))
             assert cref.mont_to_ints(out) == [c[3] for c in sel], (name, op)
 
 
