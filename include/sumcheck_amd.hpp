@@ -274,6 +274,92 @@ class ProverState { // prover.rs:19-33, tables resident in HBM
     size_t n_tables_ = 0;
 };
 
+// n x ProverState of ONE structure behind one sc_batch_prover handle: IPForMLSumcheck::prover_init_batch / prove_round_batch.  The caller owns
+// the transcript(s) and hands in every challenge: one VerifierMsg per instance, or one for all of them.
+class BatchProverState {
+  public:
+    size_t n = 0, num_vars = 0, max_multiplicands = 0;
+    BatchProverState() = default;
+    BatchProverState(sc_batch_prover *h, size_t n_, const ListOfProductsOfPolynomials &p)
+        : n(n_), num_vars(p.num_variables), max_multiplicands(p.max_multiplicands), h_(h), n_tables_(p.flattened_ml_extensions.size()) {}
+    BatchProverState(BatchProverState &&o) noexcept { *this = std::move(o); }
+    BatchProverState &operator=(BatchProverState &&o) noexcept {
+        if (h_) sc_batch_prover_free(h_);
+        n = o.n;
+        num_vars = o.num_vars;
+        max_multiplicands = o.max_multiplicands;
+        h_ = o.h_;
+        n_tables_ = o.n_tables_;
+        o.h_ = nullptr;
+        return *this;
+    }
+    ~BatchProverState() {
+        if (h_) sc_batch_prover_free(h_);
+    }
+    size_t round() const {
+        uint32_t r = 0;
+        check(sc_batch_prover_state(h_, 0, nullptr, nullptr, nullptr, &r));
+        return r;
+    }
+    std::vector<Fr> randomness(size_t i) const {
+        uint32_t cnt = 0;
+        check(sc_batch_prover_state(h_, (uint32_t)i, nullptr, &cnt, nullptr, nullptr));
+        std::vector<Fr> buf(std::max<size_t>(cnt, 1));
+        check(sc_batch_prover_state(h_, (uint32_t)i, buf[0].l, nullptr, nullptr, nullptr));
+        buf.resize(cnt);
+        return buf;
+    }
+    std::vector<DenseMultilinearExtension> flattened_ml_extensions(size_t i) const {
+        const size_t r = round();
+        const size_t nv = num_vars - (r > 0 ? r - 1 : 0);
+        std::vector<Fr> buf(n_tables_ << nv);
+        check(sc_batch_prover_state(h_, (uint32_t)i, nullptr, nullptr, buf[0].l, nullptr));
+        std::vector<DenseMultilinearExtension> out;
+        for (size_t u = 0; u < n_tables_; ++u)
+            out.push_back(DenseMultilinearExtension{nv, std::vector<Fr>(buf.begin() + (u << nv), buf.begin() + ((u + 1) << nv))});
+        return out;
+    }
+    // prove_as_subprotocol's final push without a bind (mod.rs:65-67)
+    void push_randomness(const std::vector<VerifierMsg> &v_msgs) {
+        const std::vector<Fr> r = challenges(v_msgs);
+        check(sc_batch_prover_push_randomness(h_, r[0].l, v_msgs.size() == 1 && n != 1 ? 1u : 0u));
+    }
+    // bind the last variable after the last round: per instance the U table evaluations at its point; the handle is exhausted until reset
+    std::vector<std::vector<Fr>> bind_final(const std::vector<VerifierMsg> &v_msgs) {
+        const std::vector<Fr> r = challenges(v_msgs);
+        std::vector<Fr> flat(n * std::max<size_t>(n_tables_, 1));
+        check(sc_batch_prover_bind_final(h_, r[0].l, v_msgs.size() == 1 && n != 1 ? 1u : 0u, flat[0].l));
+        std::vector<std::vector<Fr>> out(n);
+        for (size_t i = 0; i < n; ++i) out[i].assign(flat.begin() + i * n_tables_, flat.begin() + (i + 1) * n_tables_);
+        return out;
+    }
+    // rewind to round 0 without reallocating: over the tables the handle holds, or over n new polynomials of the same structure
+    void reset() { check(sc_batch_prover_reset(h_, nullptr)); }
+    void reset(const std::vector<const ListOfProductsOfPolynomials *> &polynomials) {
+        if (polynomials.size() != n) throw Panic(SC_ERR_BAD_ARG, "one polynomial per instance of the handle");
+        std::vector<std::unique_ptr<ListOfProductsOfPolynomials::Desc>> keep;
+        std::vector<sc_poly_desc> descs;
+        for (const ListOfProductsOfPolynomials *p : polynomials) {
+            if (!p) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            keep.push_back(p->desc());
+            descs.push_back(keep.back()->d);
+        }
+        check(sc_batch_prover_reset(h_, descs.data()));
+    }
+    sc_batch_prover *raw() { return h_; }
+    // n challenges, or ONE for all instances, as the library takes them
+    std::vector<Fr> challenges(const std::vector<VerifierMsg> &v_msgs) const {
+        if (v_msgs.size() != n && v_msgs.size() != 1) throw Panic(SC_ERR_BAD_ARG, "one VerifierMsg per instance, or a single one for all");
+        std::vector<Fr> r;
+        for (const VerifierMsg &m : v_msgs) r.push_back(m.randomness);
+        return r;
+    }
+
+  private:
+    sc_batch_prover *h_ = nullptr;
+    size_t n_tables_ = 0;
+};
+
 // The library keeps device memory between calls (the last prover it built, the work areas of evaluate / fix_variables, the GKR
 // scratch) so that one-shot calls cost what kept state costs; this returns all of it.
 inline void release_caches() { check(sc_release_caches()); }
@@ -291,6 +377,34 @@ struct IPForMLSumcheck {
         m.evaluations.resize(state.max_multiplicands + 1);
         check(sc_prove_round(state.raw(), v_msg ? v_msg->randomness.l : nullptr, m.evaluations[0].l));
         return m;
+    }
+    // n x prover_init of ONE structure behind one handle (sc_batch_prover_init); the tables are copied
+    static BatchProverState prover_init_batch(const std::vector<const ListOfProductsOfPolynomials *> &polynomials) {
+        std::vector<std::unique_ptr<ListOfProductsOfPolynomials::Desc>> keep;
+        std::vector<sc_poly_desc> descs;
+        for (const ListOfProductsOfPolynomials *p : polynomials) {
+            if (!p) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            keep.push_back(p->desc());
+            descs.push_back(keep.back()->d);
+        }
+        sc_batch_prover *h = nullptr;
+        check(sc_batch_prover_init(descs.data(), (uint32_t)descs.size(), &h));
+        return BatchProverState(h, descs.size(), *polynomials[0]);
+    }
+    // n x prove_round in one library call (sc_batch_prove_round): v_msgs empty on the first call, then one VerifierMsg per instance or ONE
+    // for all instances; message i is bit for bit prove_round's
+    static std::vector<ProverMsg> prove_round_batch(BatchProverState &state, const std::vector<VerifierMsg> &v_msgs) {
+        const size_t Dg = state.max_multiplicands + 1;
+        std::vector<Fr> flat(state.n * Dg);
+        if (v_msgs.empty()) {
+            check(sc_batch_prove_round(state.raw(), nullptr, 0, flat[0].l));
+        } else {
+            const std::vector<Fr> r = state.challenges(v_msgs);
+            check(sc_batch_prove_round(state.raw(), r[0].l, v_msgs.size() == 1 && state.n != 1 ? 1u : 0u, flat[0].l));
+        }
+        std::vector<ProverMsg> out(state.n);
+        for (size_t i = 0; i < state.n; ++i) out[i].evaluations.assign(flat.begin() + i * Dg, flat.begin() + (i + 1) * Dg);
+        return out;
     }
     static VerifierMsg sample_round(Blake2b512Rng &rng) { return VerifierMsg{rng.rand_fr()}; } // verifier.rs:128-131
 };

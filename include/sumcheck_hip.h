@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch and sc_gkr_subclaim_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch and the sc_batch_prover_* family (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -266,6 +266,52 @@ SC_API int sc_ml_prove_handle(sc_prover *p, sc_rng *rng_or_null, uint64_t *out_p
  * and sc_last_error() names the instance and the field.  Policy "batch" selects the plan.  Work areas are cached (sc_release_caches). */
 SC_API int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *const *rngs_or_null, uint64_t *out_proofs,
                              uint64_t *out_randomness_or_null);
+/* ---- n x IPForMLSumcheck::{prover_init, prove_round} (prover.rs:49-153) behind one handle: the interactive half of the batch ------
+ * sc_ml_prove_batch keeps the crate's Blake2b transcript inside the call.  A caller with a transcript of its own -- the reference takes
+ * fs_rng: &mut impl FeedableRNG: one transcript over all instances, one shared challenge per round, a hash on many threads -- proves n
+ * small instances round by round here instead of looping sc_prove_round over n handles: the reference's caller would write
+ * states.par_iter_mut().zip(msgs).map(prove_round).  Within sc_ml_prove_batch's envelope (every instance fits ONE block's LDS) a round of
+ * the whole batch is one upload of the challenges, ONE kernel launch (a block per instance), one copy back and one synchronisation; every
+ * challenge is known before the launch, so nothing on the GPU ever waits for the host (policies "pipeline" and "wait_spins" and the
+ * device's tail slot play no part).  The calls are TOTAL over shapes: beyond the envelope, or with policy "batch" = 0 when the handle is
+ * built, the handle holds n ordinary provers (device-side waits off, no resident kernel) and a round is a loop of sc_prove_round, with the
+ * same bits; with policy "batch" = 1 or 2 the kernel runs for every n that fits.
+ * THREADING: one handle, one host thread at a time; distinct handles are independent (the library serialises its HIP calls per device). */
+typedef struct sc_batch_prover sc_batch_prover; /* n x ProverState (prover.rs:19-33) of ONE structure */
+/* SC_API_EXT is SC_API.  It marks the entry points whose prototypes name an opaque type younger than the type table of the header-vs-shim
+ * scanner in tests/test_rust_shim.py (which reads `SC_API` prototypes and cannot map sc_batch_prover); tests/test_batch_rounds_host.py
+ * compares these prototypes with the shim's declarations instead, with the same rules. */
+#define SC_API_EXT SC_API
+/* descs: n complete descriptors of the SAME structure -- sc_ml_prove_batch's rule, check and error text ("instance %u: ...").  Everything
+ * the host can check is checked before any HIP call, so an argument error is the same with or without a GPU: num_vars == 0 is
+ * SC_ERR_CONSTANT_POLY, n == 0 is SC_ERR_BAD_ARG (a handle over nothing is not a handle), a non-canonical coefficient SC_ERR_BAD_ARG.
+ * Tables are host or device memory per descs[0].flags and are COPIED, as sc_prover_init copies (device tables after a device-wide
+ * synchronise): nothing of the caller's is read after the call returns.  SC_TABLES_BORROW, SC_TABLES_STREAM and SC_NO_DEVICE_POLLING are
+ * ignored.  Device memory: 96 bytes per table entry (every binding depth keeps its own region, so the round-0 tables survive the proof)
+ * plus, for host tables, the 32-byte staging copy a reset with new tables reuses. */
+SC_API_EXT int sc_batch_prover_init(const sc_poly_desc *descs, uint32_t n, sc_batch_prover **out);
+/* One prove_round (prover.rs:74-153) for every instance.  r_or_null: NULL exactly on the first call; afterwards the previous round's
+ * challenges, n x 4 limbs instance-major, or -- r_shared != 0 -- 4 limbs for all instances.  out_evals: n x (max_multiplicands+1) x 4
+ * limbs, instance-major.  Instance i's message is bit for bit what sc_prove_round on a handle over descs[i] returns for the same
+ * challenges.  Misuse maps to sc_prove_round's status codes: SC_ERR_FIRST_ROUND_HAS_MSG, SC_ERR_MISSING_MSG, SC_ERR_NOT_ACTIVE after
+ * num_vars rounds; a non-canonical challenge is SC_ERR_BAD_ARG "instance %u: challenge is not canonical".  An argument error leaves
+ * the handle exactly where it was. */
+SC_API_EXT int sc_batch_prove_round(sc_batch_prover *bp, const uint64_t *r_or_null, uint32_t r_shared, uint64_t *out_evals);
+/* MLSumcheck::prove_as_subprotocol pushes the final challenge without binding it (mod.rs:65-67): r as for sc_batch_prove_round. */
+SC_API_EXT int sc_batch_prover_push_randomness(sc_batch_prover *bp, const uint64_t *r, uint32_t r_shared);
+/* sc_prover_state for ONE instance of the batch.  randomness: up to num_vars x 4 limbs (may be NULL); tables_out: U x 2^(num_vars - bound)
+ * x 4 limbs of canonical elements, bound = max(round-1, 0) (may be NULL); *round, *n_randomness may be NULL. */
+SC_API_EXT int sc_batch_prover_state(sc_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness, uint64_t *tables_out,
+                                 uint32_t *round);
+/* sc_prover_bind_final for the batch: after the last round, bind the last variable of every instance's tables with its challenge (r as
+ * for sc_batch_prove_round).  out_table_values: n x U x 4 limbs on the HOST -- the table evaluations at each instance's point, bit for bit
+ * the out_table_values of sc_poly_evaluate there.  Afterwards the handle is exhausted until it is reset. */
+SC_API_EXT int sc_batch_prover_bind_final(sc_batch_prover *bp, const uint64_t *r, uint32_t r_shared, uint64_t *out_table_values);
+/* Rewind the handle to round 0 without reallocating.  descs_or_null == NULL: the tables copied by init (or by the last reset) again --
+ * the handle keeps them; otherwise n new descriptors of the handle's structure, copied in as by init (new tables, new coefficients; a
+ * handle built over device tables takes device tables). */
+SC_API_EXT int sc_batch_prover_reset(sc_batch_prover *bp, const sc_poly_desc *descs_or_null);
+SC_API_EXT void sc_batch_prover_free(sc_batch_prover *bp);
 
 /* ---- verifier (reference src/ml_sumcheck/protocol/verifier.rs:90-251) -- host side, O(nv*deg) - */
 /* interpolate_uni_poly (verifier.rs:139-251, including its three tiers: i64 ratios for len <= 20, i128 for len <= 33, field
@@ -430,7 +476,7 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "wait_spins" (2^22)      bound of a device-side wait for a challenge, in polls (tests shorten it to exercise the give-up path)
  *   "staged_init" (1)        0: sc_prover_init over HOST tables copies them whole before round 1 instead of in chunks with round 1 computed
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
- *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
+ *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, sc_batch_prover_init: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
  *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);

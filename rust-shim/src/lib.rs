@@ -5,6 +5,7 @@
 //! |---|---|
 //! | [`prover_init`], [`prove_round`]            | `IPForMLSumcheck::{prover_init, prove_round}` `src/ml_sumcheck/protocol/prover.rs:49,74` |
 //! | [`prove`], [`prove_as_subprotocol`]         | `MLSumcheck::{prove, prove_as_subprotocol}` `src/ml_sumcheck/mod.rs:42,50` |
+//! | [`prover_init_batch`], [`prove_round_batch`] | (new) `states.par_iter_mut().zip(msgs).map(prove_round)`: one round of many small provers in one call, the caller's transcript |
 //! | [`prove_batch`]                            | (new) `polys.par_iter().map(MLSumcheck::prove)`: many small instances of one structure in one call |
 //! | [`evaluate`]                                | `ListOfProductsOfPolynomials::evaluate` `src/ml_sumcheck/data_structures.rs:99` |
 //! | [`initialize_phase_one`], [`initialize_phase_two`] | `src/gkr_round_sumcheck/mod.rs:22,57` |
@@ -58,6 +59,10 @@ pub struct sc_rng {
 }
 #[repr(C)]
 pub struct sc_comm {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct sc_batch_prover {
     _private: [u8; 0],
 }
 
@@ -349,6 +354,99 @@ pub fn prove_batch<F: Limbs4>(polynomials: &[ListOfProductsOfPolynomials<F>]) ->
     let mut proofs = vec![[0u64; 4]; polynomials.len() * nv.max(1) * d];
     check(unsafe { sc_ml_prove_batch(descs.as_ptr(), descs.len() as u32, core::ptr::null(), proofs.as_mut_ptr() as *mut u64, core::ptr::null_mut()) });
     proofs.chunks(nv.max(1) * d).map(|one| one.chunks(d).take(nv).map(prover_msg).collect()).collect()
+}
+
+// The batched interactive rounds (`sc_batch_prover_*`): private declarations behind the safe wrappers below.
+extern "C" {
+    fn sc_batch_prover_init(descs: *const sc_poly_desc, n: u32, out: *mut *mut sc_batch_prover) -> c_int;
+    fn sc_batch_prove_round(bp: *mut sc_batch_prover, r_or_null: *const u64, r_shared: u32, out_evals: *mut u64) -> c_int;
+    fn sc_batch_prover_push_randomness(bp: *mut sc_batch_prover, r: *const u64, r_shared: u32) -> c_int;
+    fn sc_batch_prover_state(bp: *mut sc_batch_prover, instance: u32, randomness: *mut u64, n_randomness: *mut u32, tables_out: *mut u64,
+                             round: *mut u32) -> c_int;
+    fn sc_batch_prover_bind_final(bp: *mut sc_batch_prover, r: *const u64, r_shared: u32, out_table_values: *mut u64) -> c_int;
+    fn sc_batch_prover_reset(bp: *mut sc_batch_prover, descs_or_null: *const sc_poly_desc) -> c_int;
+    fn sc_batch_prover_free(bp: *mut sc_batch_prover);
+}
+
+/// n x `ProverState` of ONE structure behind one `sc_batch_prover` handle ([`prover_init_batch`]).
+pub struct HipBatchProverState<F: Limbs4> {
+    handle: *mut sc_batch_prover,
+    pub n: usize,
+    pub num_vars: usize,
+    pub max_multiplicands: usize,
+    n_tables: usize,
+    _f: core::marker::PhantomData<F>,
+}
+impl<F: Limbs4> Drop for HipBatchProverState<F> {
+    fn drop(&mut self) {
+        unsafe { sc_batch_prover_free(self.handle) }
+    }
+}
+impl<F: Limbs4> HipBatchProverState<F> {
+    pub fn round(&self) -> usize {
+        let mut r = 0u32;
+        check(unsafe { sc_batch_prover_state(self.handle, 0, core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(), &mut r) });
+        r as usize
+    }
+    /// the challenges instance `i` has received so far
+    pub fn randomness(&self, i: usize) -> Vec<F> {
+        let mut rand = vec![[0u64; 4]; self.num_vars + 1];
+        let mut n_rand = 0u32;
+        check(unsafe { sc_batch_prover_state(self.handle, i as u32, rand.as_mut_ptr() as *mut u64, &mut n_rand, core::ptr::null_mut(), core::ptr::null_mut()) });
+        rand[..n_rand as usize].iter().map(|l| F::from_limbs(*l)).collect()
+    }
+    /// `prove_as_subprotocol`'s final push without a bind (`mod.rs:65-67`): one challenge per instance
+    pub fn push_randomness(&mut self, v_msgs: &[VerifierMsg<F>]) {
+        assert_eq!(v_msgs.len(), self.n, "one VerifierMsg per instance");
+        let r: Vec<[u64; 4]> = v_msgs.iter().map(|m| m.randomness.to_limbs()).collect();
+        check(unsafe { sc_batch_prover_push_randomness(self.handle, r.as_ptr() as *const u64, 0) });
+    }
+    /// bind the last variable after the last round: per instance the table evaluations at its point; exhausts the handle until [`Self::reset`]
+    pub fn bind_final(&mut self, v_msgs: &[VerifierMsg<F>]) -> Vec<Vec<F>> {
+        assert_eq!(v_msgs.len(), self.n, "one VerifierMsg per instance");
+        let r: Vec<[u64; 4]> = v_msgs.iter().map(|m| m.randomness.to_limbs()).collect();
+        let mut out = vec![[0u64; 4]; self.n * self.n_tables.max(1)];
+        check(unsafe { sc_batch_prover_bind_final(self.handle, r.as_ptr() as *const u64, 0, out.as_mut_ptr() as *mut u64) });
+        out.chunks(self.n_tables.max(1)).map(|t| t.iter().take(self.n_tables).map(|l| F::from_limbs(*l)).collect()).collect()
+    }
+    /// rewind to round 0 over the tables the handle holds (no allocation, no copy)
+    pub fn reset(&mut self) {
+        check(unsafe { sc_batch_prover_reset(self.handle, core::ptr::null()) });
+    }
+}
+
+/// n x `IPForMLSumcheck::prover_init` for polynomials of ONE structure behind one handle (`sc_batch_prover_init`); the tables are copied.
+pub fn prover_init_batch<F: Limbs4>(polynomials: &[ListOfProductsOfPolynomials<F>]) -> HipBatchProverState<F> {
+    assert!(!polynomials.is_empty(), "a batch handle holds at least one instance");
+    let flats: Vec<Flattened> = polynomials.iter().map(flatten).collect();
+    let descs: Vec<sc_poly_desc> = flats.iter().zip(polynomials).map(|(f, p)| f.desc(p.num_variables, p.max_multiplicands, 0)).collect();
+    let mut handle = core::ptr::null_mut();
+    check(unsafe { sc_batch_prover_init(descs.as_ptr(), descs.len() as u32, &mut handle) });
+    HipBatchProverState {
+        handle,
+        n: polynomials.len(),
+        num_vars: polynomials[0].num_variables,
+        max_multiplicands: polynomials[0].max_multiplicands,
+        n_tables: polynomials[0].flattened_ml_extensions.len(),
+        _f: core::marker::PhantomData,
+    }
+}
+
+/// `states.iter_mut().zip(v_msgs).map(|(s, m)| IPForMLSumcheck::prove_round(s, m))` in one FFI call (`sc_batch_prove_round`): `None` on
+/// the first call, then one `VerifierMsg` per instance -- from whatever transcript(s) the caller keeps.  Message i is bit for bit
+/// [`prove_round`]'s for instance i.
+pub fn prove_round_batch<F: Limbs4>(state: &mut HipBatchProverState<F>, v_msgs: Option<&[VerifierMsg<F>]>) -> Vec<ProverMsg<F>> {
+    let d = state.max_multiplicands + 1;
+    let mut out = vec![[0u64; 4]; state.n * d];
+    match v_msgs {
+        None => check(unsafe { sc_batch_prove_round(state.handle, core::ptr::null(), 0, out.as_mut_ptr() as *mut u64) }),
+        Some(ms) => {
+            assert_eq!(ms.len(), state.n, "one VerifierMsg per instance");
+            let r: Vec<[u64; 4]> = ms.iter().map(|m| m.randomness.to_limbs()).collect();
+            check(unsafe { sc_batch_prove_round(state.handle, r.as_ptr() as *const u64, 0, out.as_mut_ptr() as *mut u64) })
+        }
+    }
+    out.chunks(d).map(prover_msg).collect()
 }
 
 /// The library keeps device memory between calls so that one-shot use costs what a kept prover costs: the last prover it built (up to

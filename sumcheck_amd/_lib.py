@@ -125,6 +125,17 @@ SIGNATURES = {
     "sc_bench_modmul": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), u64p]),
 }
 
+# ... and every symbol it declares with SC_API_EXT (the same export; prototypes over opaque types added within ABI version 5)
+SIGNATURES_EXT = {
+    "sc_batch_prover_init": (C.c_int, [C.POINTER(PolyDesc), C.c_uint32, C.POINTER(_V)]),
+    "sc_batch_prove_round": (C.c_int, [_V, _V, C.c_uint32, _V]),
+    "sc_batch_prover_push_randomness": (C.c_int, [_V, _V, C.c_uint32]),
+    "sc_batch_prover_state": (C.c_int, [_V, C.c_uint32, _V, u32p, _V, u32p]),
+    "sc_batch_prover_bind_final": (C.c_int, [_V, _V, C.c_uint32, _V]),
+    "sc_batch_prover_reset": (C.c_int, [_V, C.POINTER(PolyDesc)]),
+    "sc_batch_prover_free": (None, [_V]),
+}
+
 ABI_VERSION = 5  # SC_ABI_VERSION of include/sumcheck_hip.h as declared above
 _lib = None
 
@@ -162,7 +173,7 @@ def lib():
         # An A/B run against an OLDER build (tools/ab.sh) sets SC_AB_ALLOW_MISSING=1 next to SC_LIB_PATH: entry points that build lacks
         # become stubs that raise when called.  Without it every declared symbol must resolve, whatever file SC_LIB_PATH names.
         allow_missing = os.environ.get("SC_AB_ALLOW_MISSING") == "1"
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()):
             try:
                 fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:

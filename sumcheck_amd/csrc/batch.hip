@@ -148,17 +148,9 @@ int area_reserve(BatchArea &a, size_t d_bytes, size_t up_bytes) {
     return SC_OK;
 }
 
-// the structure every instance shares, as the kernels take it (prover_build's records: abi.hip)
-struct SharedMeta {
-    uint32_t nv = 0, U = 0, K = 0, D = 0, max_mult = 0;
-    int n_combos = 0;
-    bool fits_args = false;
-    scd::ComboMeta combo;
-    scd::FinMeta fin;
-    std::vector<uint32_t> M;                    // per product
-    std::vector<const std::vector<sch::Fr> *> unit; // per product: its node -> message matrix for a coefficient of one
-    uint32_t w_elems = 0;                       // matrices of one instance, both copies of every product
-};
+} // namespace
+
+// (the structure every instance shares: SharedMeta, prover_internal.hpp -- also what batch_rounds.hip builds its launches from)
 void build_shared(const sc_poly_desc *d, SharedMeta &s) {
     s.nv = d->num_vars;
     s.U = d->n_tables;
@@ -238,6 +230,7 @@ void instance_weights(const SharedMeta &s, const uint64_t *coeffs, sch::Fr *out)
     }
 }
 
+namespace {
 // The smallest n the batched kernel takes under policy "batch" = 1 (profiles/batch_bench.json).  Measured per call: about
 // 70-150 us whatever n (wait for the tables' producers, one upload, the launch, num_vars round trips, the drain of the stream) plus
 // 5-10 us per instance, against 65-130 us per instance for the serial plan -- so from n = 2 on the kernel wins everywhere (3x at n = 4),
@@ -517,6 +510,8 @@ int run_batched(const BatchJob &job, sc_rng *const *rngs_or_null, uint64_t *out_
     return SC_OK;
 }
 
+} // namespace
+
 const char *first_structure_difference(const sc_poly_desc &a, const sc_poly_desc &b) {
     if (a.num_vars != b.num_vars) return "num_vars";
     if (a.max_multiplicands != b.max_multiplicands) return "max_multiplicands";
@@ -530,7 +525,19 @@ const char *first_structure_difference(const sc_poly_desc &a, const sc_poly_desc
     return nullptr;
 }
 
-} // namespace
+int batch_check_desc(const sc_poly_desc *descs, uint32_t i) {
+    int rc = validate_desc(&descs[i]); // prover_init panics on a constant before anything is proved (prover.rs:50-52)
+    if (rc) {
+        const std::string why = sc_last_error();
+        return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+    }
+    return SC_OK;
+}
+int batch_check_structure(const sc_poly_desc *descs, uint32_t i) {
+    if (const char *field = i ? first_structure_difference(descs[0], descs[i]) : nullptr)
+        return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u differs from instance 0 in %s: a batch has one structure", i, field);
+    return SC_OK;
+}
 
 void sc_internal_release_batch_cache() {
     std::lock_guard<std::mutex> lk(g_area.mu);
@@ -541,14 +548,9 @@ extern "C" int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *
     if (n == 0) return SC_OK;
     if (!descs || !out_proofs) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
     for (uint32_t i = 0; i < n; ++i) {
-        int rc = validate_desc(&descs[i]); // prover_init panics on a constant before anything is proved (prover.rs:50-52)
-        if (rc) {
-            const std::string why = sc_last_error();
-            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-        }
+        if (int rc = batch_check_desc(descs, i)) return rc;
         if (rngs_or_null && !rngs_or_null[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null rng", i);
-        if (const char *field = i ? first_structure_difference(descs[0], descs[i]) : nullptr)
-            return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u differs from instance 0 in %s: a batch has one structure", i, field);
+        if (int rc = batch_check_structure(descs, i)) return rc;
     }
     if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
     static const bool trace = std::getenv("SC_HOST_TRACE") != nullptr;

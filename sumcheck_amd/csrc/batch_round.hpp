@@ -2,7 +2,8 @@
 // runs a sumcheck round out of them -- the poll of the instance's own mailbox slot (the poll is the fetch), the bind in place, the sums
 // per (product, node) combination, the block reduction, finalize_message from the instance's matrices and the publication as
 // self-validating words (limb | tag << 32).  Used by k_batch_proofs (kernels_batch.hip: sc_ml_prove_batch) and by k_batch_gkr
-// (kernels_batch_gkr.hip: sc_gkr_prove_batch), which runs it twice per instance over tables it has built in LDS itself.
+// (kernels_batch_gkr.hip: sc_gkr_prove_batch), which runs it twice per instance over tables it has built in LDS itself; k_batch_round
+// (kernels_batch_rounds.hip: sc_batch_prove_round) runs ONE round of it per launch and uses neither the poll nor the tagged words.
 #pragma once
 #include "finalize_device.hpp"
 #include "kernel_common.hpp"
@@ -139,12 +140,11 @@ __device__ __forceinline__ Fe bt_combo_sum(const bool live, const uint32_t q, co
     return acc;
 }
 
-// the round's sums over the E entries still held, its message from the instance's matrices, and the message out under `tag`.
+// the round's sums over the E entries still held and its message from the instance's matrices, left in B.msg_lds behind a barrier.
 // worst_p: a bound on the magnitude of one product in units of p (round j of tables loaded canonical: entries in (-j p, p), products of
 // two or more within (1 + j^2 / 70) p -- j + 1 covers both)
 template <int kSlots, typename ProdFn>
-__device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kSlots> &ln, const ProdFn &prod_of, const uint32_t E, const uint32_t tag, const uint32_t worst_p) {
-    const int tid = threadIdx.x;
+__device__ __forceinline__ void bt_sum_message(const BtBlock &B, const BtLane<kSlots> &ln, const ProdFn &prod_of, const uint32_t E, const uint32_t worst_p) {
     // ---- sums: lane (combination, q) multiplies out the combination's pairs q, q + L, ... ----------------------------------------------
     const uint32_t pairs_here = E / 2;
     const int32_t nv = ln.my_nv;
@@ -167,9 +167,15 @@ __device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kS
     });
     if (ln.combo_live && ln.my_q == 0) fr_store(B.fin_lds + 2 * (B.prod_index_sh[ln.my_combo] * B.D + (int)B.combo_sh[ln.my_combo].t), fe_to_fr(acc));
     __syncthreads();
-    // ---- the message, from the instance's own matrices, into LDS; then out as tagged words: every 8-byte word validates itself --------
+    // ---- the message, from the instance's own matrices, into LDS -----------------------------------------------------------------------
     finalize_message<kTsBlock>(prod_of, B.Wm, B.K, B.D, B.fin_lds, B.msg_lds, (uint64_t *)nullptr, (uint4 *)nullptr, (uint32_t *)nullptr, 0u, 1, (const Fr *)nullptr);
     __syncthreads();
+}
+// ... and the message out under `tag`, as tagged words: every 8-byte word validates itself (the kernels whose host polls for it)
+template <int kSlots, typename ProdFn>
+__device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kSlots> &ln, const ProdFn &prod_of, const uint32_t E, const uint32_t tag, const uint32_t worst_p) {
+    const int tid = threadIdx.x;
+    bt_sum_message<kSlots>(B, ln, prod_of, E, worst_p);
     const uint32_t msg_words = (uint32_t)B.D * 8u;
     if ((uint32_t)tid < msg_words) {
         const uint32_t limb = reinterpret_cast<const uint32_t *>(B.msg_lds)[tid];

@@ -301,6 +301,32 @@ bool eval_batch_shape_fits(uint32_t nv);
 hipError_t launch_batch_eval(const EvalBatchArgs &args, uint32_t blocks, hipStream_t stream);
 bool gkr_eval_batch_shape_fits(uint32_t dim, uint64_t nnz_max); // sc_gkr_prove_batch's envelope: dim <= kGkrBatchMaxDim, nnz <= kGkrBatchMaxNnzPerCell x 2^dim
 hipError_t launch_batch_gkr_eval(const GkrBatchInst *inst, uint32_t n, uint32_t dim, uint4 *out, uint32_t out_stride, hipStream_t stream);
+// Batched interactive rounds (kernels_batch_rounds.hip): sc_batch_prove_round.  ONE plain launch per round for the whole batch, one block
+// per instance, k_batch_proofs' round body (batch_round.hpp) between a load from and a store to a device work area -- every challenge is
+// known before the launch, so nothing here waits for the host or for another block.  The work area holds every instance's tables as
+// 48-byte LDS slots (kBtEnt words, copied verbatim: every magnitude is k_batch_proofs'), table u of instance i at slot
+// (i * n_tables + u) * 2 * 2^nv, and inside that region the table bound b times at batch_rounds_off(nv, b): the round-0 tables are never
+// overwritten (a reset to the same tables rewinds a counter), and a round never writes what it reads.
+constexpr size_t kBatchRoundSlotBytes = 48; // (kBtEnt words: batch_round.hpp)
+constexpr uint64_t batch_rounds_off(uint32_t nv, uint32_t bound) { return bound ? (2ULL << nv) - ((1ULL << nv) >> (bound - 1)) : 0; }
+struct BatchRoundArgs {
+    int32_t *work;              // device: n x n_tables x 2 x 2^nv slots of kBtEnt words
+    const uint4 *Wm;            // device: n x w_stride elements, as in BatchArgs
+    uint32_t w_stride;
+    const uint4 *chal;          // device: the challenges behind the previous messages, n elements (ONE when chal_shared); not read in round 0
+    uint32_t chal_shared;
+    uint4 *out;                 // device: n x D elements, the round's messages
+    uint32_t n, n_tables, nv, round; // round: 0-based; round j > 0 binds the tables bound j - 1 times and stores them bound j times
+    int n_combos, K, D;
+    uint32_t fin_bytes;         // (filled in by the launcher: LDS layout -- finalize scratch | message | tables)
+};
+hipError_t launch_batch_round(BatchRoundArgs args, const ComboMeta &meta, const FinMeta &fin, hipStream_t stream); // shapes of batch_shape_fits
+// canonical tables (tables[i * n_tables + u]: 2^nv entries, reference layout) -> the work area's round-0 slots
+hipError_t launch_batch_rounds_load(const uint4 *const *tables, uint32_t n, uint32_t n_tables, uint32_t nv, int32_t *work, hipStream_t stream);
+// instances [first, first + count): the tables bound `bound` times -> canonical elements, out[(i - first) * n_tables + u][entry]; with
+// chal (first + count elements, or ONE when chal_shared) every pair of entries is bound once more on the way out (bind_final)
+hipError_t launch_batch_rounds_export(const int32_t *work, uint32_t first, uint32_t count, uint32_t n_tables, uint32_t nv, uint32_t bound, const uint4 *chal_or_null,
+                                      uint32_t chal_shared, uint4 *out, hipStream_t stream);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -363,6 +389,8 @@ enum Plan {
     kPlanGkrListForm,         // ... sort + merge + scatter
     kPlanGkrCoeffFromBound,   // phase two's coefficient f2(u) from phase one's bound table
     kPlanGkrSharded,          // sc_gkr_prove_sharded
+    kPlanBatchRoundsOneBlock, // sc_batch_prove_round: k_batch_round, one block per instance, one launch per round for the whole batch
+    kPlanBatchRoundsSerial,   // ... a loop of sc_prove_round over n handles inside the batch handle (shapes beyond the envelope, policy "batch" = 0)
     kPlanFoldMulti,           // sc_poly_evaluate / sc_fix_variables (k_fold_multi)
     kPlanBatchEvalOneBlock,   // sc_poly_evaluate_batch: k_batch_eval, one block per (instance, table), one launch for the whole batch
     kPlanBatchEvalSerial,     // ... instance after instance through sc_poly_evaluate (num_vars beyond the envelope, policy "batch" = 0, work areas taken)

@@ -248,6 +248,23 @@ bool tail_slot_acquire(sc_prover *p, bool resident); // the device's one tail sl
 void tail_slot_release(sc_prover *p);
 // ---- batch.hip ----
 void sc_internal_release_batch_cache(); // sc_release_caches: sc_ml_prove_batch's work areas
+// the structure every instance shares, as the kernels take it (prover_build's records: abi.hip)
+struct SharedMeta {
+    uint32_t nv = 0, U = 0, K = 0, D = 0, max_mult = 0;
+    int n_combos = 0;
+    bool fits_args = false;
+    scd::ComboMeta combo;
+    scd::FinMeta fin;
+    std::vector<uint32_t> M;                    // per product
+    std::vector<const std::vector<sch::Fr> *> unit; // per product: its node -> message matrix for a coefficient of one
+    uint32_t w_elems = 0;                       // matrices of one instance, both copies of every product
+};
+void build_shared(const sc_poly_desc *d, SharedMeta &s);
+const std::vector<sch::Fr> *unit_matrix(uint32_t M, uint32_t D);                          // a product's node -> message matrix for a coefficient of one (cached per process)
+void instance_weights(const SharedMeta &s, const uint64_t *coeffs, sch::Fr *out); // s.w_elems elements: c_k W_k and c_k 2^(5(M-1)) W_k, product after product
+const char *first_structure_difference(const sc_poly_desc &a, const sc_poly_desc &b);    // the first field in which two descriptors of a batch differ, or null
+int batch_check_desc(const sc_poly_desc *descs, uint32_t i);      // validate_desc on instance i, its error text behind "instance %u: "
+int batch_check_structure(const sc_poly_desc *descs, uint32_t i); // SC_ERR_BAD_ARG "instance %u differs from instance 0 in %s: a batch has one structure"
 // ---- comm.hip ----
 struct NcclApi {
     void *lib = nullptr;

@@ -287,6 +287,99 @@ class ProverState:
             pass
 
 
+def _batch_descs(polys: Sequence[ListOfProductsOfPolynomials]):
+    """n descriptors back to back, and what keeps their arrays alive"""
+    n = len(polys)
+    descs = (PolyDesc * max(n, 1))()
+    keep = []
+    for i, poly in enumerate(polys):
+        d, k = poly._desc(False)
+        C.memmove(C.byref(descs, i * C.sizeof(PolyDesc)), C.byref(d), C.sizeof(PolyDesc))
+        keep.append(k)
+    return descs, keep
+
+
+def _batch_challenges(n: int, v_msgs):
+    """one VerifierMsg (shared) or n of them -> (array, r_shared)"""
+    if isinstance(v_msgs, VerifierMsg):
+        return np.ascontiguousarray(_np64(v_msgs.randomness).reshape(4)), 1
+    if len(v_msgs) != n:
+        raise ValueError("one VerifierMsg per instance, or a single one for all")
+    return np.ascontiguousarray(np.stack([_np64(m.randomness).reshape(4) for m in v_msgs])), 0
+
+
+class BatchProverState:
+    """n x ProverState (prover.rs:19-33) of ONE structure behind an sc_batch_prover handle: IPForMLSumcheck.prover_init_batch /
+    prove_round_batch.  The caller owns the transcript(s) and hands in every challenge."""
+
+    def __init__(self, handle: C.c_void_p, polys: Sequence[ListOfProductsOfPolynomials]):
+        self._h = handle
+        self.n = len(polys)
+        self.num_vars = polys[0].num_variables
+        self.max_multiplicands = polys[0].max_multiplicands
+        self._n_tables = len(polys[0].flattened_ml_extensions)
+
+    @property
+    def round(self) -> int:
+        r = C.c_uint32()
+        check(lib().sc_batch_prover_state(self._h, 0, None, None, None, C.byref(r)))
+        return r.value
+
+    def randomness(self, i: int) -> np.ndarray:
+        cnt = C.c_uint32()
+        check(lib().sc_batch_prover_state(self._h, i, None, C.byref(cnt), None, None))
+        buf = np.zeros((max(cnt.value, 1), 4), dtype=np.uint64)
+        check(lib().sc_batch_prover_state(self._h, i, _ptr(buf), None, None, None))
+        return buf[: cnt.value].copy()
+
+    def flattened_ml_extensions(self, i: int) -> List[DenseMultilinearExtension]:
+        nvars = self.num_vars - max(self.round - 1, 0)
+        buf = np.zeros((self._n_tables, 1 << nvars, 4), dtype=np.uint64)
+        check(lib().sc_batch_prover_state(self._h, i, None, None, _ptr(buf), None))
+        return [DenseMultilinearExtension(nvars, buf[u]) for u in range(self._n_tables)]
+
+    def push_randomness(self, v_msgs) -> None:
+        """prove_as_subprotocol's final push without a bind (mod.rs:65-67)"""
+        r, shared = _batch_challenges(self.n, v_msgs)
+        check(lib().sc_batch_prover_push_randomness(self._h, _ptr(r), shared))
+
+    def bind_final(self, v_msgs) -> np.ndarray:
+        """bind the last variable after the last round -> (n, U, 4): every table's evaluation at its instance's point"""
+        r, shared = _batch_challenges(self.n, v_msgs)
+        out = np.zeros((self.n, self._n_tables, 4), dtype=np.uint64)
+        check(lib().sc_batch_prover_bind_final(self._h, _ptr(r), shared, _ptr(out)))
+        return out
+
+    def reset(self, polys: Optional[Sequence[ListOfProductsOfPolynomials]] = None) -> None:
+        """rewind to round 0 without reallocating: over the tables the handle holds, or over n new polynomials of the same structure"""
+        if polys is None:
+            check(lib().sc_batch_prover_reset(self._h, None))
+            return
+        if len(polys) != self.n:
+            raise ValueError(f"the handle holds {self.n} instances")
+        descs, keep = _batch_descs(polys)
+        _sync_device_tables(polys, descs)
+        check(lib().sc_batch_prover_reset(self._h, descs))
+        del keep
+
+    def close(self):
+        if self._h:
+            lib().sc_batch_prover_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _sync_device_tables(polys, descs) -> None:
+    if polys and (descs[0].flags & SC_TABLES_ON_DEVICE):
+        import torch
+        torch.cuda.current_stream(polys[0].flattened_ml_extensions[0].evaluations.device).synchronize()  # the library works on its own stream
+
+
 class Blake2b512Rng:
     """FeedableRNG + RngCore of reference src/rng.rs"""
 
@@ -358,6 +451,28 @@ class IPForMLSumcheck:
         r = _np64(v_msg.randomness).reshape(4) if v_msg is not None else None
         check(lib().sc_prove_round(prover_state._h, _ptr(r) if r is not None else None, _ptr(out)))
         return ProverMsg(out)
+
+    @staticmethod
+    def prover_init_batch(polynomials: Sequence[ListOfProductsOfPolynomials]) -> BatchProverState:
+        """n x prover_init (prover.rs:49-69) of ONE structure behind one handle (sc_batch_prover_init); the tables are copied"""
+        descs, keep = _batch_descs(polynomials)
+        _sync_device_tables(polynomials, descs)
+        h = C.c_void_p()
+        check(lib().sc_batch_prover_init(descs, len(polynomials), C.byref(h)))
+        del keep
+        return BatchProverState(h, polynomials)
+
+    @staticmethod
+    def prove_round_batch(state: BatchProverState, v_msgs) -> List[ProverMsg]:
+        """n x prove_round (prover.rs:74-153) in one library call (sc_batch_prove_round).  v_msgs: None on the first call, then a
+        sequence of n VerifierMsg, or ONE VerifierMsg for all instances.  -> n ProverMsg, message i bit for bit prove_round's."""
+        out = np.empty((state.n, state.max_multiplicands + 1, 4), dtype=np.uint64)
+        if v_msgs is None:
+            check(lib().sc_batch_prove_round(state._h, None, 0, _ptr(out)))
+        else:
+            r, shared = _batch_challenges(state.n, v_msgs)
+            check(lib().sc_batch_prove_round(state._h, _ptr(r), shared, _ptr(out)))
+        return [ProverMsg(out[i].copy()) for i in range(state.n)]
 
     @staticmethod
     def sample_round(rng) -> VerifierMsg:
