@@ -251,3 +251,93 @@ def fold_cell_vectors(rng: random.Random):
 def product_regimes():
     """the accumulate op's terms: the ends of fe_mul's window on canonical operands -- 1 - p (limb 8 = -7597480) and p - 1 (limb 8 = 7597479)"""
     return {"1-p": limbs_of(1 - P), "p-1": limbs_of(P - 1)}
+
+
+# ---- lazy table entries: the binds as the kernels run them, and tables that reach the ends of the entries' range (DESIGN.md 4.6) ------------------
+def carry_pass(a):
+    """fe_device.hpp: fe_carry_pass -- every limb sheds its bits above 2^29 into the next one at once; limb 8 takes limb 7's carry, unreduced"""
+    assert fits_i32(a)
+    r = [a[0] & MASK] + [(a[i] & MASK) + (a[i - 1] >> W) for i in range(1, 8)] + [a[8] + (a[7] >> W)]
+    assert fits_i32(r)
+    return r
+
+
+def fe_add(a, b):
+    return [x + y for x, y in zip(a, b)]
+
+
+def fe_sub(a, b):
+    return [x - y for x, y in zip(a, b)]
+
+
+def bind_f29(lo, hi, r_std: int):
+    """load_factor.hpp's bind into the internal table format: lo + fe_mul_bind(hi - lo), one carry pass, no reduction"""
+    return carry_pass(fe_add(lo, fe_mul_bind(fe_sub(hi, lo), r_std)))
+
+
+def bind_lds(lo, hi, r_mont: int):
+    """bt_bind's and k_tail_slices' bind in LDS: lo + fe_mul_u(hi - lo, 32 r), r the challenge as stored (Montgomery form), one carry pass"""
+    return carry_pass(fe_add(lo, fe_shl5_mul_u(fe_sub(hi, lo), r_mont)))
+
+
+def fe_line(lo, hi, x: int):
+    """kernel_common.hpp: fe_line, step by step (one carry pass per step) -> (result, every intermediate handed to fe_carry_pass)"""
+    if x == 0:
+        return lo, []
+    if x == 1:
+        return hi, []
+    step = fe_sub(hi, lo)
+    if x == NODE_INF:
+        return step, []
+    seen = []
+    if x < 0:
+        cur = fe_sub(lo, step)
+        for _ in range(-1, x, -1):
+            seen.append(cur)
+            cur = fe_sub(carry_pass(cur), step)
+    else:
+        cur = fe_add(hi, step)
+        for _ in range(2, x):
+            seen.append(cur)
+            cur = fe_add(carry_pass(cur), step)
+    seen.append(cur)
+    return carry_pass(cur), seen
+
+
+# delta: above 2^230 (the upper end of a bind's term) so that the term HAS to be m delta - p, and small enough that k binds of m delta leave
+# an entry within 2^242 of -k p for every k m < 2^9 (2^240 forces the same terms; its entries pass -k p + 2^242 from k m = 4 on)
+DELTA = 1 << 232
+DELTA_WIDE = 1 << 240
+
+
+def sinking_challenges(nv: int, seed: int, delta: int = DELTA):
+    """-> (s, r): s_j in [1, 2^200) and the challenge r_j = delta / (p - s_j) mod p in STANDARD form, round j = 1..nv at index j - 1.
+    A slope of value -m s_j times r_j is m delta (mod p), and both bind forms return a term in (-p - 2^230, 2^230): so m delta - p, for
+    every 2^230 < m delta < p - 2^230.  An entry sinks by p - m delta in every bind: the lower end of (-(k + 1) p, p) after k."""
+    rng = random.Random(seed)
+    s = [rng.randrange(1, 1 << 200) for _ in range(nv)]
+    return s, [delta * pow(P - sj, -1, P) % P for sj in s]
+
+
+def sinking_table(nv: int, s, m: int, c: int):
+    """the STORED integers e(x) = c - m sum_j x_j s_j (x_j = bit j - 1 of the index: the variable round j binds), all in [0, p)"""
+    assert len(s) == nv and m >= 1 and m * sum(s) <= c < P
+    tab = [c]
+    for sj in s:
+        tab = tab + [v - m * sj for v in tab]
+    return tab
+
+
+def selector_table(nv: int, s, sel: int, m: int, c: int, flip: bool = False):
+    """a sinking table (in the other variables) on the half x_sel = 0, the constant p - 1 on the half x_sel = 1 (sel counts from 0: the
+    variable round sel + 1 binds): after sel binds every pair is (an entry at -sel p, p - 1).  flip: the halves the other way round"""
+    assert 0 <= sel < nv
+    half = sinking_table(nv - 1, list(s[:sel]) + list(s[sel + 1:]), m, c)
+    lo_mask = (1 << sel) - 1
+    const_bit = 0 if flip else 1
+    return [P - 1 if (x >> sel) & 1 == const_bit else half[(x & lo_mask) | ((x >> (sel + 1)) << sel)] for x in range(1 << nv)]
+
+
+def to_mont(r_std: int) -> int:
+    """a standard-form value as the API takes it and the tables store it"""
+    return r_std * R256 % P

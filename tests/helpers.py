@@ -135,3 +135,68 @@ def fe_run_op(op, n, a, b=None, c=None, d=None, params=(), aux_tail=None):
 
 def fe_as_fr(out_row) -> int:
     return sum(int(np.uint32(w)) << (32 * i) for i, w in enumerate(out_row[:8]))
+
+
+# ---- tables whose lazily bound entries reach the ends of their range (tests/fe_model.py: sinking_table, selector_table), at any size --------
+def raw_limbs(v: int) -> np.ndarray:
+    """the 4 x u64 limbs of the integer v: as a table entry, the element whose STORED (Montgomery) form is v; as a challenge, to_mont's result"""
+    assert 0 <= v < (1 << 256)
+    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+
+def _sub256(a: np.ndarray, b: int) -> np.ndarray:
+    """(n, 4) u64 minus the integer b, row by row; the caller guarantees no row goes below zero"""
+    out = np.empty_like(a)
+    borrow = np.zeros(a.shape[0], dtype=np.uint64)
+    for k in range(4):
+        bk = np.uint64((b >> (64 * k)) & 0xFFFFFFFFFFFFFFFF)
+        t = a[:, k] - bk
+        out[:, k] = t - borrow
+        borrow = ((a[:, k] < bk) | (t < borrow)).astype(np.uint64)
+    assert not borrow.any(), "an entry below zero: c < m sum s_j"
+    return out
+
+
+def sinking_table_limbs(nv: int, s, m: int, c: int) -> np.ndarray:
+    """fe_model.sinking_table as the (2^nv, 4) array the API and the oracle take, by doubling: the upper half is the lower minus m s_j"""
+    assert len(s) == nv and m >= 1 and m * sum(s) <= c < (1 << 256)
+    tab = raw_limbs(c).reshape(1, 4)
+    for sj in s:
+        tab = np.concatenate([tab, _sub256(tab, m * sj)])
+    return np.ascontiguousarray(tab)
+
+
+def selector_table_limbs(nv: int, s, sel: int, m: int, c: int, flip: bool = False) -> np.ndarray:
+    """fe_model.selector_table, likewise"""
+    from tests import fe_model as fm
+    half = sinking_table_limbs(nv - 1, list(s[:sel]) + list(s[sel + 1:]), m, c).reshape(1 << (nv - 1 - sel), 1 << sel, 4)
+    out = np.empty((1 << (nv - 1 - sel), 2, 1 << sel, 4), dtype=np.uint64)
+    out[:, 1 if flip else 0] = half
+    out[:, 0 if flip else 1] = raw_limbs(fm.P - 1)
+    return np.ascontiguousarray(out.reshape(1 << nv, 4))
+
+
+def assert_entries_match(tab: np.ndarray, entry_of, seed: int = 1, samples: int = 300):
+    """the array against the big-integer formula entry_of(index) at the ends and at `samples` random indices"""
+    rng = np.random.default_rng(seed)
+    n = tab.shape[0]
+    for x in [0, 1, n // 2 - 1, n // 2, n - 2, n - 1] + [int(i) for i in rng.integers(0, n, size=samples)]:
+        got = sum(int(tab[x, k]) << (64 * k) for k in range(4))
+        assert got == entry_of(x), f"entry {x}"
+
+
+def sinking_entry(s, m: int, c: int):
+    """index -> c - m sum_j x_j s_j, the formula itself"""
+    return lambda x: c - m * sum(sj for j, sj in enumerate(s) if (x >> j) & 1)
+
+
+def selector_entry(s, sel: int, m: int, c: int, flip: bool = False):
+    from tests import fe_model as fm
+    const_bit = 0 if flip else 1
+    return lambda x: fm.P - 1 if (x >> sel) & 1 == const_bit else c - m * sum(sj for j, sj in enumerate(s) if j != sel and (x >> j) & 1)
+
+
+def mont_challenges(r_std) -> np.ndarray:
+    """standard-form challenges -> (len, 4) as the API takes them"""
+    from tests import fe_model as fm
+    return np.stack([raw_limbs(fm.to_mont(r)) for r in r_std])

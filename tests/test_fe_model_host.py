@@ -126,3 +126,153 @@ def test_accumulate_terms_are_fe_mul_extremes():
     assert fm.value(t["p-1"]) == P - 1 and t["1-p"][8] == -(fm.PH + 1)
     # 256 of either fit ONE int32 top limb, 512 do not: the rule (kernels.h: lazy_sum_needs_reduce)
     assert 256 * (fm.PH + 1) < (1 << 31) < 512 * fm.PH
+
+
+# ---- lazy table entries at the ends of their range: the model's binds on the sinking and selector tables -------------------------
+NV = 10
+SEL = 6
+FORMS = ["f29", "lds"]
+
+
+def test_carry_pass_model_keeps_the_value_and_tightens_limbs_0_to_7():
+    rng = random.Random(fm.SEED + 4)
+    bx = fm.BOX_CARRY
+    for a in fm.corners_of(bx) + fm.random_limbs(rng, 500, bx["lo"], bx["hi"], bx["top_lo"], bx["top_hi"]):
+        r = fm.carry_pass(a)
+        assert fm.value(r) == fm.value(a)
+        assert 0 <= r[0] <= fm.MASK and all(-4 <= x < fm.T29 + 4 for x in r[1:8])
+        assert r[8] - a[8] in range(-4, 4)
+
+
+def _bind(form, lo, hi, r_std):
+    return fm.bind_f29(lo, hi, r_std) if form == "f29" else fm.bind_lds(lo, hi, fm.to_mont(r_std))
+
+
+def _rounds(form, ints, r_std):
+    """the table after 0, 1, ..., len(r_std) binds, as limbs -- every difference a bind takes checked against the multipliers' boxes"""
+    tab = [fm.limbs_of(v) for v in ints]
+    out = [tab]
+    for r in r_std:
+        for i in range(len(tab) // 2):
+            d = fm.fe_sub(tab[2 * i + 1], tab[2 * i])
+            assert fm.in_box(d, fm.BOX_BIND_D) and fm.in_box(d, fm.BOX_MUL_A), "a bind's difference leaves fe_mul_bind's / fe_mul_u's box"
+        tab = [_bind(form, tab[2 * i], tab[2 * i + 1], r) for i in range(len(tab) // 2)]
+        out.append(tab)
+    return out
+
+
+def _in_line_box_limbs(e):
+    """BOX_LINE as limb ranges: what fe_line, and fe_mul as its second operand, take from a table"""
+    return fm.in_box(e, fm.BOX_LINE) and fm.in_box(e, fm.BOX_MUL_B)
+
+
+def _family(delta=fm.DELTA):
+    s, r = fm.sinking_challenges(NV, fm.SEED + 5, delta)
+    return s, r
+
+
+@pytest.mark.parametrize("delta", [fm.DELTA, fm.DELTA_WIDE], ids=["d232", "d240"])
+def test_generated_entries_and_challenges_are_canonical_and_non_zero(delta):
+    s, r = _family(delta)
+    assert all(0 < x < P for x in r) and len(set(r)) == NV
+    assert all(x * (P - sj) % P == delta for x, sj in zip(r, s))
+    for m, c in ((1, sum(s)), (1, sum(s) + 1), (7, 7 * sum(s) + 12345), (1, P - 1), (3, P - 2)):
+        t = fm.sinking_table(NV, s, m, c)
+        assert len(t) == 1 << NV and all(0 <= v < P for v in t) and (min(t) > 0 or c == m * sum(s))
+        assert t[0] == c and t[-1] == c - m * sum(s) and t[5] == c - m * (s[0] + s[2])
+        for flip in (False, True):
+            u = fm.selector_table(NV, s, SEL, m, c, flip)
+            assert len(u) == 1 << NV and all(0 <= v < P for v in u)
+            assert all(u[x] == P - 1 for x in range(1 << NV) if ((x >> SEL) & 1) != flip)
+            assert u[((1 << NV) - 1) ^ (0 if flip else 1 << SEL)] == c - m * (sum(s) - s[SEL])
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("delta", [fm.DELTA, fm.DELTA_WIDE], ids=["d232", "d240"])
+@pytest.mark.parametrize("m", [1, 7])
+def test_sinking_entries_attain_the_lower_end_after_every_bind(form, delta, m):
+    """after k binds every entry is EXACTLY its start + k (m delta - p): in [-k p, -k p + 2^242) wherever k m delta + c < 2^242 (every k for
+    delta = 2^232), never outside (-(k + 1) p, p), its limbs inside what fe_line and fe_mul take"""
+    s, r = _family(delta)
+    c = m * sum(s) + 1
+    ints = fm.sinking_table(NV, s, m, c)
+    reached = 0
+    for k, tab in enumerate(_rounds(form, ints, r)):
+        for y, e in enumerate(tab):
+            v = fm.value(e)
+            assert v == ints[y << k] + k * (m * delta - P), (k, y)
+            assert -(k + 1) * P < v < P and _in_line_box_limbs(e)
+            if k * m * delta + c < (1 << 242):
+                assert -k * P <= v < -k * P + (1 << 242), (k, y)
+        reached = k if k * m * delta + c < (1 << 242) else reached
+    assert reached == (NV if delta == fm.DELTA else (3 if m == 1 else 0))
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_a_table_that_starts_at_the_high_end_stays_below_p(form):
+    s, r = _family()
+    ints = fm.sinking_table(NV, s, 1, P - 1)
+    for k, tab in enumerate(_rounds(form, ints, r)):
+        vs = [fm.value(e) for e in tab]
+        assert max(vs) == P - 1 + k * (fm.DELTA - P) and all(-(k + 1) * P < v < P for v in vs) and all(_in_line_box_limbs(e) for e in tab)
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("flip", [False, True], ids=["up", "down"])
+def test_selector_slopes_and_the_lines_through_them(form, flip):
+    """round sel + 1 of a selector table: every slope beyond (sel + 0.5) p; fe_line at every node a fused product takes, step by step --
+    intermediates below 1.5 * 2^30 a limb, results with limbs 0..7 carry-passed and limb 8 inside fe_mul's second operand"""
+    s, r = _family()
+    ints = fm.selector_table(NV, s, SEL, 1, sum(s) + 1, flip)
+    tab = _rounds(form, ints, r[:SEL])[SEL]
+    widest = 0
+    for i in range(len(tab) // 2):
+        lo, hi = tab[2 * i], tab[2 * i + 1]
+        slope = fm.value(hi) - fm.value(lo)
+        assert (slope <= -(SEL + 0.5) * P) if flip else (slope >= (SEL + 0.5) * P)
+        assert _in_line_box_limbs(lo) and _in_line_box_limbs(hi)
+        for x in fm.LINE_NODES:
+            res, seen = fm.fe_line(lo, hi, x)
+            assert all(abs(l) < 3 << 29 for t in seen for l in t)
+            if x == fm.NODE_INF:
+                assert fm.value(res) == slope and fm.in_box(res, fm.BOX_MUL_B)
+                continue
+            assert fm.value(res) == fm.value(lo) + x * slope
+            assert all(-4 <= l < fm.T29 + 4 for l in res[:8]) and fm.in_box(res, fm.BOX_MUL_B)
+            widest = max(widest, abs(fm.value(res)))
+    # node 4 of a (sel + 1) p slope from -sel p: 22 p for sel = 6 -- beyond the +-16 p of the ENTRIES' box, which is no bound on the line
+    assert (3 * SEL + 3.9) * P < widest < (4 * SEL + 7) * P and widest < (fm.T29 + 16) // (fm.PH + 1) * P
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_the_models_binds_are_the_oracles_fix_variables_mod_p(form):
+    s, r = _family()
+    rinv = pow(fm.R256, -1, P)
+    tables = [fm.sinking_table(NV, s, 1, sum(s)), fm.sinking_table(NV, s, 5, P - 1), fm.selector_table(NV, s, SEL, 1, sum(s) + 9),
+              fm.selector_table(NV, s, 3, 2, P - 1, True)]
+    for ints in tables:
+        std = [v * rinv % P for v in ints]
+        for k, tab in enumerate(_rounds(form, ints, r)):  # (past round sel + 1 a selector table's slopes are arbitrary: the same binds)
+            want = po.dense_fix_variables(std, r[:k])
+            assert [fm.value(e) * rinv % P for e in tab] == want, k
+            assert all(-(k + 1) * P < fm.value(e) < P for e in tab)
+
+
+def test_the_array_builders_give_the_formulas_entries():
+    import numpy as np
+    from tests import helpers as H
+    s, _ = _family()
+    as_ints = lambda a: [sum(int(row[k]) << (64 * k) for k in range(4)) for row in a]
+    assert as_ints(H.sinking_table_limbs(NV, s, 3, P - 1)) == fm.sinking_table(NV, s, 3, P - 1)
+    for sel, flip in ((0, False), (SEL, True), (NV - 1, False)):
+        assert as_ints(H.selector_table_limbs(NV, s, sel, 2, 2 * sum(s), flip)) == fm.selector_table(NV, s, sel, 2, 2 * sum(s), flip)
+    nv = 18
+    s, r = fm.sinking_challenges(nv, fm.SEED + 6)
+    t = H.sinking_table_limbs(nv, s, 5, 5 * sum(s) + 77)
+    assert t.shape == (1 << nv, 4) and t.dtype == np.uint64
+    H.assert_entries_match(t, H.sinking_entry(s, 5, 5 * sum(s) + 77))
+    u = H.selector_table_limbs(nv, s, 11, 1, P - 1, True)
+    H.assert_entries_match(u, H.selector_entry(s, 11, 1, P - 1, True))
+    with pytest.raises(AssertionError):
+        H.assert_entries_match(u, H.selector_entry(s, 11, 1, P - 1, False))
+    assert H.mont_challenges(r).shape == (nv, 4) and as_ints(H.mont_challenges(r[:2])) == [x * fm.R256 % P for x in r[:2]]

@@ -122,7 +122,9 @@ def raw(v):
 @pytest.mark.parametrize("entry", [P - 1, 1, (P - 1) * fm.R256 % P], ids=["p-1", "one", "field-minus-one"])
 def test_lazy_sums_at_the_bound(shapes, entry):
     """512 pairs a block with EVERY entry at one value and every challenge p - 1: the lazy sums of batch_round.hpp at kLazySumMaxP's rule
-    (entries stored as LDS slots: the magnitudes are k_batch_proofs').  n = 2, all rounds against the oracle."""
+    (entries stored as LDS slots: the magnitudes are k_batch_proofs').  n = 2, all rounds against the oracle.
+    These cases pin ROUND 0 only: every slope of a constant table is 0, so a bind adds exactly 0 and the entries never go lazy -- later
+    rounds see the same canonical values.  Entries at the ends of their lazy range: tests/test_gpu_lazy_entries.py."""
     n, nv = 2, 10
     nt = max(max(s) for s in shapes) + 1
     polys, descs = [], []
