@@ -372,7 +372,7 @@ int prover_build(const sc_poly_desc *d, sc_prover *p) {
     bool staged = false;
     const uint64_t s0 = small_foot ? std::max<uint64_t>(n >> 1, 1) : n;
     const uint64_t s1 = small_foot ? std::max<uint64_t>(n >> 2, 1) : std::max<uint64_t>(n >> 1, 1);
-    const uint64_t per_table = (s0 + s1) * 36; // 32 B main + 4 B limb-8 array per element (internal F29 format)
+    const uint64_t per_table = (s0 + s1) * 32; // canonical and internal (F29) elements alike: 32 bytes
     HIP_TRY(hipMalloc(&p->arena, per_table * p->U));
     p->arena_bytes = per_table * p->U;
     p->tabs.resize(p->U);
@@ -385,8 +385,6 @@ int prover_build(const sc_poly_desc *d, sc_prover *p) {
         char *base = static_cast<char *>(p->arena) + per_table * u;
         t.buf[0] = reinterpret_cast<uint4 *>(base);
         t.buf[1] = reinterpret_cast<uint4 *>(base + s0 * 32);
-        t.buf_top[0] = reinterpret_cast<int32_t *>(base + (s0 + s1) * 32);
-        t.buf_top[1] = t.buf_top[0] + s0;
         if (streamed) {
             t.cur = nullptr; // nothing resident before round 2
             t.next = 0;
@@ -584,7 +582,7 @@ int prover_bind_out(sc_prover *p, const uint64_t *r, uint64_t *d_out) {
         std::memset(&tp, 0, sizeof(tp));
         for (uint32_t j = 0; j < cnt; ++j) {
             tp.src[j] = p->tabs[u0 + j].cur;
-            tp.src_top[j] = p->tabs[u0 + j].cur_top;
+            tp.src_f29[j] = p->tabs[u0 + j].cur_f29 ? 1 : 0;
             tp.dst[j] = reinterpret_cast<uint4 *>(d_out + 4 * n_out * (size_t)(u0 + j));
         }
         HIP_TRY(scd::launch_fix_multi(tp, (int)cnt, to_dev(rr), nullptr, n_out, p->stream));
@@ -629,9 +627,9 @@ extern "C" int sc_prover_state(sc_prover *p, uint64_t *randomness, uint32_t *n_r
         void *tmp = nullptr; // tables in the internal F29 format are converted to the canonical reference layout first
         for (uint32_t u = 0; u < p->U; ++u) {
             const void *src = p->tabs[u].cur;
-            if (p->tabs[u].cur_top) {
+            if (p->tabs[u].cur_f29) {
                 if (!tmp) HIP_TRY(hipMalloc(&tmp, n * 32));
-                HIP_TRY(scd::launch_f29_to_sat(p->tabs[u].cur, p->tabs[u].cur_top, static_cast<uint4 *>(tmp), n, p->stream));
+                HIP_TRY(scd::launch_f29_to_sat(p->tabs[u].cur, static_cast<uint4 *>(tmp), n, p->stream));
                 src = tmp;
             }
             HIP_TRY(hipMemcpyAsync(tables_out + 4 * n * u, src, n * 32, hipMemcpyDeviceToHost, p->stream));
@@ -734,7 +732,7 @@ extern "C" int sc_prover_reset(sc_prover *p, const uint64_t *const *tables_or_nu
                 p->host_tabs[u] = tables_or_null[u];
             }
             p->tabs[u].cur = nullptr;
-            p->tabs[u].cur_top = nullptr;
+            p->tabs[u].cur_f29 = false;
             p->tabs[u].next = 0;
         }
     } else if (p->borrow) {
@@ -744,7 +742,7 @@ extern "C" int sc_prover_reset(sc_prover *p, const uint64_t *const *tables_or_nu
                 p->origin[u] = reinterpret_cast<const uint4 *>(tables_or_null[u]);
             }
             p->tabs[u].cur = p->origin[u];
-            p->tabs[u].cur_top = nullptr;
+            p->tabs[u].cur_f29 = false;
             p->tabs[u].next = 0;
         }
     } else {
@@ -759,7 +757,7 @@ extern "C" int sc_prover_reset(sc_prover *p, const uint64_t *const *tables_or_nu
                 HIP_TRY(hipMemcpyAsync(p->tabs[u].buf[0], tables_or_null[u], n * 32, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                        p->stream));
             p->tabs[u].cur = p->tabs[u].buf[0];
-            p->tabs[u].cur_top = nullptr;
+            p->tabs[u].cur_f29 = false;
             p->tabs[u].next = 1;
         }
         if (staged) {
@@ -786,7 +784,7 @@ extern "C" int sc_prover_reset(sc_prover *p, const uint64_t *const *tables_or_nu
 //                                   (descriptor's matrix) x table(r_last); nothing visits the host.  The next reset restores the matrices.
 hipStream_t sc_internal_prover_stream(sc_prover *p) { return p->stream; }
 const void *sc_internal_bound_table(sc_prover *p, uint32_t u) {
-    if (!p || u >= p->U || p->round != p->nv || p->exhausted || p->tabs[u].cur_top || p->res.active) return nullptr;
+    if (!p || u >= p->U || p->round != p->nv || p->exhausted || p->tabs[u].cur_f29 || p->res.active) return nullptr;
     return p->tabs[u].cur;
 }
 int sc_internal_scale_by_bound_table(sc_prover *p, const void *table, const sch::Fr &r_last) {

@@ -35,6 +35,7 @@
 #include <utility>
 #include "fr_device.hpp"
 #include "kernels.h"
+#include "f29_pack.hpp"
 
 namespace scd {
 
@@ -49,8 +50,7 @@ constexpr int32_t kFeMask = 0x1fffffff;
 
 // p in radix 2^29
 __device__ __forceinline__ constexpr int32_t fe_p_limb(int i) {
-    return i == 0 ? 0x00000001 : i == 1 ? 0x1ffffff8 : i == 2 ? 0x1f96ffbf : i == 3 ? 0x1b4805ff : i == 4 ? 0x1d80553b
-         : i == 5 ? 0x0c0404d0 : i == 6 ? 0x1520cce7 : i == 7 ? 0x0a6533af : 0x0073eda7;
+    return f29_p_limb(i);
 }
 
 // 8 x u32 (value < 2^256) -> 9 x 29-bit limbs, same value
@@ -139,10 +139,12 @@ __device__ __forceinline__ Fe fe_carry_pass(const Fe &a) {
 }
 
 // ---- internal table format F29 -----------------------------------------------------------------------------------
-// An element is nine 29-bit limbs.  Limb 8 lives in a linear int32 array top[entry].  Limbs 0..7 live in the "main" array in
-// a chunk-planar layout chosen so that every store instruction of the bind kernel is contiguous across the wavefront:
+// An element is nine 29-bit limbs, limbs 0..7 in [0, 2^29) and limb 8 signed, PACKED into 32 bytes: its value as a 256-bit
+// two's-complement integer in eight 32-bit words (f29_pack.hpp: the encoding, and the range rule f29_settle that keeps every
+// stored value inside [-2^255, 2^255) without a modular reduction).  The eight words live in a chunk-planar layout chosen so
+// that every store instruction of the bind kernel is contiguous across the wavefront:
 // entries are grouped in blocks of 64 pairs (128 entries, 4 KiB); inside a block, plane k = 2*(entry & 1) + half holds the
-// 16-byte chunk (limbs 4*half .. 4*half+3) of that entry for the 64 pairs side by side:
+// 16-byte chunk (words 4*half .. 4*half+3) of that entry for the 64 pairs side by side:
 //     byte offset(entry e, half) = (e >> 7) * 4096 + (2 * (e & 1) + half) * 1024 + col(q) * 16,  q = e >> 1 (the pair),
 //     col(q) = ((q & 63) >> 1) | ((q & 1) << 5)   -- even pairs of the block in columns 0..31, odd pairs in 32..63.
 // The writer lane of pair q stores plane k at column col(q): the 64 lanes of a wavefront cover one contiguous 1 KiB row per
@@ -174,17 +176,26 @@ __device__ __forceinline__ uint64_t f29_chunk(uint64_t entry, int half) { // ind
     const uint64_t col = ((q & 63) >> 1) | ((q & 1) << 5); // even pairs in columns 0..31, odd pairs in 32..63
     return (entry >> 7) * 256 + (uint64_t)(2 * (int)(entry & 1) + half) * 64 + col;
 }
-__device__ __forceinline__ Fe fe_load_f29(const uint4 *main, uint64_t entry, int32_t top) {
+__device__ __forceinline__ Fe fe_load_f29(const uint4 *main, uint64_t entry) {
     const uint4 a = f29_ld(main + f29_chunk(entry, 0)), b = f29_ld(main + f29_chunk(entry, 1));
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     Fe r;
-    r.l[0] = (int32_t)a.x; r.l[1] = (int32_t)a.y; r.l[2] = (int32_t)a.z; r.l[3] = (int32_t)a.w;
-    r.l[4] = (int32_t)b.x; r.l[5] = (int32_t)b.y; r.l[6] = (int32_t)b.z; r.l[7] = (int32_t)b.w;
-    r.l[8] = top;
+    f29_unpack(w, r.l);
     return r;
 }
+// v: limbs 0..7 in [0, 2^29), limb 8 in [-2^23, 2^23) -- what fe_settle_f29 returns
 __device__ __forceinline__ void fe_store_f29(uint4 *main, uint64_t entry, const Fe &v) {
-    f29_st(main + f29_chunk(entry, 0), (uint32_t)v.l[0], (uint32_t)v.l[1], (uint32_t)v.l[2], (uint32_t)v.l[3]);
-    f29_st(main + f29_chunk(entry, 1), (uint32_t)v.l[4], (uint32_t)v.l[5], (uint32_t)v.l[6], (uint32_t)v.l[7]);
+    uint32_t w[8];
+    f29_pack(v.l, w);
+    f29_st(main + f29_chunk(entry, 0), w[0], w[1], w[2], w[3]);
+    f29_st(main + f29_chunk(entry, 1), w[4], w[5], w[6], w[7]);
+}
+// a freshly bound entry (e0 + fe_mul_bind(e1 - e0), both terms normalised) as the format stores it: p added once where the value
+// reads below about -p / 2, limbs 0..7 exact digits.  |result| < 2^255 for sources the format holds (f29_pack.hpp).
+__device__ __forceinline__ Fe fe_settle_f29(const Fe &a) {
+    Fe r = a;
+    f29_settle(r.l);
+    return r;
 }
 // One multiply-add of a column.  kChain: the instruction is written out, so that every multiply-add of a product accumulates into ONE
 // register pair in program order -- the compiler otherwise starts each column's chain from zero and joins it to the carry with a 64-bit

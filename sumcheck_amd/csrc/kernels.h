@@ -43,13 +43,12 @@ struct Slot {
     uint4 *dst;
     uint32_t mode;
     uint32_t exp; // multiplicity of the table inside the product (e.g. [1,4,4] -> table 4 has exp 2)
-    // Internal table format "F29" (big rounds after the first bind): an element is nine signed 29-bit limbs, limbs
-    // 0..7 in the 32-byte main array (same stride as the reference layout) and limb 8 in a separate 4-byte array, so
-    // a bound table is stored after a carry pass instead of a full canonical reduction + repack, and loads need no
-    // unpacking.  src_top == nullptr: `src` is in the reference layout (canonical 8 x 32-bit).  dst is always F29
-    // when dst_top != nullptr.
-    const int32_t *src_top;
-    int32_t *dst_top;
+    // Internal table format "F29" (big rounds after the first bind): an element is nine signed 29-bit limbs packed into the same 32
+    // bytes as a canonical element (fe_device.hpp, f29_pack.hpp), in a chunk-planar layout, so a bound table is stored after a carry
+    // chain instead of a full canonical reduction.  src_f29 == 0: `src` is in the reference layout (canonical 8 x 32-bit).
+    // dst_f29 != 0: the bound table is kept (mode 1: stored, mode 3: used) in the internal format.
+    uint32_t src_f29;
+    uint32_t dst_f29;
 };
 
 struct ProdArgs {
@@ -110,7 +109,7 @@ struct FinProd {
 struct TablePtrs {
     const uint4 *src[kMaxSmallTables];
     uint4 *dst[kMaxSmallTables];
-    const int32_t *src_top[kMaxSmallTables]; // non-null: that source table is in the internal F29 format
+    uint8_t src_f29[kMaxSmallTables]; // non-zero: that source table is in the internal F29 format
 };
 // one (product, evaluation point) combination of the small-round sum kernel (device memory, static per prover)
 struct Combo {
@@ -163,7 +162,7 @@ __host__ __device__ constexpr uint64_t tail_flat_pairs(int n_combos) {
 }
 struct TailTables {
     const uint4 *cur0[kMaxSmallTables];       // where each table's evaluations are when the tail starts ...
-    const int32_t *cur0_top[kMaxSmallTables]; // ... non-null: in the internal F29 format (straight from the big rounds)
+    uint8_t cur0_f29[kMaxSmallTables];        // ... non-zero: in the internal F29 format (straight from the big rounds)
     uint4 *b0[kMaxSmallTables];               // the 1st, 3rd, ... bind of the tail writes here
     uint4 *b1[kMaxSmallTables];               // the 2nd, 4th, ... here
 };
@@ -222,8 +221,9 @@ struct TailSlicesArgs {
 // reductions, which has to stay inside kLazySumMaxP too
 int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_combos, int max_multiplicands, int max_blocks, uint32_t worst_p);
 // The magnitude, in units of p, that the LDS-resident tail counts for one product of its first round.  Tables in the internal format have
-// been bound `lazy_binds` times with fe_mul_bind and a carry pass, never reduced: fe_mul_bind's term lies in (-p - 2^230, 2^230), so an
-// entry lies in (-(lazy_binds + 1) p, p) and sinks by about p / 2 a round on average; canonical tables bound on the way in: (-p, p).
+// been bound `lazy_binds` times with fe_mul_bind, never reduced: fe_mul_bind's term lies in (-p - 2^230, 2^230), so an
+// entry lies in (-(lazy_binds + 1) p, p) -- the packed format's range rule (f29_pack.hpp) keeps it in a subset of that, about
+// (-p / 2, p), and this bound is left as it was; canonical tables bound on the way in: (-p, p).
 constexpr uint32_t tail_worst_p(uint32_t lazy_binds) { return lazy_binds + 2; }
 int tail_slices_max_blocks(int device, int max_multiplicands); // occupancy of k_tail_slices<.> at its LDS limit x the device's CUs (0: unknown)
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, DEVICE): thread ranks of one process drive several GPUs
@@ -517,7 +517,7 @@ hipError_t launch_gather_to_tables(const uint4 *recv, uint4 *tabs, uint32_t G, u
 hipError_t launch_msg_accumulate(const FrHost *in, FrHost *acc, int D, bool first, bool last, FrHost *d_out, uint64_t *d_out_wide, FrHost *h_out_mapped,
                                  uint32_t *h_flag_mapped, uint32_t seq, hipStream_t stream);
 // F29 table -> canonical reference layout (state export)
-hipError_t launch_f29_to_sat(const uint4 *src, const int32_t *src_top, uint4 *dst, uint64_t n, hipStream_t stream);
+hipError_t launch_f29_to_sat(const uint4 *src, uint4 *dst, uint64_t n, hipStream_t stream);
 hipError_t launch_fr_elementwise(int op, const uint4 *a, const uint4 *b, const FrHost &u, uint4 *out, uint64_t n, hipStream_t stream);
 hipError_t launch_bench_modmul(uint64_t n_threads, uint32_t reps, uint32_t variant, uint64_t *d_sink, hipStream_t stream);
 

@@ -181,15 +181,14 @@ __global__ __launch_bounds__(kBlock) void k_fix_multi(const TablePtrs tp, const 
     const FeU r32 = feu_shl5(r.v);                       // carry-free bind: one chain of multiply-adds, no carry instruction (fe_device.hpp)
     const uint4 *__restrict__ src = tp.src[blockIdx.y];
     uint4 *__restrict__ dst = tp.dst[blockIdx.y];
-    const int32_t *__restrict__ stop = tp.src_top[blockIdx.y];
+    const bool sf29 = tp.src_f29[blockIdx.y] != 0;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < n_out; b += stride) {
         const uint4 *p = src + 4 * b;
         Fe lo, hi;
-        if (stop) { // first latency-bound round after the big rounds: the table arrives in F29 (used as it is), leaves canonical
-            const int2 t = *reinterpret_cast<const int2 *>(stop + 2 * b);
-            lo = fe_load_f29(src, 2 * b, t.x);
-            hi = fe_load_f29(src, 2 * b + 1, t.y);
+        if (sf29) { // first latency-bound round after the big rounds: the table arrives in F29 (used as it is), leaves canonical
+            lo = fe_load_f29(src, 2 * b);
+            hi = fe_load_f29(src, 2 * b + 1);
         } else {
             lo = fe_from_fr(fr_load(p));
             hi = fe_from_fr(fr_load(p + 2));
@@ -198,11 +197,10 @@ __global__ __launch_bounds__(kBlock) void k_fix_multi(const TablePtrs tp, const 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_f29_to_sat(const uint4 *__restrict__ src, const int32_t *__restrict__ stop, uint4 *__restrict__ dst,
-                                                       const uint64_t n) {
+__global__ __launch_bounds__(kBlock) void k_f29_to_sat(const uint4 *__restrict__ src, uint4 *__restrict__ dst, const uint64_t n) {
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-        fr_store(dst + 2 * i, fe_to_fr(fe_load_f29(src, i, stop[i])));
+        fr_store(dst + 2 * i, fe_to_fr(fe_load_f29(src, i)));
 }
 
 // The product of one (product, node) combination at pair b: prod_s line_s(node)^exp_s over the combination's slots.
@@ -591,11 +589,10 @@ __global__ __launch_bounds__(kBlock) void k_tail_rounds(const TailArgs A, const 
                 const uint4 *src = tab(u);
                 uint4 *dst = (binds & 1) ? A.t.b1[u] : A.t.b0[u];
                 Fe lo, hi;
-                const int32_t *stop = binds == 0 ? A.t.cur0_top[u] : nullptr;
-                if (stop) { // the table arrives from the big rounds in F29, leaves canonical
-                    const int2 t = *reinterpret_cast<const int2 *>(stop + 2 * b);
-                    lo = fe_load_f29(src, 2 * b, t.x);
-                    hi = fe_load_f29(src, 2 * b + 1, t.y);
+                const bool sf29 = binds == 0 && A.t.cur0_f29[u] != 0;
+                if (sf29) { // the table arrives from the big rounds in F29, leaves canonical
+                    lo = fe_load_f29(src, 2 * b);
+                    hi = fe_load_f29(src, 2 * b + 1);
                 } else {
                     lo = fe_from_fr(fr_load(src + 4 * b));
                     hi = fe_from_fr(fr_load(src + 4 * b + 2));
@@ -1104,8 +1101,8 @@ hipError_t launch_msg_accumulate(const FrHost *in, FrHost *acc, int D, bool firs
     return hipGetLastError();
 }
 
-hipError_t launch_f29_to_sat(const uint4 *src, const int32_t *src_top, uint4 *dst, uint64_t n, hipStream_t stream) {
-    hipLaunchKernelGGL(k_f29_to_sat, dim3(grid_for_pairs(n)), dim3(kBlock), 0, stream, src, src_top, dst, n);
+hipError_t launch_f29_to_sat(const uint4 *src, uint4 *dst, uint64_t n, hipStream_t stream) {
+    hipLaunchKernelGGL(k_f29_to_sat, dim3(grid_for_pairs(n)), dim3(kBlock), 0, stream, src, dst, n);
     return hipGetLastError();
 }
 

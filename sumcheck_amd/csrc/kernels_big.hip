@@ -791,7 +791,7 @@ hipError_t launch_round_tree(const RoundArgs &args, const BindConst &r32, uint64
 #endif
     bool round1 = args.fin.enabled == 0; // every factor read in place from a canonical table: the round-1 instantiation
     for (int q = 0; q < args.n_prod && round1; ++q)
-        for (uint32_t f = 0; f < args.prod[q].M; ++f) round1 = round1 && args.prod[q].slot[f].mode == 0 && args.prod[q].slot[f].src_top == nullptr;
+        for (uint32_t f = 0; f < args.prod[q].M; ++f) round1 = round1 && args.prod[q].slot[f].mode == 0 && args.prod[q].slot[f].src_f29 == 0;
 #ifdef SC_EXPERIMENTS
     if (!split) {
         if (skip1) return hipErrorInvalidValue;
@@ -810,7 +810,7 @@ hipError_t launch_round_tree(const RoundArgs &args, const BindConst &r32, uint64
     bool canonical_sources = !round1;
 #endif
     for (int q = 0; q < args.n_prod && canonical_sources; ++q)
-        for (uint32_t f = 0; f < args.prod[q].M; ++f) canonical_sources = canonical_sources && args.prod[q].slot[f].src_top == nullptr;
+        for (uint32_t f = 0; f < args.prod[q].M; ++f) canonical_sources = canonical_sources && args.prod[q].slot[f].src_f29 == 0;
     const dim3 g(grid, args.n_prod), b(kBlock);
     uint4 *const part = (uint4 *)d_partials;
     plan_hit(round1 ? kPlanBigMergedRound1 : canonical_sources ? kPlanBigMergedBindChain : kPlanBigMergedBind);

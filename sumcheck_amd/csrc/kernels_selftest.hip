@@ -36,6 +36,9 @@ enum FeOp : int {
     kOpFoldCell = 16,    // wide_fold_cell(aux + 4 + 8 i)
     kOpWideValue = 17,   // wide_value<m, t>(v), m = aux[0] (1: the single factor's line as WideNodes takes it), t = aux[1]      a: n x 5 x 9
     kOpWideExt = 18,     // wide_ext<m, t>(v)                                                                                   a: n x 9 x 9
+    kOpF29RoundTrip = 19, // fe_load_f29(fe_store_f29(a)): the packed table format (f29_pack.hpp), one launch stores entry i from lane i, a second
+                          // loads it back; n a multiple of 128 (the layout's block), b: n x 8 ints of scratch for the table
+    kOpF29Settle = 20,    // fe_settle_f29(a): the range rule and the exact digits of a freshly bound entry
 };
 
 __device__ __forceinline__ Fe st_load(const int32_t *p, const uint64_t i) {
@@ -128,6 +131,9 @@ __global__ __launch_bounds__(kTsBlock) void k_fe_op(const int32_t *__restrict__ 
         const Fe r = bt_combo_sum(true, (uint32_t)(gid % L), (int)L, pairs, lazy_sum_needs_reduce(pairs, (uint32_t)p2),
                                   [&](const uint32_t pr) -> Fe { return st_load(a, group * pairs + pr); });
         st_store(out, gid, r);
+    } else if constexpr (kOp == kOpF29Settle) {
+        const Fe r = fe_settle_f29(st_load(a, i));
+        if (live) st_store(out, i, r);
     } else if constexpr (kOp == kOpFoldCell) {
         uint64_t lane[8];
 #pragma unroll
@@ -135,6 +141,15 @@ __global__ __launch_bounds__(kTsBlock) void k_fe_op(const int32_t *__restrict__ 
         const Fr r = wide_fold_cell(lane);
         if (live) st_store_fr(out, i, r);
     }
+}
+
+__global__ __launch_bounds__(kTsBlock) void k_f29_store_op(const int32_t *__restrict__ a, uint4 *__restrict__ table, const uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kTsBlock + threadIdx.x;
+    if (i < n) fe_store_f29(table, i, st_load(a, i));
+}
+__global__ __launch_bounds__(kTsBlock) void k_f29_load_op(const uint4 *__restrict__ table, int32_t *__restrict__ out, const uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * kTsBlock + threadIdx.x;
+    if (i < n) st_store(out, i, fe_load_f29(table, i));
 }
 
 template <int m, int t>
@@ -179,9 +194,10 @@ extern "C" __attribute__((visibility("default"))) int sc_debug_fe_op(int op, con
         const uint64_t L = par[1];
         if (par[0] == 0 || par[0] > 64 || L == 0 || L > 64 || (L & (L - 1)) != 0 || n % kTsBlock != 0) return -2;
     }
-    if ((op >= kOpMul && op <= kOpMul2Chain) || op == kOpShl5MulU || op == kOpLine) {
+    if ((op >= kOpMul && op <= kOpMul2Chain) || op == kOpShl5MulU || op == kOpLine || op == kOpF29RoundTrip) {
         if (b == nullptr) return -2;
     }
+    if (op == kOpF29RoundTrip && n % 128 != 0) return -2; // whole blocks of the layout: every chunk index stays below n * 2
     if ((op == kOpMul2 || op == kOpMul2Chain) && (c == nullptr || d == nullptr)) return -2;
     const int64_t p0 = (int64_t)par[0], p1 = (int64_t)par[1], p2 = (int64_t)par[2];
 #define SC_FE_OP(OP)                                                                                                    \
@@ -212,6 +228,13 @@ extern "C" __attribute__((visibility("default"))) int sc_debug_fe_op(int op, con
         SC_FE_OP(kOpLine)
         SC_FE_OP(kOpAccum)
         SC_FE_OP(kOpFoldCell)
+        SC_FE_OP(kOpF29Settle)
+    case kOpF29RoundTrip: {
+        uint4 *table = reinterpret_cast<uint4 *>(const_cast<int32_t *>(b));
+        hipLaunchKernelGGL(k_f29_store_op, grid, block, 0, 0, a, table, n);
+        hipLaunchKernelGGL(k_f29_load_op, grid, block, 0, 0, table, out, n);
+        break;
+    }
     case kOpWideValue:
         // every instantiation the product trees of five to eight make (wide_tree.hpp: WideNodes<M, t>): the first half at the nodes beyond
         // its own, the second half (one to four factors) likewise

@@ -206,21 +206,20 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
                 const uint32_t u = i >> shE, e = i & (E - 1);
                 const uint64_t ge = (uint64_t)g * E + e; // the entry's index in this round's table
                 const uint4 *src = A.t.cur0[u];
-                const int32_t *stop = A.t.cur0_top[u];
+                const bool sf29 = A.t.cur0_f29[u] != 0;
                 Fe v;
                 if (has_bind) { // entries 2 ge, 2 ge + 1 of the previous table
                     Fe lo, hi;
-                    if (stop) {
-                        const int2 t = *reinterpret_cast<const int2 *>(stop + 2 * ge);
-                        lo = fe_load_f29(src, 2 * ge, t.x);
-                        hi = fe_load_f29(src, 2 * ge + 1, t.y);
+                    if (sf29) {
+                        lo = fe_load_f29(src, 2 * ge);
+                        hi = fe_load_f29(src, 2 * ge + 1);
                     } else {
                         lo = fe_from_fr(fr_load(src + 4 * ge));
                         hi = fe_from_fr(fr_load(src + 4 * ge + 2));
                     }
                     v = fe_carry_pass(fe_add(lo, fe_mul_u<true>(fe_sub(hi, lo), r32)));
                 } else {
-                    v = stop ? fe_load_f29(src, ge, stop[ge]) : fe_from_fr(fr_load(src + 2 * ge));
+                    v = sf29 ? fe_load_f29(src, ge) : fe_from_fr(fr_load(src + 2 * ge));
                 }
                 ts_lds_store(tab_at((int)u, e), v);
             }

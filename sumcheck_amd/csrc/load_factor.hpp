@@ -20,13 +20,12 @@ struct LoadFactor {
             return;
         }
         const uint32_t mode = sl.mode;
-        const int32_t *stop = sl.src_top; // non-null: the source table is in the internal F29 format
+        const bool sf29 = sl.src_f29 != 0; // the source table is in the internal F29 format
         if (mode == 0) {
             const uint4 *p = sl.src + 4 * b;
-            if (stop) {
-                const int2 t = *reinterpret_cast<const int2 *>(stop + 2 * b);
-                lo_out = fe_load_f29(sl.src, 2 * b, t.x);
-                hi_out = fe_load_f29(sl.src, 2 * b + 1, t.y);
+            if (sf29) {
+                lo_out = fe_load_f29(sl.src, 2 * b);
+                hi_out = fe_load_f29(sl.src, 2 * b + 1);
             } else {
                 lo_out = fe_from_fr(fr_load(p));
                 hi_out = fe_from_fr(fr_load(p + 2));
@@ -34,28 +33,26 @@ struct LoadFactor {
         } else {
             const uint4 *p = sl.src + 8 * b; // entries 4b..4b+3 of the previous table: 128 contiguous bytes
             Fe e0, e1, e2, e3;
-            if (stop) {
-                const int4 t = *reinterpret_cast<const int4 *>(stop + 4 * b);
+            if (sf29) {
                 const uint4 *m = sl.src;
-                e0 = fe_load_f29(m, 4 * b, t.x); e1 = fe_load_f29(m, 4 * b + 1, t.y);
-                e2 = fe_load_f29(m, 4 * b + 2, t.z); e3 = fe_load_f29(m, 4 * b + 3, t.w);
+                e0 = fe_load_f29(m, 4 * b); e1 = fe_load_f29(m, 4 * b + 1);
+                e2 = fe_load_f29(m, 4 * b + 2); e3 = fe_load_f29(m, 4 * b + 3);
             } else {
                 e0 = fe_from_fr(fr_load(p)); e1 = fe_from_fr(fr_load(p + 2)); e2 = fe_from_fr(fr_load(p + 4)); e3 = fe_from_fr(fr_load(p + 6));
             }
             const Fe l0 = fe_add(e0, fe_mul_bind<kChain>(fe_sub(e1, e0), r));
             asm volatile("" : "+v"(e3.l[8]) : "v"(l0.l[8])); // one product at a time: interleaving the two doubles the live constants
             const Fe h0 = fe_add(e2, fe_mul_bind<kChain>(fe_sub(e3, e2), r));
-            if (sl.dst_top || (mode == 3 && stop)) {
-                // internal F29 tables: ONE parallel carry pass, no modular reduction.  The value moves by < p + 2^231 per bind
-                // (fe_mul_bind: r*(e1-e0) comes back in (-p - 2^230, 2^230)), i.e. stays within (rounds+1) p < 2^261 in magnitude for any
-                // nv <= 40, which every consumer tolerates: the multipliers' bounds depend on limb sizes only (limbs 0..7 are
-                // re-tightened here, the top limb stays below 2^28), and fe_to_fr reduces any |v| < 2^260 exactly.
-                lo_out = fe_carry_pass(l0);
-                hi_out = fe_carry_pass(h0);
+            if (sl.dst_f29 || (mode == 3 && sf29)) {
+                // internal F29 tables: no modular reduction.  fe_mul_bind's term lies in (-p - 2^230, 2^230); where the sum reads below
+                // -p / 2, p is added back once, inside the carry chain that makes limbs 0..7 exact 29-bit digits (fe_settle_f29).  From
+                // canonical tables, k binds leave an entry in (-p / 2 - (k - 1) 2^230, p + k 2^230): inside the packed form's
+                // [-2^255, 2^255) for any nv <= 40, and inside the (-(k + 1) p, p) that every consumer's bound was written for.
+                lo_out = fe_settle_f29(l0);
+                hi_out = fe_settle_f29(h0);
                 if (mode == 1) {
                     fe_store_f29(sl.dst, 2 * b, lo_out);
                     fe_store_f29(sl.dst, 2 * b + 1, hi_out);
-                    *reinterpret_cast<int2 *>(sl.dst_top + 2 * b) = make_int2(lo_out.l[8], hi_out.l[8]);
                 }
             } else { // tables stay canonical in the reference layout
                 const Fr lc = fe_to_fr(l0), hc = fe_to_fr(h0);

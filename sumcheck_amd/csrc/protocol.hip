@@ -219,17 +219,17 @@ int launch_round_streamed(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_w
                         scd::Slot &sl = tp.slot[f];
                         sl.exp = 1;
                         sl.src = ring_tab(u);
-                        sl.src_top = nullptr;
+                        sl.src_f29 = 0;
                         if (!bind) {
                             sl.mode = 0;
                         } else if (!bound[u]) { // this chunk's half of the bound table, in place (F29 blocks of 128 entries stay aligned: C / 2 >= 512)
                             sl.mode = 1;
                             sl.dst = t.buf[0] + 2 * (c * (C / 2));
-                            sl.dst_top = p->use_f29 ? t.buf_top[0] + c * (C / 2) : nullptr;
+                            sl.dst_f29 = p->use_f29 ? 1 : 0;
                             bound[u] = 1;
                         } else {
                             sl.mode = 3;
-                            sl.dst_top = p->use_f29 ? t.buf_top[0] : nullptr;
+                            sl.dst_f29 = p->use_f29 ? 1 : 0;
                         }
                     }
                 }
@@ -304,7 +304,7 @@ int launch_round_streamed(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_w
             for (const Product &pr : p->prods)
                 for (uint32_t tt : pr.tables) referenced |= tt == u;
             t.cur = t.buf[0];
-            t.cur_top = (merged && p->use_f29 && referenced) ? t.buf_top[0] : nullptr;
+            t.cur_f29 = merged && p->use_f29 && referenced;
             t.next = 1;
         }
     }
@@ -527,7 +527,7 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
                 for (uint32_t j = 0; j < cnt; ++j) {
                     Table &t = p->tabs[u0 + j];
                     tp.src[j] = t.cur;
-                    tp.src_top[j] = t.cur_top;
+                    tp.src_f29[j] = t.cur_f29 ? 1 : 0;
                     tp.dst[j] = t.buf[t.next];
                 }
                 {
@@ -537,7 +537,7 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
                 for (uint32_t j = 0; j < cnt; ++j) {
                     Table &t = p->tabs[u0 + j];
                     t.cur = t.buf[t.next];
-                    t.cur_top = nullptr; // the latency-bound path keeps tables canonical in the reference layout
+                    t.cur_f29 = false; // the latency-bound path keeps tables canonical in the reference layout
                     t.next ^= 1;
                 }
             }
@@ -566,14 +566,14 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
             for (uint32_t j = 0; j < cnt; ++j) {
                 Table &t = p->tabs[u0 + j];
                 tp.src[j] = t.cur;
-                tp.src_top[j] = t.cur_top;
+                tp.src_f29[j] = t.cur_f29 ? 1 : 0;
                 tp.dst[j] = t.buf[t.next];
             }
             HIP_TRY(scd::launch_fix_multi(tp, (int)cnt, rdev, nullptr, 2 * n_pairs, p->stream));
             for (uint32_t j = 0; j < cnt; ++j) {
                 Table &t = p->tabs[u0 + j];
                 t.cur = t.buf[t.next];
-                t.cur_top = nullptr;
+                t.cur_f29 = false;
                 t.next ^= 1;
             }
         }
@@ -616,10 +616,10 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
         std::memset(&ra, 0, sizeof(ra));
         ra.n_prod = (int)p->K;
         std::vector<const uint4 *> old_src(p->U);
-        std::vector<const int32_t *> old_top(p->U);
+        std::vector<uint8_t> old_f29(p->U);
         for (uint32_t u = 0; u < p->U; ++u) {
             old_src[u] = p->tabs[u].cur;
-            old_top[u] = p->tabs[u].cur_top;
+            old_f29[u] = p->tabs[u].cur_f29 ? 1 : 0;
         }
         for (uint32_t k = 0; k < p->K; ++k) {
             const Product &pr = p->prods[k];
@@ -634,20 +634,20 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
                     scd::Slot &sl = tp.slot[f];
                     sl.exp = 1;
                     sl.src = old_src[u];
-                    sl.src_top = old_top[u];
+                    sl.src_f29 = old_f29[u];
                     if (!bind) {
                         sl.mode = 0;
                     } else if (!bound[u]) {
                         sl.mode = 1;
                         sl.dst = t.buf[t.next];
-                        sl.dst_top = p->use_f29 ? t.buf_top[t.next] : nullptr;
+                        sl.dst_f29 = p->use_f29 ? 1 : 0;
                         t.cur = t.buf[t.next];
-                        t.cur_top = sl.dst_top;
+                        t.cur_f29 = p->use_f29;
                         t.next ^= 1;
                         bound[u] = 1;
                     } else {
                         sl.mode = 3;
-                        sl.dst_top = p->use_f29 ? t.buf_top[0] : nullptr; // only selects the carry-pass path
+                        sl.dst_f29 = p->use_f29 ? 1 : 0; // (nothing is stored: keeps the value in the stored table's form)
                     }
                 }
             }
@@ -687,31 +687,31 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
             for (size_t s = 0; s < pr.tables.size(); ++s) {
                 Table &t = p->tabs[pr.tables[s]];
                 const uint4 *old_src = t.cur;
-                const int32_t *old_top = t.cur_top;
+                const uint32_t old_f29 = t.cur_f29 ? 1 : 0;
                 bool stored_here = false;
                 for (uint32_t rep = 0; rep < pr.exps[s]; ++rep, ++f) {
                     a.slot[f].exp = 1;
                     if (bind && !bound[pr.tables[s]]) {
                         a.slot[f].mode = 1;
                         a.slot[f].src = old_src;
-                        a.slot[f].src_top = old_top;
+                        a.slot[f].src_f29 = old_f29;
                         a.slot[f].dst = t.buf[t.next];
-                        a.slot[f].dst_top = p->use_f29 ? t.buf_top[t.next] : nullptr;
+                        a.slot[f].dst_f29 = p->use_f29 ? 1 : 0;
                         t.cur = t.buf[t.next];
-                        t.cur_top = a.slot[f].dst_top;
+                        t.cur_f29 = p->use_f29;
                         t.next ^= 1;
                         bound[pr.tables[s]] = 1;
                         stored_here = true;
                     } else if (stored_here) {
                         a.slot[f].mode = 3;
                         a.slot[f].src = old_src;
-                        a.slot[f].src_top = old_top;
+                        a.slot[f].src_f29 = old_f29;
                         a.slot[f].dst = nullptr;
-                        a.slot[f].dst_top = p->use_f29 ? t.buf_top[0] : nullptr; // only selects the tighten path
+                        a.slot[f].dst_f29 = p->use_f29 ? 1 : 0; // (nothing is stored: keeps the value in the stored table's form)
                     } else {
                         a.slot[f].mode = 0;
                         a.slot[f].src = t.cur;
-                        a.slot[f].src_top = t.cur_top;
+                        a.slot[f].src_f29 = t.cur_f29 ? 1 : 0;
                         a.slot[f].dst = nullptr;
                     }
                 }
@@ -765,7 +765,7 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
                 a.slot[f].mode = 0;
                 a.slot[f].exp = 1;
                 a.slot[f].src = t.cur;
-                a.slot[f].src_top = t.cur_top;
+                a.slot[f].src_f29 = t.cur_f29 ? 1 : 0;
             }
             sch::Fr comp = sch::kOne; // 2^(5(M-1)) in Montgomery form
             for (uint32_t dbl = 0; dbl < 5 * (pr.M - 1); ++dbl) comp = sch::add(comp, comp);
@@ -964,7 +964,7 @@ bool tail_possible(sc_prover *p, bool slices = false) {
 // tail_worst_p of the tables as they stand: every round so far may have bound a table in the internal format lazily
 static uint32_t tail_tables_worst_p(sc_prover *p) {
     bool f29 = false;
-    for (uint32_t u = 0; u < p->U; ++u) f29 = f29 || p->tabs[u].cur_top != nullptr;
+    for (uint32_t u = 0; u < p->U; ++u) f29 = f29 || p->tabs[u].cur_f29;
     return scd::tail_worst_p(f29 ? p->round : 0);
 }
 int tail_slices_blocks_for(sc_prover *p) {
@@ -1001,7 +1001,7 @@ int tail_launch(sc_prover *p, uint32_t n_rounds, const sch::Fr *r_or_null, uint3
     for (uint32_t u = 0; u < p->U; ++u) {
         Table &t = p->tabs[u];
         A.t.cur0[u] = t.cur;
-        A.t.cur0_top[u] = t.cur_top;
+        A.t.cur0_f29[u] = t.cur_f29 ? 1 : 0;
         A.t.b0[u] = t.buf[t.next];
         A.t.b1[u] = t.buf[t.next ^ 1];
     }
@@ -1061,7 +1061,7 @@ void tail_epilogue_tables(sc_prover *p, uint32_t nb) {
         Table &t = p->tabs[u];
         uint4 *b0 = t.buf[t.next], *b1 = t.buf[t.next ^ 1];
         t.cur = (nb & 1) ? b0 : b1;
-        t.cur_top = nullptr;
+        t.cur_f29 = false;
         if (nb & 1) t.next ^= 1;
     }
 }

@@ -97,9 +97,8 @@ struct Product {
 
 struct Table {
     const uint4 *cur = nullptr;       // this round's evaluations (main array)
-    const int32_t *cur_top = nullptr; // non-null: `cur` is in the internal F29 format and this is its limb-8 array
+    bool cur_f29 = false;             // `cur` is in the internal F29 format (fe_device.hpp: 32 bytes an entry, chunk-planar)
     uint4 *buf[2] = {nullptr, nullptr};
-    int32_t *buf_top[2] = {nullptr, nullptr}; // limb-8 arrays of the two ping-pong buffers
     int next = 0;                     // buffer the next bind writes to
 };
 

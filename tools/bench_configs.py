@@ -180,7 +180,7 @@ if "--only-gkr" in sys.argv:  # for rocprofv3 runs of config 5 alone
     print(json.dumps({"config5_gkr": gkr(20)}, indent=1))
     sys.exit(0)
 out = {"config2": ml(20, [[0, 1, 2]], 3), "readme_bench_shape": ml(20, [[0, 1, 2], [3, 4, 5]], 6), "config5_gkr": gkr(20)}
-if "--config4" in sys.argv:  # the whole nv=28 job of config 4 on ONE GPU (24 GiB of tables + 13.5 GiB of bound-table buffers in HBM)
+if "--config4" in sys.argv:  # the whole nv=28 job of config 4 on ONE GPU (24 GiB of tables + 12 GiB of bound-table buffers in HBM)
     out["config4_nv28_one_gpu"] = ml(28, [[0, 1, 2]], 3, reps=3, cpu=False)
     out["config4_shard_nv25_one_gpu"] = ml(25, [[0, 1, 2]], 3, reps=5, cpu=False)
 print(json.dumps(out, indent=1))
