@@ -197,6 +197,15 @@ constexpr int kTsBlock = 256, kTsMaxBlocks = 256;
 // (fe_from_fr(fe_to_fr(acc)), exact for every int32 top limb).  The rule, wave-uniform: terms x (worst magnitude of a term in units of p).
 constexpr uint32_t kLazySumMaxP = 282;
 __host__ __device__ constexpr bool lazy_sum_needs_reduce(uint64_t terms, uint32_t worst_p) { return terms * (uint64_t)worst_p > (uint64_t)kLazySumMaxP; }
+// A line through two lazy entries leaves the entries' range: entries in (-(w - 1) p, p) put node x > 0 (x - 1 slopes beyond hi) and node -x
+// (x slopes beyond lo) within (n w - 1) p, n = ceil(D / 2) for a list of degree D.  A product is the chain prod = fe_mul(line, prod), and a
+// factor of magnitude L p scales the running product by L / 70.66 (2^261 = 70.66 p) and adds up to p: while L <= 69 the product stays below
+// 69 p -- inside fe_mul's second operand, |limb 8| <= 2^29 + 16 --, beyond 70.66 it GROWS with every factor (twelve factors at 89 p: 1100 p,
+// outside int32).  n w <= 70 holds by itself for every tail of products of up to kMaxFusedM multiplicands (n <= 4, w <= 17: DESIGN 4.6);
+// k_tail_slices<kMaxWideM> (n = 5, 6) stores a bind's results canonical where it would not: w starts again at tail_worst_p(0).
+constexpr uint32_t kLineReachMaxP = 70;
+__host__ __device__ constexpr uint32_t line_reach_n(int D) { return ((uint32_t)D + 1) / 2; }
+__host__ __device__ constexpr bool line_needs_canonical(uint32_t n, uint32_t w) { return n * w > kLineReachMaxP; }
 constexpr uint64_t kTsMaxPairs = 1u << 16; // it takes over from the first latency-bound round (kSmallRoundPairs) where the slices fit LDS, and up to two
                                            // rounds earlier for shapes with few multiplications per pair (tail_slices_blocks)
 // hand-over area (64-bit words): a ring of four accumulator sets (8 groups x kMetaCombos x 8 words) | the last entries of merging blocks

@@ -129,6 +129,20 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
     uint64_t n_pairs = A.first_pairs; // pairs of the round in hand, over all blocks
     uint32_t E = 0;                   // entries per table this block holds
     int binds = 0;
+    // kSlots > kMaxFusedM only (kernels.h: line_needs_canonical): the entries lie in (-(lazy_w - 1) p, p), one p more with every bind; the
+    // bind after which a line of this list could pass 70 p stores its results canonical instead (wave-uniform, the same in every block)
+    uint32_t lazy_w = S.worst_p;
+    const uint32_t reach_n = line_reach_n(A.D);
+    auto bind_stores_canonical = [&](const bool bound) -> bool {
+        if constexpr (kSlots > kMaxFusedM) {
+            if (bound) lazy_w += 1;
+            if (!line_needs_canonical(reach_n, lazy_w)) return false;
+            lazy_w = tail_worst_p(0);
+            return true;
+        } else {
+            return false;
+        }
+    };
     for (int j = 0; j < A.n_rounds; ++j, n_pairs >>= 1) {
         const uint32_t tag = S.tag0 + (uint32_t)j;
         const bool has_bind = j > 0 || A.first_has_bind;
@@ -202,6 +216,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
             E = (uint32_t)((2 * n_pairs) / B); // entries per table and block of THIS round's tables
             const uint32_t total = E * (uint32_t)U;
             const int shE = 31 - __builtin_clz(E); // (E is a power of two: no integer divisions on a latency-bound path)
+            const bool canonical = bind_stores_canonical(has_bind);
             for (uint32_t i = tid; i < total; i += kTsBlock) {
                 const uint32_t u = i >> shE, e = i & (E - 1);
                 const uint64_t ge = (uint64_t)g * E + e; // the entry's index in this round's table
@@ -221,6 +236,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
                 } else {
                     v = sf29 ? fe_load_f29(src, ge) : fe_from_fr(fr_load(src + 2 * ge));
                 }
+                if (canonical) v = fe_from_fr(fe_to_fr(v));
                 ts_lds_store(tab_at((int)u, e), v);
             }
             if (has_bind) binds += 1;
@@ -230,6 +246,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
             // read higher entries than any earlier pass wrote (2 e'' > e for e'' > e).
             const uint32_t half = E / 2, total = half * (uint32_t)U;
             const int shH = 31 - __builtin_clz(half);
+            const bool canonical = bind_stores_canonical(true);
             for (uint32_t i0 = 0; i0 < total; i0 += kTsBlock) {
                 const uint32_t i = i0 + tid;
                 const bool live = i < total;
@@ -238,6 +255,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
                 if (live) {
                     const Fe lo = ts_lds_load(tab_at((int)u, 2 * e)), hi = ts_lds_load(tab_at((int)u, 2 * e + 1));
                     v = fe_carry_pass(fe_add(lo, fe_mul_u<true>(fe_sub(hi, lo), r32)));
+                    if (canonical) v = fe_from_fr(fe_to_fr(v));
                 }
                 __syncthreads();
                 if (live) ts_lds_store(tab_at((int)u, e), v);

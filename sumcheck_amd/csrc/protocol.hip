@@ -53,8 +53,8 @@ bool launches_are_async(sc_prover *p) {
 // for this handle.
 bool ensure_mailbox(sc_prover *p) {
     if (!p->pipeline_ok) return false;
-    if (p->sig) return true;
-    bool env_off = scd::policy(scd::kPolPipeline) == 0; // read per handle, at its first late round
+    if (p->sig) return scd::policy(scd::kPolPipeline) != 0; // (a handle that comes back from the pool brings its mailbox along: the policy still decides)
+    bool env_off = scd::policy(scd::kPolPipeline) == 0; // a handle without a mailbox: read at its first late round
     // a runtime that makes every launch wait for its kernel would block on the waiting kernel until its bound expires
     for (const char *name : {"AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING"}) {
         const char *v = std::getenv(name);

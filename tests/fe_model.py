@@ -338,6 +338,78 @@ def selector_table(nv: int, s, sel: int, m: int, c: int, flip: bool = False):
     return [P - 1 if (x >> sel) & 1 == const_bit else half[(x & lo_mask) | ((x >> (sel + 1)) << sel)] for x in range(1 << nv)]
 
 
+# ---- every factor of a product at its range end at once: the product loop of k_tail_slices and bt_sum_message -------------------
+MAX_WIDE_M = 12             # kernels.h: kMaxWideM
+LINE_REACH_MAX_P = 70       # kernels.h: kLineReachMaxP = floor(2^261 / p)
+
+
+def product_chain(vals, strict: bool = True):
+    """kernels_tail.hip's and bt_sum_message's product loop: the first factor is handed on as the running product, every further one is
+    fe_mul(val, prod) -- val the FIRST operand (BOX_MUL_A), the running product the SECOND (BOX_MUL_B), every result an int32 vector.
+    A multiplicity e is the same value e times in `vals` (the exponent loop).  -> (product, peak |fe_mul result|, what was left: a set of
+    "mul_a", "mul_b", "int32"); strict: leaving anything is an AssertionError"""
+    left = set()
+    prod, peak = vals[0], 0
+    for val in vals[1:]:
+        if not in_box(val, BOX_MUL_A):
+            left.add("mul_a")
+        if not in_box(prod, BOX_MUL_B):
+            left.add("mul_b")
+        prod = fe_mul(val, prod)
+        if not fits_i32(prod):
+            left.add("int32")
+        peak = max(peak, abs(value(prod)))
+    assert not (strict and left), f"the product chain leaves {sorted(left)}"
+    return prod, peak, left
+
+
+def line_reach_n(M: int) -> int:
+    """the n of a line's reach (n (k + 2) - 1) p for entries in (-(k + 1) p, p): node x > 0 is x - 1 slopes beyond hi, node -x is x slopes
+    beyond lo, and a product of M takes the nodes node_value(0 .. M) -- kernels.h: line_reach_n(D) = (D + 1) / 2"""
+    n = max(x if x > 0 else 1 - x for x in (node_value(t) for t in range(M + 1)) if x != NODE_INF)
+    assert n == (M + 1) // 2 or M == 1
+    return n
+
+
+def line_needs_canonical(n: int, worst_p: int) -> bool:
+    """kernels.h: line_needs_canonical -- entries in (-(worst_p - 1) p, p) put a line within (n worst_p - 1) p; beyond 69 p a chain of
+    fe_muls no longer keeps its running product inside fe_mul's second operand (prod' < prod L / 70.66 + 1 in units of p)"""
+    return n * worst_p > LINE_REACH_MAX_P
+
+
+def lazy_binds_under_the_rule(M: int, k: int) -> int:
+    """k_tail_slices<12>'s bookkeeping for a tail that starts from canonical tables (tail_worst_p(0) = 2): the binds behind an entry since it
+    was last canonical, after k binds.  A bind whose result could put a line beyond the reach writes its entries canonical instead"""
+    n, lazy = line_reach_n(M), 0
+    for _ in range(k):
+        lazy = 0 if line_needs_canonical(n, lazy + 1 + 2) else lazy + 1
+    return lazy
+
+
+def selector_pair(k: int, m: int, c: int, flip: bool, lazy: int = None, delta: int = DELTA):
+    """a selector table's pair in round k + 1 = sel + 1, in closed form: the entry that started at the stored integer c has sunk k times,
+    c + k (m delta - p), against the constant p - 1 -- (lo, hi), flip: the other way round.  lazy < k: the entry was made canonical
+    k - lazy binds ago (c + (k - lazy) m delta, still below p) and has sunk `lazy` times since"""
+    lazy = k if lazy is None else lazy
+    assert 0 <= lazy <= k and 0 <= c and c + k * m * delta < P
+    e, one = limbs_of(c + k * m * delta - lazy * P), limbs_of(P - 1)
+    return (one, e) if flip else (e, one)
+
+
+def all_selector_values(M: int, k: int, orient: str, t_node: int, lazy: int = None, low: bool = True, mult=None):
+    """the factors of one pair's product at node index t_node, in the kernel's order, when EVERY table is a selector at sel = k
+    (tests/test_gpu_lazy_entries.py: selector(): m = 1 + t % 7): orient "up" (entries on the lo side), "down" or "alt" (odd tables down);
+    low: the pair whose entries started lowest (c = t) or highest (c = 7 * 2^203 + t: beyond any m sum s_j); mult: the multiplicity of every
+    table (default: M distinct tables)"""
+    mult = [1] * M if mult is None else mult
+    vals = []
+    for t, e in enumerate(mult):
+        flip = orient == "down" or (orient == "alt" and t % 2 == 1)
+        lo, hi = selector_pair(k, 1 + t % 7, t if low else (7 << 203) + t, flip, lazy)
+        vals += [fe_line(lo, hi, node_value(t_node))[0]] * e
+    return vals
+
+
 def to_mont(r_std: int) -> int:
     """a standard-form value as the API takes it and the tables store it"""
     return r_std * R256 % P

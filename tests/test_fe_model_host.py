@@ -276,3 +276,144 @@ def test_the_array_builders_give_the_formulas_entries():
     with pytest.raises(AssertionError):
         H.assert_entries_match(u, H.selector_entry(s, 11, 1, P - 1, False))
     assert H.mont_challenges(r).shape == (nv, 4) and as_ints(H.mont_challenges(r[:2])) == [x * fm.R256 % P for x in r[:2]]
+
+
+# ---- every factor of a product at its range end at once: the product loop on all-selector pairs, in closed form ------------------
+import functools
+
+LAMBDA = (1 << fm.K) / P  # 70.66: a factor of magnitude L p scales a running product by L / LAMBDA (and fe_mul's window adds up to p)
+ORIENTS = ["up", "down", "alt"]
+K_TAIL_MAX = 15           # a tail of 2^14 pairs whose first round binds on the way in: 15 binds behind its last round (2^14 = kSmallRoundPairs)
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_the_selector_pairs_closed_form_is_what_the_binds_leave(form):
+    """selector_pair against the tables bound round by round, both orientations; and with the entries made canonical after k0 binds
+    (what the rule of k_tail_slices<12> does): the stored integers are a sinking table again, c + k0 m delta, and sink from there"""
+    s, r = _family()
+    for sel, m, flip in ((0, 1, False), (3, 7, True), (SEL, 2, False), (NV - 1, 5, True)):
+        ints = fm.selector_table(NV, s, sel, m, m * sum(s) + 3, flip)
+        for k0 in sorted({0, sel // 2, sel}):
+            tab = _rounds(form, ints, r[:k0])[k0]
+            if k0:
+                tab = [fm.limbs_of(fm.value(e) % P) for e in tab]
+                assert all(0 <= fm.value(e) < P for e in tab)
+            tab = _rounds(form, [fm.value(e) for e in tab], r[k0:sel])[sel - k0]
+            for i in range(len(tab) // 2):
+                start = ints[(2 * i + (1 if flip else 0)) << sel]
+                lo, hi = fm.selector_pair(sel, m, start, flip, lazy=sel if k0 == 0 else sel - k0)
+                assert (fm.value(tab[2 * i]), fm.value(tab[2 * i + 1])) == (fm.value(lo), fm.value(hi)), (sel, k0, i)
+                assert _in_line_box_limbs(tab[2 * i]) and _in_line_box_limbs(tab[2 * i + 1])
+
+
+def test_product_chain_is_the_field_product_and_names_what_it_leaves():
+    rng = random.Random(fm.SEED + 7)
+    vals = [fm.limbs_of(rng.randrange(P)) for _ in range(12)]
+    prod, peak, left = fm.product_chain(vals)
+    want = 1
+    for v in vals:
+        want = want * fm.value(v) % P
+    assert fm.value(prod) % P == want * pow(1 << fm.K, -11, P) % P and not left and peak < 2 * P
+    wide = [fm.limbs_of(-89 * P + 5)] * 12  # node -5 of an all-selector product of twelve after 14 binds
+    assert fm.product_chain(wide, strict=False)[2] == {"mul_b", "int32"}
+    with pytest.raises(AssertionError):
+        fm.product_chain(wide)
+    assert fm.product_chain([fm.limbs_of(P), fm.limbs_of(142 * P)], strict=False)[2] == {"mul_a"}  # 2^30 / PH = 141.3
+
+
+def test_line_reach_n_is_half_the_degree_rounded_up():
+    assert [fm.line_reach_n(M) for M in range(1, 13)] == [1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6]
+    assert fm.LINE_REACH_MAX_P == (1 << fm.K) // P == (fm.T29 + 16) // (fm.PH + 1)  # |value| < 70 p: limb 8 inside BOX_MUL_B
+
+
+@functools.lru_cache(maxsize=None)
+def _scan(M, k, lazy, mult=None):
+    """every node the product takes, the three orientations, the pairs whose entries started lowest and highest -> (widest |line|, peak
+    |running product|, largest |final product| -- all in p --, what any chain left)"""
+    line = peak = final = 0
+    left = set()
+    for orient in ORIENTS:
+        for low in (True, False):
+            for t in range((sum(mult) if mult else M) + 1):
+                vals = fm.all_selector_values(len(mult) if mult else M, k, orient, t, lazy, low, mult)
+                assert all(-4 <= l < fm.T29 + 4 for v in vals for l in v[:8]) or fm.node_value(t) == fm.NODE_INF
+                line = max(line, max(abs(fm.value(v)) for v in vals))
+                prod, pk, lf = fm.product_chain(vals, strict=False)
+                peak, final, left = max(peak, pk), max(final, abs(fm.value(prod))), left | lf
+    return line / P, peak / P, final / P, frozenset(left)
+
+
+def _final_bounds(L, M):
+    """|prod'| <= |prod| L / LAMBDA + 1 (fe_mul's window), M - 1 times from L: L rho^(M-1) +- (1 - rho^(M-1)) / (1 - rho), rho = L / LAMBDA"""
+    rho = L / LAMBDA
+    geo = (1 - rho ** (M - 1)) / (1 - rho)
+    return L * rho ** (M - 1) - geo, L * rho ** (M - 1) + geo
+
+
+@pytest.mark.parametrize("M", range(2, 9))
+def test_every_factor_a_selector_products_of_up_to_eight_stay_inside_every_box(M):
+    """k = 0 .. 15 binds (no tail of such a product has more: K_TAIL_MAX), entries AT -k p: every line is within (n (k + 2) - 1) p < 69 p, so
+    the running product only shrinks towards LAMBDA / (LAMBDA - L) and never leaves fe_mul's second operand"""
+    n = fm.line_reach_n(M)
+    for k in range(K_TAIL_MAX + 1):
+        line, peak, final, left = _scan(M, k, k)
+        assert not left, (k, sorted(left))
+        assert not fm.line_needs_canonical(n, k + 2), "the rule of the wide tail would never fire for a product of up to eight"
+        # entries at -k p, not -(k + 1) p: one n short of the bound (node n from canonical entries: n p; the slope itself: (k + 1) p)
+        assert line <= max(n * (k + 2) - 1, k + 2) and abs(line - max(n * (k + 1) - 1, n, k + 1)) < 0.01
+        assert peak <= max(line * line / LAMBDA + 1, 2) and final <= peak
+        lo, hi = _final_bounds(line, M)
+        assert lo <= final <= hi, (k, final, lo, hi)
+    if M >= 7:  # round 15 of a proof in 15 variables, the widest the GPU tests reach: lines at 59 p, the product of 7 at 59 (59 / 70.66)^6 = 19.9 p
+        line, _, final, _ = _scan(M, 14, 14)
+        assert abs(line - 59) < 0.01 and abs(final - 59 * (59 / LAMBDA) ** (M - 1)) < 4.1
+
+
+def test_the_unremedied_chain_of_nine_to_twelve_leaves_the_second_operand_and_then_int32():
+    """WITHOUT the rule (entries lazy for all k binds): the first k at which a running product leaves BOX_MUL_B, and at which a limb 8
+    leaves int32 -- why k_tail_slices<12> makes its entries canonical (kernels.h: line_needs_canonical)"""
+    first_b, first_i32 = {}, {}
+    for M in range(9, 13):
+        for k in range(K_TAIL_MAX + 1):
+            left = _scan(M, k, k)[3]
+            assert "mul_a" not in left
+            if "mul_b" in left:
+                first_b.setdefault(M, k)
+            if "int32" in left:
+                first_i32.setdefault(M, k)
+    assert first_b == {9: 14, 10: 14, 11: 11, 12: 11}
+    assert first_i32 == {11: 13, 12: 13}
+    assert abs(_scan(12, 14, 14)[0] - 89) < 0.01 and _scan(12, 14, 14)[1] > 1000  # lines at -89 p, a running product beyond 1000 p
+
+
+@pytest.mark.parametrize("M", range(9, 13))
+def test_with_the_rule_products_of_nine_to_twelve_stay_inside_every_box(M):
+    """the entries made canonical by the bind that would take n (lazy binds + 2) beyond 70: lazy <= 12 for M = 9, 10 and <= 9 for M = 11, 12"""
+    n = fm.line_reach_n(M)
+    depth = [fm.lazy_binds_under_the_rule(M, k) for k in range(17)]
+    assert max(depth) == (12 if n == 5 else 9) and depth[:max(depth) + 2] == list(range(max(depth) + 1)) + [0]
+    for k in range(17):
+        line, peak, final, left = _scan(M, k, depth[k])
+        assert not left, (k, sorted(left))
+        assert line <= n * (depth[k] + 2) - 1 <= fm.LINE_REACH_MAX_P - 1 and peak < line + 1
+        assert final <= _final_bounds(line, M)[1]
+    if M == 12:  # the exponent loop of the same chain (tests/test_gpu_lazy_entries.py: the multiplicity shapes at sel = 14)
+        for mult in ((12,), (4, 4, 4)):
+            assert not _scan(M, 14, depth[14], mult)[3] and _scan(M, 14, 14, mult)[3] == {"mul_b", "int32"}
+
+
+def test_the_lazy_sum_of_all_selector_products_stays_inside_the_top_limb():
+    """worst_p + j counts a product at (k + 2) p; the all-selector products exceed that late in a tail (21.5 p against 16 for a product of 7
+    after 14 binds).  One accumulator adds at most the round's pairs: 2^14 >> (k - 1) in a tail of 2^14 pairs that binds on the way in, 2^14 >> k
+    in one that does not.  Where lazy_sum_needs_reduce(pairs, k + 2) does not fire, pairs x the largest product must fit kLazySumMaxP p.
+    The model's worst ratio: 0.85 (M = 9 after 12 binds, the last before its entries are made canonical: 8 pairs x 29.9 p = 239 p of 282)"""
+    worst = (0,)
+    for M in range(2, 13):
+        for k in range(K_TAIL_MAX + 1):
+            final = _scan(M, k, k if M <= 8 else fm.lazy_binds_under_the_rule(M, k))[2]
+            for first_bind in (0, 1):
+                pairs = (1 << 14) >> (k - first_bind) if k >= first_bind else 0
+                if pairs >= 1 and pairs * (k + 2) <= fm.LAZY_SUM_MAX_P:
+                    assert pairs <= 16
+                    worst = max(worst, (pairs * final / fm.LAZY_SUM_MAX_P, M, k, pairs))
+    assert worst[0] < 1 and worst[1:] == (9, 12, 8) and 0.84 < worst[0] < 0.86, worst

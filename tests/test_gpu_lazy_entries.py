@@ -72,13 +72,20 @@ def test_batched_rounds_on_sinking_and_selector_tables(shapes, nv):
     """k_batch_round at the envelope's largest sizes, n = 3: instance 0 every table sinking (entries at -k p in round k + 1: the lower end,
     against worst_p = round + 1), instance 1 every table a selector with sel = 3 (every slope of round 4 at +-4 p; a product's tables
     alternate in orientation, so two slopes have opposite signs), instance 2 random tables under instance 0's challenges."""
-    nt, n = n_tables(shapes), 3
+    nt = n_tables(shapes)
     s0, r0 = fm.sinking_challenges(nv, 61000 + nv)
     s1, r1 = fm.sinking_challenges(nv, 62000 + nv)
     tabs = [[sinking(nv, s0, t) for t in range(nt)],
             [selector(nv, s1, BATCH_SEL, t, flip=t % 2 == 1) for t in range(nt)],
             [cref.synth_table(63000 + nv, t, 1 << nv) for t in range(nt)]]
     chal = np.stack([H.mont_challenges(r0), H.mont_challenges(r1), H.mont_challenges(r0)], axis=1)  # (nv, n, 4): chal[j][i] follows message j + 1
+    batched_rounds(nv, shapes, tabs, chal)
+
+
+def batched_rounds(nv, shapes, tabs, chal):
+    """all nv rounds of len(tabs) instances as one k_batch_round launch a round: every message against the oracle's, the bound tables after
+    rounds 1, 2 and nv, bind_final"""
+    n = len(tabs)
     coefs = [cref.synth_table(64000 + i, 1000, len(shapes)) for i in range(n)]
     descs = [H.desc_from(nv, shapes, tabs[i], coefs[i]) for i in range(n)]
     polys = [poly_of(nv, shapes, tabs[i], coefs[i]) for i in range(n)]
@@ -107,11 +114,27 @@ def test_batched_rounds_on_sinking_and_selector_tables(shapes, nv):
         assert batch_plans() == (b0 + nv, s0_), "every round must be one launch of k_batch_round"
 
 
+EIGHT = [[0, 1, 2, 3, 4, 5, 6, 7]]
+
+
+@pytest.mark.parametrize("shapes", [SIX, EIGHT], ids=["six-nv8", "eight-nv8"])
+def test_batched_rounds_with_every_table_a_selector_in_the_last_round(shapes):
+    """k_batch_round where its envelope ends (products of six and of eight at nv = 8), EVERY table a selector at sel = 7: the last round's pair
+    is (entry at -7 p, p - 1) in every factor at once -- instance 0 all up, instance 1 all down, so no factor of a product is near 0.  fe_line
+    out to nodes 3 / -2 (-23 p) and 4 / -3 (-31 p) in all six / eight factors, the running product at 31 * 31 / 70.66 = 13.6 p (the model:
+    tests/test_fe_model_host.py, k = 7)"""
+    nv, sel, nt = 8, 7, n_tables(shapes)
+    s0, r0 = fm.sinking_challenges(nv, 61500 + nt)
+    s1, r1 = fm.sinking_challenges(nv, 62500 + nt)
+    tabs = [[selector(nv, s0, sel, t, flip=False) for t in range(nt)], [selector(nv, s1, sel, t, flip=True) for t in range(nt)]]
+    batched_rounds(nv, shapes, tabs, np.stack([H.mont_challenges(r0), H.mont_challenges(r1)], axis=1))
+
+
 # ---- sc_prove_round: lazy big rounds, then the resident k_tail_slices ---------------------------------------------------------------------------
 def interactive(nv, shapes, tabs, chal, lazy_big_binds, resident="resident.slices"):
     """all nv rounds of one interactive prover over device tables against the oracle's (computed first: the resident kernel waits for its
     challenges), then the bound tables; the counters: `lazy_big_binds` big rounds stored their bound tables in the internal format, and the
-    rest of the proof ran in ONE resident kernel of the given kind"""
+    rest of the proof ran in ONE resident kernel of the given kind (None: in no resident kernel at all)"""
     coefs = cref.synth_table(65000 + nv, 1000, len(shapes))
     t0 = time.perf_counter()
     op = cref.Prover(H.desc_from(nv, shapes, tabs, coefs), threads=cref.max_threads())
@@ -135,6 +158,9 @@ def interactive(nv, shapes, tabs, chal, lazy_big_binds, resident="resident.slice
         assert np.array_equal(t.evaluations, otabs[u]), f"bound table {u} after the last round"
     st.close()
     assert moved.get("big.store_f29", 0) == lazy_big_binds, "the big rounds must bind lazily, in the internal format"
+    if resident is None:
+        assert moved.get("resident.slices", 0) == 0 and moved.get("resident.rounds", 0) == 0, "no kernel may wait for the host"
+        return moved
     other = "resident.rounds" if resident == "resident.slices" else "resident.slices"
     assert moved.get(resident, 0) == 1 and moved.get(other, 0) == 0, f"the tail must run as one {resident} kernel"
     return moved
@@ -181,6 +207,59 @@ def test_a_product_of_five_through_the_wide_tree_with_selector_slopes_in_its_las
     tabs = [sinking(nv, s, 0), selector(nv, s, 2, 1, True), sinking(nv, s, 3), selector(nv, s, 3, 2, False), selector(nv, s, 2, 4, False)]
     moved = interactive(nv, shapes, tabs, H.mont_challenges(r), lazy_big_binds=2)
     assert moved.get("big.wide", 0) > 0, "the big rounds must run in the tree kernel for five to eight multiplicands"
+
+
+# ---- every factor of a product at its range end at once, through the resident k_tail_slices ------------------------------------------------------
+ALL_NV = 15  # the tail takes the proof from round 1 (2^14 pairs): entries at -k p after k binds, k = 14 in the last round -- the smallest such shape
+ORIENT = {"up": lambda t: False, "down": lambda t: True, "alt": lambda t: t % 2 == 1}
+
+
+def all_selectors(nv, nt, sel, orient):
+    """nt selector tables at the same sel in the given orientation, and the challenges that sink them"""
+    s, r = fm.sinking_challenges(nv, 72000 + 100 * nv + sel)
+    return [selector(nv, s, sel, t, ORIENT[orient](t)) for t in range(nt)], H.mont_challenges(r)
+
+
+@pytest.mark.parametrize("orient", ["up", "down", "alt"])
+@pytest.mark.parametrize("sel", [10, 13, 14])
+@pytest.mark.parametrize("M", [3, 4, 6, 8, 9, 10, 11, 12])
+def test_every_factor_a_selector_through_the_resident_slices(M, sel, orient):
+    """one product of M distinct tables at nv = 15, every table a selector at the same sel: in round sel + 1 every factor's pair is (entry at
+    -sel p, p - 1), or the other way round -- no factor near 0.  sel = 10: 16 pairs, the largest sum lazy_sum_needs_reduce leaves lazy; sel = 13
+    and 14: the widest lines, -(n (sel + 1) - 1) p at the outermost node, n = ceil(M / 2) -- 59 p for M = 8 and, were the entries left lazy,
+    89 p for M = 12, where a chain of fe_muls grows by 89 / 70.66 a factor and leaves int32 (tests/test_fe_model_host.py); k_tail_slices<12>
+    makes its entries canonical in the bind that could put a line beyond 70 p (kernels.h: line_needs_canonical)"""
+    tabs, chal = all_selectors(ALL_NV, M, sel, orient)
+    interactive(ALL_NV, [list(range(M))], tabs, chal, lazy_big_binds=0)  # (k_tail_slices<12> from nine multiplicands on: launch_tail_slices)
+
+
+@pytest.mark.parametrize("shapes", [[[0] * 12], [[0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2]]], ids=["0^12", "0^4-1^4-2^4"])
+def test_powers_of_selectors_through_the_resident_slices(shapes):
+    """the exponent loop of the same chain: twelve multiplicands from one table and from three, sel = 14"""
+    tabs, chal = all_selectors(ALL_NV, n_tables(shapes), 14, "up")
+    interactive(ALL_NV, shapes, tabs, chal, lazy_big_binds=0)
+
+
+def test_a_product_of_twelve_selectors_beside_a_product_of_two():
+    """[[0 .. 11], [0, 1]] at sel = 13: two products under kSlots = 12, 13 + 3 combinations sharing a block's lanes"""
+    tabs, chal = all_selectors(ALL_NV, 12, 13, "down")
+    interactive(ALL_NV, [list(range(12)), [0, 1]], tabs, chal, lazy_big_binds=0)
+
+
+def test_a_product_of_twelve_selectors_at_the_smallest_nv_that_overflows():
+    """nv = 14, sel = 13: the last round of a tail of 2^13 pairs -- 13 lazy binds put the line at -83 p and limb 8 of the running product
+    outside int32 in the model"""
+    tabs, chal = all_selectors(14, 12, 13, "up")
+    interactive(14, [list(range(12))], tabs, chal, lazy_big_binds=0)
+
+
+@pytest.mark.parametrize("policy,resident", [({"tail_slices": 0}, "resident.rounds"), ({"pipeline": 0}, None)], ids=["tail_rounds", "launches"])
+def test_a_product_of_twelve_selectors_on_the_paths_that_rebuild_canonical_tables(policy, resident):
+    """M = 12, sel = 14 again where no entry is ever lazy: k_tail_rounds (tables through memory, canonical) and plain launches (no kernel
+    waits for the host).  The same inputs and the same oracle messages as the resident-slices case: what tells a wrong kernel from a wrong test"""
+    tabs, chal = all_selectors(ALL_NV, 12, 14, "up")
+    with _lib.policy(**policy):
+        interactive(ALL_NV, [list(range(12))], tabs, chal, lazy_big_binds=0, resident=resident)
 
 
 # ---- whole-table consumers at the sinking point ------------------------------------------------------------------------------------------------

@@ -159,8 +159,10 @@ def wide(nv, ms, reps=7):
     return r
 
 
-if "--only-wide12" in sys.argv:  # for rocprofv3 runs of one product of twelve alone
-    print(json.dumps({"one_product_of_12": wide(20, [12])}, indent=1))
+_w12 = [a for a in sys.argv if a == "--only-wide12" or a.startswith("--only-wide12=")]
+if _w12:  # for rocprofv3 runs of one product of twelve alone; --only-wide12=NV[,REPS]: at another size (nv = 16: the big rounds end at 2^14 pairs, most of the proof is k_tail_slices<12>)
+    _nv, _, _reps = _w12[0].partition("=")[2].partition(",")
+    print(json.dumps({"one_product_of_12": wide(int(_nv or 20), [12], reps=int(_reps or 7))}, indent=1))
     sys.exit(0)
 if "--wide" in sys.argv:  # the M >= 5 paths, timed
     nvw = 20
