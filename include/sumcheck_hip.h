@@ -478,6 +478,9 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
  *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, sc_batch_prover_init: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
  *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
+ *   "lag_single" (2)         big rounds that a table named only by single-table products skips after round 1 (0: none .. 4): its products' messages come
+ *                            from class sums of the table, and one pass binds the table with every challenge it missed before the next round
+ *                            (or anything else) reads it.  The proof does not depend on the value.
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);
 SC_API int sc_get_policy(const char *key, int64_t *value);

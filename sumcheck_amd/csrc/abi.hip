@@ -114,6 +114,7 @@ void prover_destroy(sc_prover *p) {
     if (p->own_stream) (void)hipStreamSynchronize(p->own_stream);
     if (p->arena) (void)hipFree(p->arena);
     if (p->d_partials) (void)hipFree(p->d_partials);
+    if (p->d_lag_area) (void)hipFree(p->d_lag_area);
     if (p->d_partials2) (void)hipFree(p->d_partials2);
     if (p->d_fin_counters) (void)hipFree(p->d_fin_counters);
     if (p->d_finprods) (void)hipFree(p->d_finprods);
@@ -574,6 +575,10 @@ int prover_bind_out(sc_prover *p, const uint64_t *r, uint64_t *d_out) {
     std::memcpy(&rr, r, 32);
     if (sch::geq_p(rr)) return sc_internal_fail(SC_ERR_BAD_ARG, "challenge is not a canonical field element");
     HIP_TRY(hipSetDevice(p->device));
+    {
+        int rc_l = materialize_lagging(p);
+        if (rc_l) return rc_l;
+    }
     p->randomness.push_back(rr);
     const uint64_t n_out = 1ULL << (p->nv - p->round);
     for (uint32_t u0 = 0; u0 < p->U; u0 += (uint32_t)scd::kMaxSmallTables) { // one launch per 32 tables
@@ -618,6 +623,10 @@ extern "C" int sc_prover_state(sc_prover *p, uint64_t *randomness, uint32_t *n_r
     if (tables_out) {
         if (p->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "tables were consumed by sc_prover_bind_final");
         HIP_TRY(hipSetDevice(p->device));
+        {
+            int rc_l = materialize_lagging(p); // (the exported tables are the bound ones, whatever the rounds let lag)
+            if (rc_l) return rc_l;
+        }
         const uint32_t bound = p->round > 0 ? p->round - 1 : 0;
         const uint64_t n = 1ULL << (p->nv - bound);
         if (p->streamed && p->round < 2) { // nothing bound yet: the tables are the caller's host arrays
@@ -772,6 +781,7 @@ extern "C" int sc_prover_reset(sc_prover *p, const uint64_t *const *tables_or_nu
     p->sums_round = -1;
     p->exhausted = false;
     p->randomness.clear();
+    lag_clear(p); // (the tables were replaced or rewound: nothing to catch up on)
     return SC_OK;
 }
 
@@ -784,7 +794,7 @@ extern "C" int sc_prover_reset(sc_prover *p, const uint64_t *const *tables_or_nu
 //                                   (descriptor's matrix) x table(r_last); nothing visits the host.  The next reset restores the matrices.
 hipStream_t sc_internal_prover_stream(sc_prover *p) { return p->stream; }
 const void *sc_internal_bound_table(sc_prover *p, uint32_t u) {
-    if (!p || u >= p->U || p->round != p->nv || p->exhausted || p->tabs[u].cur_f29 || p->res.active) return nullptr;
+    if (!p || u >= p->U || p->round != p->nv || p->exhausted || p->tabs[u].cur_f29 || p->tabs[u].lag || p->res.active) return nullptr;
     return p->tabs[u].cur;
 }
 int sc_internal_scale_by_bound_table(sc_prover *p, const void *table, const sch::Fr &r_last) {
@@ -1126,7 +1136,7 @@ struct PolicyDef {
 constexpr PolicyDef kPolicyDefs[scd::kPolCount] = {
     {"pipeline", 1, 0, 1},     {"resident", 1, 0, 1},          {"tail_slices", 1, 0, 1}, {"vram_mailbox", 1, 0, 1},           {"wide_tree", 1, 0, 1},
     {"rccl_direct", 1, 0, 1},  {"shard_gather_log2", 15, 1, 15}, {"gkr_direct", 1, 0, 1},  {"wait_spins", 1 << 22, 1, 0xffffffffLL}, {"tail", 1, 0, 1},
-    {"staged_init", 1, 0, 1},  {"batch", 1, 0, 2},
+    {"staged_init", 1, 0, 1},  {"batch", 1, 0, 2},        {"lag_single", 2, 0, scd::kLagMaxSkip},
 };
 struct PolicyTable {
     std::atomic<int64_t> v[scd::kPolCount];
@@ -1149,7 +1159,7 @@ PolicyTable &policy_table() {
 std::atomic<uint64_t> g_plan[scd::kPlanCount];
 constexpr const char *kPlanNames[scd::kPlanCount] = {
     "big.merged.round1", "big.merged.bind_chain", "big.merged.bind", "big.claim_identity", "big.store_f29", "big.store_canonical", "big.per_product_tree",
-    "big.wide", "big.wide16", "big.generic", "big.node_by_node", "big.bind_pass", "big.streamed", "big.staged_round1", "finalize.multi_block", "finalize.one_block", "finalize.no_lds",
+    "big.wide", "big.wide16", "big.generic", "big.node_by_node", "big.bind_pass", "big.streamed", "big.staged_round1", "big.lag_class_round", "big.lag_catch_up", "big.lag_materialize", "finalize.multi_block", "finalize.one_block", "finalize.no_lds",
     "small.launched", "small.combos_table", "small.ptrs", "small.pipelined", "tail.slices8", "tail.slices12", "tail.rounds", "resident.slices",
     "resident.rounds", "sharded.rccl_direct", "sharded.rccl_publish", "sharded.host", "sharded.p2p", "sharded.gather_tail", "gkr.bucketed_grouped",
     "gkr.bucketed_counted", "gkr.list_form", "gkr.coeff_from_bound_table", "gkr.sharded", "batch.rounds_one_block", "batch.rounds_serial", "fold_multi",

@@ -172,9 +172,9 @@ __device__ __forceinline__ uint4 f29_ld(const uint4 *p) { return *p; }
 __device__ __forceinline__ void f29_st(uint4 *p, const uint32_t a, const uint32_t b, const uint32_t c, const uint32_t d) { *p = make_uint4(a, b, c, d); }
 #endif
 __device__ __forceinline__ uint64_t f29_chunk(uint64_t entry, int half) { // index in uint4 units
-    const uint64_t q = entry >> 1; // pair
-    const uint64_t col = ((q & 63) >> 1) | ((q & 1) << 5); // even pairs in columns 0..31, odd pairs in 32..63
-    return (entry >> 7) * 256 + (uint64_t)(2 * (int)(entry & 1) + half) * 64 + col;
+    // pair q = entry >> 1 at column ((q & 63) >> 1) | ((q & 1) << 5): even pairs in columns 0..31, odd pairs in 32..63.  The arithmetic is
+    // lag_index.hpp's constexpr function (host-testable: tests/cpp/test_lag_index.cpp), so k_fix_deep's stores and these loads cannot part
+    return lag_f29_chunk(entry, half);
 }
 __device__ __forceinline__ Fe fe_load_f29(const uint4 *main, uint64_t entry) {
     const uint4 a = f29_ld(main + f29_chunk(entry, 0)), b = f29_ld(main + f29_chunk(entry, 1));

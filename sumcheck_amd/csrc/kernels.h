@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lag_index.hpp"
+
 namespace scd {
 
 constexpr int kBlock = 256;    // 4 wavefronts of 64
@@ -69,7 +71,12 @@ constexpr int kRoundTreeGrid = 768; // k_round_tree holds 3 blocks per CU (156 V
 struct TreeProd {
     Slot slot[4];
     uint32_t M;
-    uint32_t pad;
+    // Lagging single-table product (lag_index.hpp; lag_m = 0: an ordinary row).  slot[0].dst is the product's class work area.
+    //   round 1: besides its two node partials the block leaves its 2^lag_m class partials there;
+    //   rounds 2 .. lag_m (lag_done + 2 = the round): the row binds the class table, lag_done binds so far, and never touches the table itself --
+    //   block 0 does the work, the row's other blocks store zero partials.  lag_grid: blocks per row of the round-1 launch.
+    uint8_t lag_m, lag_done;
+    uint16_t lag_grid;
     uint64_t partial_off; // in field elements, as in FinProd
 };
 // the round's finalize step inside k_round_tree (kernels.hip): what k_finalize would have been given
@@ -93,6 +100,7 @@ struct RoundArgs {
     // k_round1_tree_split only: this launch fills blocks [part_block0, part_block0 + gridDim.x) of node rows that are part_stride blocks long
     // (a staged sc_prover_init runs round 1 chunk by chunk under the host-to-device copy, one finalize over all of it); 0 / 0: the whole rows
     uint32_t part_stride, part_block0;
+    uint32_t binding; // 1: a binding round, whatever its slots' modes (a round whose every table was bound by k_fix_deep just before has mode 0 throughout)
 };
 
 // static per-product record for the finalize kernel (device memory)
@@ -354,6 +362,7 @@ enum PolicyKey {
     kPolTail,             // "tail"               1: the persistent tail kernels; 0: latency-bound rounds as pipelined launches (what sharded RCCL rounds use)
     kPolStagedInit,       // "staged_init"        1: sc_prover_init over HOST tables copies them in chunks and computes round 1 under the copy (shapes of the merged big-round kernel, >= 2^18 entries)
     kPolBatch,            // "batch"              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
+    kPolLagSingle,        // "lag_single"         tables that only single-table products name skip this many big rounds after the first (0: off .. 4): class sums stand in for them (lag_index.hpp)
     kPolCount
 };
 int64_t policy(int key);
@@ -376,6 +385,9 @@ enum Plan {
     kPlanBigBindPass,         // k_fix_multi up front (lists with products beyond kMaxFusedM)
     kPlanBigStreamed,         // rounds 1-2 of a streamed handle, chunk by chunk
     kPlanBigStagedRound1,     // round 1 computed inside sc_prover_init / sc_prover_reset, chunk by chunk under the host-to-device copy
+    kPlanBigLagClassRound,    // a merged big round in which a lagging product's row bound its class table instead of the table
+    kPlanBigLagCatchUp,       // k_fix_deep in front of the merged round that reads a lagging table again
+    kPlanBigLagMaterialize,   // k_fix_deep because something else needed the table (materialize_lagging)
     kPlanFinalizeMultiBlock,  // k_finalize_mb
     kPlanFinalizeOneBlock,    // k_finalize (more products than a launch's arguments describe: metadata from device memory)
     kPlanFinalizeNoLds,       // k_finalize without LDS staging (node sums beyond 48 KB)
@@ -525,6 +537,17 @@ hipError_t launch_gather_to_tables(const uint4 *recv, uint4 *tabs, uint32_t G, u
 // acc (+)= in (D elements; first: acc = in); last: the sum also goes to d_out / the host-mapped page with its sequence flag (D <= 64)
 hipError_t launch_msg_accumulate(const FrHost *in, FrHost *acc, int D, bool first, bool last, FrHost *d_out, uint64_t *d_out_wide, FrHost *h_out_mapped,
                                  uint32_t *h_flag_mapped, uint32_t seq, hipStream_t stream);
+// A lagging table's catch-up (kernels_lag.hip: k_fix_deep): the canonical table `src` of n_in entries bound `levels` (1 .. kLagMaxLevels)
+// times in one pass, r[0] first, into `dst` (n_in >> levels entries; F29 when dst_f29); every level's result takes the form a big round
+// would have stored it in, so `dst` is bit for bit the table `levels` big rounds would have left.  n_in >= 256 entries, a power of two.
+struct DeepArgs {
+    BindConst r[kLagMaxLevels];
+    const uint4 *src;
+    uint4 *dst;
+    uint64_t n_groups; // n_in / 4
+    uint32_t levels;
+};
+hipError_t launch_fix_deep(const DeepArgs &args, bool dst_f29, hipStream_t stream);
 // F29 table -> canonical reference layout (state export)
 hipError_t launch_f29_to_sat(const uint4 *src, uint4 *dst, uint64_t n, hipStream_t stream);
 hipError_t launch_fr_elementwise(int op, const uint4 *a, const uint4 *b, const FrHost &u, uint4 *out, uint64_t n, hipStream_t stream);

@@ -175,7 +175,8 @@ __global__ __launch_bounds__(kBlock) void k_prod_round_fe(const ProdArgs A, cons
 // polynomial at the challenge, product by product: ClaimArgs in kernels.h); binding rounds only
 template <int M, bool kR1 = false, bool kChain = kChainDefault, bool kSkip1 = false>
 __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBindLds], const uint64_t n_pairs, uint4 *__restrict__ row, uint32_t (*sm)[8],
-                                          int32_t *lacc, const uint32_t part_stride = 0) {
+                                          int32_t *lacc, const uint32_t part_stride = 0, uint4 *__restrict__ lag_area = nullptr, const int lag_m = 0) {
+    // (lag_area, lag_m: round 1 of a lagging single-table product -- the block also leaves its 2^lag_m class partials, see the epilogue)
     // (part_stride: blocks per node row of the partial sums when this launch fills only a SECTION of them -- round 1 of a staged
     // sc_prover_init, chunk by chunk under the host-to-device copy; 0: this launch's own grid)
     const uint64_t pstride = part_stride ? part_stride : gridDim.x;
@@ -414,6 +415,11 @@ __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBin
         for (int l = 0; l < 9; ++l) a.l[l] = my[(9 * t + l) * kBlock];
         s[t] = fe_to_fr(a);
     }
+    [[maybe_unused]] Fr cls[2]; // (round 1 of a lagging product: the lane's two sums once more, for the class partials below)
+    if constexpr (M == 1 && kR1) {
+        cls[0] = s[0];
+        cls[1] = s[1];
+    }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
@@ -444,7 +450,43 @@ __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBin
         fr_store(row + 2 * ((uint64_t)t * pstride), acc);
     }
     __syncthreads(); // (a block that walks several products -- the experiments build's k_round_tree -- reuses the LDS at once)
+    // Round 1 of a lagging single-table product (lag_index.hpp): the same two sums per lane, reduced per CLASS instead of per node.  A
+    // lane's lo entries are all in class 2 (tid mod 2^(m-1)) and its hi entries in that class + 1, so the shuffle tree stops at offset
+    // 2^(m-1) and the wavefronts' class sums cross through LDS like the node sums above.  Partials: class-major, lag_area[class * grid + block].
+    if constexpr (M == 1 && kR1) {
+        if (lag_m != 0) {
+            const int lanes = (int)lag_class_lanes(lag_m);
+            for (int off = 32; off >= lanes; off >>= 1) {
+                cls[0] = fr_add(cls[0], fr_shfl_down(cls[0], off));
+                cls[1] = fr_add(cls[1], fr_shfl_down(cls[1], off));
+            }
+            if (lane < lanes) { // x: [wave][class][8]
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    x[((wave << lag_m) + (int)lag_class_lo(lane, lag_m)) * 8 + i] = cls[0].v[i];
+                    x[((wave << lag_m) + (int)lag_class_hi(lane, lag_m)) * 8 + i] = cls[1].v[i];
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < (1 << lag_m)) {
+                const int c = threadIdx.x;
+                Fr acc;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc.v[i] = x[c * 8 + i];
+                for (int w = 1; w < kBlock / 64; ++w) {
+                    Fr o;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) o.v[i] = x[(((w << lag_m) + c)) * 8 + i];
+                    acc = fr_add(acc, o);
+                }
+                fr_store(lag_area + 2 * ((uint64_t)c * gridDim.x + blockIdx.x), acc);
+            }
+            __syncthreads();
+        }
+    }
 #else
+    // (A/B build of the serial epilogue: it has no class partials, so single-table products must not lag -- launch_round_tree refuses
+    // the launch that would start it, see there)
 #pragma unroll
     for (int t = 0; t <= M; ++t) {
         if (kSkip1 && t == 1) continue;
@@ -677,17 +719,81 @@ __global__ __launch_bounds__(kBlock, 3) void k_round1_tree_split(const RoundArgs
     constexpr bool kC1 = true;
 #endif
     switch (T.M) {
-    case 1: tree_pass<1, true, kC1>(T.slot, rt, n_pairs, row, sm, lacc, R.part_stride); break;
+    case 1: tree_pass<1, true, kC1>(T.slot, rt, n_pairs, row, sm, lacc, R.part_stride, T.slot[0].dst, (int)T.lag_m); break;
     case 2: tree_pass<2, true, kC1>(T.slot, rt, n_pairs, row, sm, lacc, R.part_stride); break;
     case 3: tree_pass<3, true, kC1>(T.slot, rt, n_pairs, row, sm, lacc, R.part_stride); break;
     default: tree_pass<4, true, kC1>(T.slot, rt, n_pairs, row, sm, lacc, R.part_stride); break;
+    }
+}
+// A lagging single-table product's row in the rounds its table skips (lag_index.hpp): the product's message is the sum of the even and of
+// the odd entries of its table, and the class table -- the table with its high variables summed out, 2^m entries -- gives the same two
+// sums when it is bound in the table's place.  Block 0 of the row does that: in the first skipped round it adds up round 1's class
+// partials, then binds the class table with this round's constants, keeps the bound table for the next round (ping-pong behind the
+// partials) and writes the two sums as the row's partials of block 0.  The row's other blocks store zeros, so the finalize step, the
+// claim identity and the node sums kept for the next round see this product like any other.  M = 1: no 2^(-5(M-1)) to carry.
+template <bool kSkip1>
+__device__ __forceinline__ void class_row(const TreeProd &T, const int32_t (&rt)[kBindLds], uint4 *__restrict__ row, uint32_t *x) {
+    if (blockIdx.x != 0) {
+        if (threadIdx.x == 0) {
+            fr_store(row, fr_zero());
+            if (!kSkip1) fr_store(row + 2 * (uint64_t)gridDim.x, fr_zero());
+        }
+        return;
+    }
+    const int m = (int)T.lag_m, done = (int)T.lag_done;
+    const uint32_t G = T.lag_grid;
+    uint4 *area = T.slot[0].dst;
+    uint4 *tabs = area + 2 * lag_area_partials(m, G); // two class tables of 2^m entries
+    const int n_cur = 1 << (m - done);                 // entries of the class table as the previous round left it
+    if (done == 0) { // 256 >> m lanes per class add up the grid's partials, a shuffle tree folds them (m >= 2: a class's lanes share a wavefront)
+        const int per = kBlock >> m, c = (int)threadIdx.x / per, sub = (int)threadIdx.x % per;
+        Fr acc = fr_zero();
+        for (uint32_t b = (uint32_t)sub; b < G; b += (uint32_t)per) acc = fr_add(acc, fr_load(area + 2 * ((uint64_t)c * G + b)));
+        for (int off = per >> 1; off >= 1; off >>= 1) acc = fr_add(acc, fr_shfl_down(acc, off));
+        if (sub == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) x[c * 8 + i] = acc.v[i];
+        }
+    } else if ((int)threadIdx.x < n_cur) {
+        const Fr v = fr_load(tabs + 2 * ((uint64_t)((done & 1) << m) + threadIdx.x));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[threadIdx.x * 8 + i] = v.v[i];
+    }
+    __syncthreads();
+    uint32_t *y = x + 8 * kLagMaxClasses; // the bound class table
+    if ((int)threadIdx.x < n_cur / 2) {
+        Fr lo, hi;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            lo.v[i] = x[(2 * threadIdx.x) * 8 + i];
+            hi.v[i] = x[(2 * threadIdx.x + 1) * 8 + i];
+        }
+        const Fe l = fe_from_fr(lo), h = fe_from_fr(hi);
+        const Fr v = fe_to_fr(fe_add(l, fe_mul_bind<kChainDefault>(fe_sub(h, l), rt)));
+        fr_store(tabs + 2 * ((uint64_t)(((done + 1) & 1) << m) + threadIdx.x), v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[threadIdx.x * 8 + i] = v.v[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && !(kSkip1 && threadIdx.x == 1)) { // node 0: the even entries, node 1: the odd ones (at most 16 each)
+        Fr acc = fr_zero();
+        for (int e = (int)threadIdx.x; e < n_cur / 2; e += 2) {
+            Fr o;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o.v[i] = y[e * 8 + i];
+            acc = fr_add(acc, o);
+        }
+        fr_store(row + 2 * ((uint64_t)threadIdx.x * gridDim.x), acc);
     }
 }
 // kChain: single-chain multiply-adds (fe_device.hpp) -- the instantiation for a proof's first binding round, whose sources are canonical.
 // (Round 4 measured instantiations for launches whose products all have at most three multiplicands -- four nodes of running sums, one
 // pair per iteration, 113-116 registers, FOUR resident blocks per CU -- on config 4's shapes: no change beyond box noise,
 // profiles/r4c_config4_m3_occupancy_ab.txt; those rounds already move their real bytes at 5.2-5.3 TB/s.  Not kept.)
-template <bool kChain, bool kSkip1>
+// kLag: the instantiation for the rounds in which some row is a class row.  Every other round runs the instantiation without that branch:
+// with it the register allocation of the whole kernel moves (163-165 VGPRs and no scratch instead of 168 and 20 / 28 bytes), and the
+// shapes that have nothing to gain from lagging measured 0.3-1 % slower for it (config 4: profiles/lag_bench_configs.json).
+template <bool kChain, bool kSkip1, bool kLag = false>
 __global__ __launch_bounds__(kBlock, 3) void k_round_tree_split(const RoundArgs R, const BindConst r, const uint64_t n_pairs, uint4 *__restrict__ partials) {
     __shared__ uint32_t sm[kBlock / 64][8];
     __shared__ int32_t rt[kBindLds];
@@ -695,6 +801,12 @@ __global__ __launch_bounds__(kBlock, 3) void k_round_tree_split(const RoundArgs 
     bind_consts_to_lds(r, rt);
     const TreeProd &T = R.prod[blockIdx.y];
     uint4 *row = partials + 2 * (T.partial_off + (uint64_t)blockIdx.x);
+    if constexpr (kLag) {
+        if (T.lag_m != 0) { // (block-uniform)
+            class_row<kSkip1>(T, rt, row, reinterpret_cast<uint32_t *>(lacc));
+            return;
+        }
+    }
     switch (T.M) {
     case 1: tree_pass<1, false, kChain, kSkip1>(T.slot, rt, n_pairs, row, sm, lacc); break;
     case 2: tree_pass<2, false, kChain, kSkip1>(T.slot, rt, n_pairs, row, sm, lacc); break;
@@ -789,7 +901,7 @@ hipError_t launch_round_tree(const RoundArgs &args, const BindConst &r32, uint64
     }();
     extra_lds = env_lds;
 #endif
-    bool round1 = args.fin.enabled == 0; // every factor read in place from a canonical table: the round-1 instantiation
+    bool round1 = args.fin.enabled == 0 && args.binding == 0; // every factor read in place from a canonical table: the round-1 instantiation
     for (int q = 0; q < args.n_prod && round1; ++q)
         for (uint32_t f = 0; f < args.prod[q].M; ++f) round1 = round1 && args.prod[q].slot[f].mode == 0 && args.prod[q].slot[f].src_f29 == 0;
 #ifdef SC_EXPERIMENTS
@@ -811,6 +923,10 @@ hipError_t launch_round_tree(const RoundArgs &args, const BindConst &r32, uint64
 #endif
     for (int q = 0; q < args.n_prod && canonical_sources; ++q)
         for (uint32_t f = 0; f < args.prod[q].M; ++f) canonical_sources = canonical_sources && args.prod[q].slot[f].src_f29 == 0;
+#ifdef SC_SERIAL_EPILOGUE // (A/B build: the serial epilogue writes no class partials)
+    for (int q = 0; q < args.n_prod; ++q)
+        if (args.prod[q].lag_m != 0) return hipErrorInvalidValue;
+#endif
     const dim3 g(grid, args.n_prod), b(kBlock);
     uint4 *const part = (uint4 *)d_partials;
     plan_hit(round1 ? kPlanBigMergedRound1 : canonical_sources ? kPlanBigMergedBindChain : kPlanBigMergedBind);
@@ -818,12 +934,20 @@ hipError_t launch_round_tree(const RoundArgs &args, const BindConst &r32, uint64
     if (round1) {
         if (skip1) return hipErrorInvalidValue; // (round 1 has no previous round)
         hipLaunchKernelGGL(k_round1_tree_split, g, b, 0, stream, args, n_pairs, part);
-    } else if (canonical_sources) {
-        if (skip1) hipLaunchKernelGGL((k_round_tree_split<true, true>), g, b, 0, stream, args, r32, n_pairs, part);
-        else hipLaunchKernelGGL((k_round_tree_split<true, false>), g, b, 0, stream, args, r32, n_pairs, part);
     } else {
-        if (skip1) hipLaunchKernelGGL((k_round_tree_split<kChainDefault, true>), g, b, 0, stream, args, r32, n_pairs, part);
-        else hipLaunchKernelGGL((k_round_tree_split<kChainDefault, false>), g, b, 0, stream, args, r32, n_pairs, part);
+        bool lag = false; // a class row among the round's rows (never in round 1: its rows carry lag_m for the epilogue only)
+        for (int q = 0; q < args.n_prod; ++q) lag = lag || args.prod[q].lag_m != 0;
+        const int sel = (canonical_sources ? 4 : 0) | (skip1 ? 2 : 0) | (lag ? 1 : 0);
+        switch (sel) {
+        case 7: hipLaunchKernelGGL((k_round_tree_split<true, true, true>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        case 6: hipLaunchKernelGGL((k_round_tree_split<true, true, false>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        case 5: hipLaunchKernelGGL((k_round_tree_split<true, false, true>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        case 4: hipLaunchKernelGGL((k_round_tree_split<true, false, false>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        case 3: hipLaunchKernelGGL((k_round_tree_split<kChainDefault, true, true>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        case 2: hipLaunchKernelGGL((k_round_tree_split<kChainDefault, true, false>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        case 1: hipLaunchKernelGGL((k_round_tree_split<kChainDefault, false, true>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        default: hipLaunchKernelGGL((k_round_tree_split<kChainDefault, false, false>), g, b, 0, stream, args, r32, n_pairs, part); break;
+        }
     }
     return hipGetLastError();
 }

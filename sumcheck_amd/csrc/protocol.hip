@@ -135,6 +135,7 @@ void abandon_deferred(sc_prover *p) {
         p->deferred_pending = false;
         (void)hipStreamSynchronize(p->stream);
         p->exhausted = true; // tables are no longer meaningful: the handle must be reset
+        lag_clear(p);
     }
 }
 
@@ -159,6 +160,38 @@ void make_bind_const(const sch::Fr &r, scd::BindConst &rc) {
             rc.R[i][k] = (int32_t)(v & 0x1fffffffULL);
         }
     }
+}
+
+// ---- lagging single-table products (lag_index.hpp): the host state and the catch-up pass ----
+void lag_clear(sc_prover *p) {
+    p->lag.active = false;
+    p->lag.j = p->lag.m = p->lag.grid = 0;
+    p->lag.r.clear();
+    for (Table &t : p->tabs) t.lag = 0;
+}
+int materialize_lagging(sc_prover *p, bool catch_up) {
+    if (!p->lag.active) return SC_OK;
+    const uint32_t k = (uint32_t)p->lag.r.size();
+    if (k > 0) { // (k = 0: round 1 alone has run, and the original IS the table)
+        if (k > (uint32_t)scd::kLagMaxLevels) return sc_internal_fail(SC_ERR_HIP, "a lagging table is %u challenges behind", k);
+        scd::DeepArgs A;
+        std::memset(&A, 0, sizeof(A));
+        for (uint32_t l = 0; l < k; ++l) make_bind_const(p->lag.r[l], A.r[l]);
+        A.levels = k;
+        A.n_groups = (1ULL << p->nv) >> 2;
+        for (Table &t : p->tabs) {
+            if (!t.lag) continue;
+            A.src = t.cur;
+            A.dst = t.buf[t.next];
+            scd::plan_hit(catch_up ? scd::kPlanBigLagCatchUp : scd::kPlanBigLagMaterialize);
+            HIP_TRY(scd::launch_fix_deep(A, p->use_f29, p->stream));
+            t.cur = t.buf[t.next];
+            t.cur_f29 = p->use_f29;
+            t.next ^= 1;
+        }
+    }
+    lag_clear(p);
+    return SC_OK;
 }
 
 // Rounds 1 and 2 of a handle whose tables stay in host memory (SC_TABLES_STREAM).  The round is the sum of its chunks: chunk c = entries
@@ -507,6 +540,28 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
         p->deferred_pending = true;
     }
 
+    // Lagging tables (lag_index.hpp): a merged big round before the catch-up round lets them lag on (its rows bind the class tables), the
+    // catch-up round binds them with everything they missed, this round's challenge included, and reads them in place; any other round
+    // first makes the tables what they would be without lagging.
+    bool lag_class = false;
+    std::vector<uint8_t> bound(p->U, 0); // 1: bound by this round; 2: bound up to and including this round's challenge by k_fix_deep
+    if (p->lag.active) {
+        const bool lag_round = bind && !deferred && !d_wide && !small_round && p->merge_rounds && !p->any_generic && !p->fused_finalize;
+        if (lag_round && p->round < p->lag.j) {
+            lag_class = true;
+            p->lag.r.push_back(r);
+        } else if (lag_round && p->round == p->lag.j) {
+            p->lag.r.push_back(r);
+            for (uint32_t u = 0; u < p->U; ++u)
+                if (p->tabs[u].lag) bound[u] = 2;
+            int rc_l = materialize_lagging(p, true);
+            if (rc_l) return rc_l;
+        } else {
+            int rc_l = materialize_lagging(p);
+            if (rc_l) return rc_l;
+        }
+    }
+
     auto bind_table = [&](uint32_t u) -> hipError_t { // stand-alone bind of table u (2*n_pairs outputs)
         Table &t = p->tabs[u];
         uint4 *dst = t.buf[t.next];
@@ -579,7 +634,6 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
         }
         bind = false;
     }
-    std::vector<uint8_t> bound(p->U, 0);
     bool ptrs_uploaded = false;
     bool finalized = false; // the merged big-round launch also produced the message
     bool skip1 = false;     // the round kernel leaves node 1 out (ClaimArgs)
@@ -621,11 +675,79 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
             old_src[u] = p->tabs[u].cur;
             old_f29[u] = p->tabs[u].cur_f29 ? 1 : 0;
         }
-        for (uint32_t k = 0; k < p->K; ++k) {
+        ra.binding = bind ? 1 : 0;
+        // Round 1 decides which tables lag: those that only products of one multiplicand name, where at least three big rounds exist and
+        // this launch is the plain merged one (not a sharded round's, not a section of a staged initialisation).  The class work areas
+        // are allocated with the first proof that needs them; a handle that cannot have them proves without lagging.
+        std::vector<uint8_t> lag_prod(p->K, 0);
+#ifdef SC_SERIAL_EPILOGUE // (A/B build: the serial epilogue of round 1 leaves no class partials behind)
+        const int64_t lag_pol = 0;
+#else
+        const int64_t lag_pol = scd::policy(scd::kPolLagSingle);
+#endif
+        if (!bind && p->round == 1 && lag_pol > 0 && split && !d_wide && !p->streamed && !p->lag.active) {
+            uint32_t last_big = 0;
+            for (uint32_t q = 1; q <= p->nv; ++q)
+                if ((1ULL << (p->nv - q)) > small_pairs) last_big = q;
+            std::vector<uint8_t> eligible(p->U, 0);
+            for (const Product &pr : p->prods)
+                for (uint32_t u : pr.tables) eligible[u] = 1;
+            for (const Product &pr : p->prods)
+                if (pr.M != 1)
+                    for (uint32_t u : pr.tables) eligible[u] = 0;
+            uint32_t n_lag = 0;
+            for (uint32_t k = 0; k < p->K; ++k)
+                if (p->prods[k].M == 1 && eligible[p->prods[k].tables[0]]) lag_prod[k] = 1, ++n_lag;
+            const size_t area = (size_t)scd::lag_area_elems(scd::kLagMaxM, scd::kMaxGrid);
+            if (n_lag > 0 && last_big >= 3 && p->lag_areas < n_lag) {
+                if (p->d_lag_area) (void)hipFree(p->d_lag_area);
+                p->d_lag_area = nullptr;
+                p->lag_areas = 0;
+                if (hipMalloc(reinterpret_cast<void **>(&p->d_lag_area), area * n_lag * 32) == hipSuccess) p->lag_areas = n_lag;
+                else (void)hipGetLastError();
+            }
+            if (n_lag > 0 && last_big >= 3 && p->lag_areas >= n_lag) {
+                p->lag.active = true;
+                p->lag.j = std::min<uint32_t>((uint32_t)lag_pol + 2, last_big);
+                p->lag.m = p->lag.j - 1;
+                p->lag.grid = (uint32_t)grid;
+                p->lag.r.clear();
+                for (uint32_t k = 0; k < p->K; ++k)
+                    if (lag_prod[k]) p->tabs[p->prods[k].tables[0]].lag = 1;
+            } else {
+                std::fill(lag_prod.begin(), lag_prod.end(), 0);
+            }
+        } else if (lag_class) {
+            scd::plan_hit(scd::kPlanBigLagClassRound);
+            for (uint32_t k = 0; k < p->K; ++k)
+                if (p->prods[k].M == 1 && p->tabs[p->prods[k].tables[0]].lag) lag_prod[k] = 1;
+        }
+        // (class rows first: block 0 of a row that is dispatched late would be the launch's last block)
+        std::vector<uint32_t> order;
+        for (int pass = 0; pass < 2; ++pass)
+            for (uint32_t k = 0; k < p->K; ++k)
+                if ((lag_class && lag_prod[k]) == (pass == 0)) order.push_back(k);
+        uint32_t lag_slot = 0; // the k-th lagging product owns the k-th work area
+        std::vector<uint32_t> area_of(p->K, 0);
+        for (uint32_t k = 0; k < p->K; ++k)
+            if (lag_prod[k]) area_of[k] = lag_slot++;
+        for (uint32_t row = 0; row < p->K; ++row) {
+            const uint32_t k = order[row];
             const Product &pr = p->prods[k];
-            scd::TreeProd &tp = ra.prod[k];
+            scd::TreeProd &tp = ra.prod[row];
             tp.M = pr.M;
             tp.partial_off = pr.partial_off;
+            if (lag_prod[k]) {
+                tp.lag_m = (uint8_t)p->lag.m;
+                tp.lag_grid = (uint16_t)p->lag.grid;
+                tp.slot[0].dst = reinterpret_cast<uint4 *>(p->d_lag_area + (size_t)area_of[k] * (size_t)scd::lag_area_elems(scd::kLagMaxM, scd::kMaxGrid));
+                if (lag_class) { // the row binds its class table; the table itself stays as it is
+                    tp.lag_done = (uint8_t)(p->lag.r.size() - 1);
+                    tp.slot[0].exp = 1;
+                    bound[pr.tables[0]] = 1;
+                    continue;
+                }
+            }
             int f = 0;
             for (size_t s = 0; s < pr.tables.size(); ++s) {
                 const uint32_t u = pr.tables[s];
@@ -635,7 +757,7 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
                     sl.exp = 1;
                     sl.src = old_src[u];
                     sl.src_f29 = old_f29[u];
-                    if (!bind) {
+                    if (!bind || bound[u] == 2) {
                         sl.mode = 0;
                     } else if (!bound[u]) {
                         sl.mode = 1;
@@ -964,7 +1086,7 @@ bool tail_possible(sc_prover *p, bool slices = false) {
 // tail_worst_p of the tables as they stand: every round so far may have bound a table in the internal format lazily
 static uint32_t tail_tables_worst_p(sc_prover *p) {
     bool f29 = false;
-    for (uint32_t u = 0; u < p->U; ++u) f29 = f29 || p->tabs[u].cur_f29;
+    for (uint32_t u = 0; u < p->U; ++u) f29 = f29 || p->tabs[u].cur_f29 || (p->tabs[u].lag && p->use_f29); // (a lagging table is caught up before the tail reads it)
     return scd::tail_worst_p(f29 ? p->round : 0);
 }
 int tail_slices_blocks_for(sc_prover *p) {
@@ -997,6 +1119,10 @@ int tail_slices_blocks_for(sc_prover *p) {
 }
 int tail_launch(sc_prover *p, uint32_t n_rounds, const sch::Fr *r_or_null, uint32_t max_spins, scd::TailArgs &A, int &grid, int slices_B = 0, bool host_mailbox_only = false) {
     const uint32_t D = p->D;
+    {
+        int rc_l = materialize_lagging(p);
+        if (rc_l) return rc_l;
+    }
     std::memset(&A, 0, sizeof(A));
     for (uint32_t u = 0; u < p->U; ++u) {
         Table &t = p->tabs[u];

@@ -100,6 +100,7 @@ struct Table {
     bool cur_f29 = false;             // `cur` is in the internal F29 format (fe_device.hpp: 32 bytes an entry, chunk-planar)
     uint4 *buf[2] = {nullptr, nullptr};
     int next = 0;                     // buffer the next bind writes to
+    uint32_t lag = 0;                 // 1: the table lags (sc_prover::lag): `cur` is still the original, the challenges in lag.r are not applied yet
 };
 
 constexpr uint32_t kResidentSpinsDefault = 256; // ~0.5 ms of polls
@@ -126,6 +127,17 @@ struct sc_prover {
     // sums are here leaves node 1 to the claim identity (kernels.h: ClaimArgs).  sums_round: the round whose complete sums are held, or -1
     FrHost *d_sums[2] = {nullptr, nullptr};
     int64_t sums_round = -1;
+    // Lagging single-table products (lag_index.hpp).  A table that only products of ONE multiplicand name skips the big rounds
+    // 2 .. j - 1: its products' rows bind a class table of 2^m entries (m = j - 1) that round 1 left in d_lag_area, and k_fix_deep binds the
+    // table itself with every challenge it missed in front of round j -- or earlier, as soon as anything but a merged big round wants
+    // the handle's tables (materialize_lagging).  While `active`, every lagging table's `cur` is the original and `r` the challenges so far.
+    struct Lag {
+        bool active = false;
+        uint32_t j = 0, m = 0, grid = 0; // catch-up round; log2 classes; blocks per row of the round-1 launch
+        std::vector<sch::Fr> r;
+    } lag;
+    FrHost *d_lag_area = nullptr;     // one class work area (lag_area_elems(kLagMaxM, kMaxGrid) elements) per lagging product
+    uint32_t lag_areas = 0;
     FrHost *d_out = nullptr;
     FrHost *h_out = nullptr;      // pinned, host-mapped: k_finalize writes the message here directly
     uint32_t *h_flag = nullptr;   // pinned, host-mapped sequence flag raised by k_finalize
@@ -236,6 +248,11 @@ enum { kStatTailLaunches = 0, kStatTailSlotBusy = 1, kStatTailSlotReclaims = 2, 
 bool wide_tree_enabled(); // products of five to eight multiplicands through kernels_wide.hip (policy "wide_tree" = 0: node by node)
 int resident_quiesce(sc_prover *p); // the interactive protocol's resident kernel leaves before anything else touches the handle
 int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool publish_to_host, bool deferred = false);
+// Every lagging table bound with the challenges it missed (k_fix_deep, on the handle's stream), buffers flipped, the class state cleared:
+// afterwards the handle's tables are what they would be without lagging.  Called, under the device gate, by everything that reads a
+// table's `cur` other than a merged big round that lets the table lag on.  catch_up: the merged round's own call (plan counter only).
+int materialize_lagging(sc_prover *p, bool catch_up = false);
+void lag_clear(sc_prover *p); // forget the state without binding (reset: the tables are replaced)
 bool staged_init_applies(const sc_prover *p);                                   // host tables, copy mode: the shape and size the staged form takes
 int staged_copy_and_round1(sc_prover *p, const uint64_t *const *host_tables); // H2D in chunks + round 1 under the copy (prover.rs:55-59 and the first prove_round)
 int await_round(sc_prover *p, uint64_t *out_evals, uint32_t want);
