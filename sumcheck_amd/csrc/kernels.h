@@ -4,12 +4,11 @@
 #include <stdint.h>
 
 #include "lag_index.hpp"
+#include "lane_sum.hpp"
 
 namespace scd {
 
-constexpr int kBlock = 256;    // 4 wavefronts of 64
 constexpr int kMaxFusedM = 8;  // products up to this many multiplicands run register-resident and fused with the bind
-constexpr int kMaxGrid = 1024; // 256 CUs x 4 resident 256-thread blocks; longer ranges are grid-strided
 constexpr int kMaxSmallTables = 32;         // table-pointer block that fits a kernel argument
 constexpr uint64_t kSmallRoundPairs = 1u << 14; // rounds at or below this many pairs are latency-bound: split finer (bind launch + one lane per
                                                 // (combination, pair)).  2^16 until round 4: at 2^16 and 2^15 pairs that pair of launches moves 2.2x
@@ -67,7 +66,6 @@ struct WideArgs16 {
 // own share of the pairs, so a round is one kernel with no launch gaps and the multiplier-bound products (M = 3, 4) of
 // some blocks overlap the HBM-bound ones (M = 1, 2) of others.  Partials keep the per-product layout k_finalize reads.
 constexpr int kMaxRoundProds = 12;
-constexpr int kRoundTreeGrid = 768; // k_round_tree holds 3 blocks per CU (156 VGPRs, 46 KB LDS): one full wave of blocks on 256 CUs
 struct TreeProd {
     Slot slot[4];
     uint32_t M;
@@ -199,12 +197,7 @@ struct TailArgs {
 // The same rounds with the tables resident in LDS (kernels_tail.hip: k_tail_slices): block g of B owns a contiguous range of every
 // table for the whole launch; one hand-over per round (its sums -> block 0) as self-validating words in `xw`.
 constexpr int kTsBlock = 256, kTsMaxBlocks = 256;
-// Lazy sums of carry-free elements (fe_carry_pass(fe_add(acc, x)), lane by lane and down a shuffle tree) never reduce limb 8: the int32
-// top limb holds floor(sum / 2^232).  A term of magnitude p puts p >> 232 = 7597479 there (7597480 for a negative one), and
-// 2^31 / 7597479 = 282.6: at most 282 terms of magnitude p may meet in one accumulator before it has to be reduced
-// (fe_from_fr(fe_to_fr(acc)), exact for every int32 top limb).  The rule, wave-uniform: terms x (worst magnitude of a term in units of p).
-constexpr uint32_t kLazySumMaxP = 282;
-__host__ __device__ constexpr bool lazy_sum_needs_reduce(uint64_t terms, uint32_t worst_p) { return terms * (uint64_t)worst_p > (uint64_t)kLazySumMaxP; }
+// (kLazySumMaxP and lazy_sum_needs_reduce, the rule of every lazy sum: lane_sum.hpp)
 // A line through two lazy entries leaves the entries' range: entries in (-(w - 1) p, p) put node x > 0 (x - 1 slopes beyond hi) and node -x
 // (x slopes beyond lo) within (n w - 1) p, n = ceil(D / 2) for a list of degree D.  A product is the chain prod = fe_mul(line, prod), and a
 // factor of magnitude L p scales the running product by L / 70.66 (2^261 = 70.66 p) and adds up to p: while L <= 69 the product stays below

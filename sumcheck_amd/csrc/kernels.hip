@@ -870,12 +870,7 @@ static int grid_cap() {
     return kMaxGrid;
 #endif
 }
-int grid_for_pairs(uint64_t n_pairs) {
-    uint64_t g = (n_pairs + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    if (g > (uint64_t)grid_cap()) g = grid_cap();
-    return (int)g;
-}
+int grid_for_pairs(uint64_t n_pairs) { return grid_blocks_for_pairs(n_pairs, grid_cap()); }
 
 hipError_t launch_sum_generic(const uint4 *const *d_cur_tables, const uint32_t *d_slot_table, const uint32_t *d_slot_exp,
                               int n_slots, int M, uint64_t n_pairs, FrHost *d_partials, int grid, hipStream_t stream) {

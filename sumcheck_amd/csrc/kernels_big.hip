@@ -199,7 +199,7 @@ __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBin
 #else
     constexpr bool kM4Pairs = kR1;
 #endif
-    if constexpr (M == 2 || M == 3 || (M == 4 && kM4Pairs)) {
+    if constexpr (tree_two_pairs(M, kM4Pairs)) {
         for (; b + stride < n_pairs; b += 2 * stride, ++iter) {
             Fe P[M + 1];
             const uint64_t b2 = b + stride;
@@ -209,7 +209,7 @@ __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBin
                 for (int l = 0; l < 9; ++l) acc.l[l] = my[(9 * t + l) * kBlock];
                 acc = fe_add(acc, v);
                 if (iter & 1u) acc = fe_carry_pass(acc);
-                if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc));
+                if ((iter & (kBigSumReduceEvery - 1)) == kBigSumReduceEvery - 1) acc = fe_from_fr(fe_to_fr(acc));
 #pragma unroll
                 for (int l = 0; l < 9; ++l) my[(9 * t + l) * kBlock] = acc.l[l];
             };
@@ -321,7 +321,7 @@ __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBin
                 for (int l = 0; l < 9; ++l) a.l[l] = my[(9 * t + l) * kBlock];
                 a = fe_add(a, P[t]);
                 if (iter & 1u) a = fe_carry_pass(a);
-                if ((iter & 31u) == 31u) a = fe_from_fr(fe_to_fr(a));
+                if ((iter & (kBigSumReduceEvery - 1)) == kBigSumReduceEvery - 1) a = fe_from_fr(fe_to_fr(a));
 #pragma unroll
                 for (int l = 0; l < 9; ++l) my[(9 * t + l) * kBlock] = a.l[l];
             }
@@ -395,7 +395,7 @@ __device__ __forceinline__ void tree_pass(const Slot *S, const int32_t (&r)[kBin
             a = fe_add(a, P[t]);
             // limbs: tightened + two products' limbs < 3 * 2^29 < 2^31, so a carry pass every other iteration suffices
             if (iter & 1u) a = fe_carry_pass(a);
-            if ((iter & 31u) == 31u) a = fe_from_fr(fe_to_fr(a)); // keep the top limb far from 2^31 on very long grid-stride loops
+            if ((iter & (kBigSumReduceEvery - 1)) == kBigSumReduceEvery - 1) a = fe_from_fr(fe_to_fr(a)); // keep the top limb far from 2^31 on very long grid-stride loops
 #pragma unroll
             for (int l = 0; l < 9; ++l) my[(9 * t + l) * kBlock] = a.l[l];
         }

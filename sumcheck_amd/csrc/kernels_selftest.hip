@@ -266,3 +266,7 @@ extern "C" __attribute__((visibility("default"))) int sc_debug_fe_op(int op, con
     if (e != hipSuccess) return (int)e;
     return (int)hipDeviceSynchronize();
 }
+
+// blocks of a grid-strided launch over n_pairs items as THIS build launches them (the experiments build: capped by SC_GRID), for tests
+// that set the iterations a lane makes (tests/test_gpu_big_sum_bounds.py); exported, not part of the ABI
+extern "C" __attribute__((visibility("default"))) int sc_debug_grid_for_pairs(uint64_t n_pairs) { return scd::grid_for_pairs(n_pairs); }

@@ -640,26 +640,21 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
     const bool merged = !small && p->merge_rounds && !p->any_generic;
     if (merged) {
         grid = std::min(grid, scd::kRoundTreeGrid);
-        // One product per block row (k_round_tree_split / k_round1_tree_split): `grid` blocks per product.  Measured per round size on
-        // config 3 (profiles/r2e_split_rounds.txt): many small blocks for the rounds that stream tables, fewer for the short ones.
+        // One product per block row (k_round_tree_split / k_round1_tree_split): `grid` blocks per product, merged_row_blocks (lane_sum.hpp)
         bool split = !p->fused_finalize;
-        int split_grid = n_pairs >= (1ULL << 21) ? 1024 : n_pairs >= (1ULL << 20) ? 768 : n_pairs >= (1ULL << 18) ? 384 : n_pairs >= (1ULL << 17) ? 256 : 192;
+        int split_base = 0;
 #ifdef SC_EXPERIMENTS // SC_SPLIT=0: every product in every block (k_round_tree); SC_SPLIT_GRID=n: blocks per product
         static const bool split_off = std::getenv("SC_SPLIT") && std::atoi(std::getenv("SC_SPLIT")) == 0;
         static const int split_cap = std::getenv("SC_SPLIT_GRID") ? std::atoi(std::getenv("SC_SPLIT_GRID")) : 0;
         if (split_off) split = false;
-        if (split_cap > 0) split_grid = split_cap;
+        if (split_cap > 0) split_base = split_cap;
 #endif
-        // The block counts above were measured on config 3's FOUR rows; what a short round needs is enough blocks in all to keep the per-lane
-        // chain at one iteration.  Fewer rows get proportionally more blocks per row in the rounds that no longer stream (< 2^21 pairs);
-        // the streaming rounds of a single row keep one full wave of resident blocks (a second, partial wave would run alone at the end).
 #ifndef SC_NO_KGRID // (A/B build: the per-row counts whatever the number of rows)
-        if (p->K < 4 && n_pairs < (1ULL << 21)) split_grid = std::min(scd::kMaxGrid, split_grid * 4 / (int)p->K);
-        else if (p->K == 1) split_grid = std::min(split_grid, scd::kRoundTreeGrid); // (one product: one full wave of resident blocks)
+        constexpr bool by_rows = true;
 #else
-        if (p->K == 1) split_grid = std::min(split_grid, scd::kRoundTreeGrid);
+        constexpr bool by_rows = false;
 #endif
-        if (split) grid = std::min(scd::grid_for_pairs(n_pairs), split_grid);
+        if (split) grid = std::min(scd::grid_for_pairs(n_pairs), scd::merged_row_blocks(n_pairs, p->K, split_base, by_rows));
         // the previous round's complete node sums are on the device and this round's will be: node 1 comes from the claim identity
         skip1 = bind && split && p->sums_round == (int64_t)p->round - 1 && skip1_enabled() &&
                 scd::finalize_keeps_sums((int)p->K, (int)p->D, grid, !p->h_finprods.empty(), fin_mb_enabled());

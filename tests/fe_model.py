@@ -27,7 +27,7 @@ OP_SHL5_MUL_U, OP_LINE, OP_ACCUM, OP_FOLD_CELL, OP_WIDE_VALUE, OP_WIDE_EXT = 13,
 
 NODE_INF = 0x7FFFFFFF
 MAX_FUSED_M = 8
-LAZY_SUM_MAX_P = 282        # kernels.h: kLazySumMaxP = floor(2^31 / 7597479)
+LAZY_SUM_MAX_P = 282        # lane_sum.hpp: kLazySumMaxP = floor(2^31 / 7597479)
 
 
 def node_value(s: int) -> int:
@@ -408,6 +408,76 @@ def all_selector_values(M: int, k: int, orient: str, t_node: int, lazy: int = No
         lo, hi = selector_pair(k, 1 + t % 7, t if low else (7 << 203) + t, flip, lazy)
         vals += [fe_line(lo, hi, node_value(t_node))[0]] * e
     return vals
+
+
+# ---- the per-lane running sums of the big rounds: tree_pass of kernels_big.hip ----------------------------------------------
+BIG_SUM_REDUCE_EVERY = 32   # lane_sum.hpp: kBigSumReduceEvery
+BIG_TERM_WORST_P = 2        # lane_sum.hpp: kBigTermWorstP
+F29_ENTRY_BOUND = 1 << 255  # f29_pack.hpp: a packed entry is a 256-bit two's-complement integer
+
+
+def big_lane_sum(terms, strict: bool = True):
+    """one running sum of a lane of tree_pass over its pass: sum += term, a carry pass on odd iterations, fe_from_fr(fe_to_fr(sum)) when
+    (iter & 31) == 31; every limb checked against int32 after every step.  -> (the sum, peak |limb 8| in units of p >> 232, the
+    iteration at which a limb left int32 or None); strict: leaving is an AssertionError"""
+    acc, peak = [0] * NL, 0
+    for it, term in enumerate(terms):
+        acc = fe_add(acc, term)
+        peak = max(peak, abs(acc[8]))
+        if not fits_i32(acc):
+            assert not strict, f"the running sum leaves int32 in iteration {it}: limb 8 = {acc[8]} ({acc[8] / PH:.1f} p)"
+            return acc, peak / PH, it
+        if it & 1:
+            acc = carry_pass(acc)
+        if (it & (BIG_SUM_REDUCE_EVERY - 1)) == BIG_SUM_REDUCE_EVERY - 1:
+            acc = limbs_of(value(acc) % P)
+    return acc, peak / PH, None
+
+
+def big_lane_sum_pairs(operands, strict: bool = True):
+    """the two-pair form: a term is fe_mul2_sum(a, b, c, d) -- the final products of pairs b and b + stride behind ONE Montgomery reduction,
+    so 64 products make 32 terms; operands: (a, b, c, d) per iteration, each inside BOX_MUL2"""
+    for ops in operands:
+        assert all(in_box(x, BOX_MUL2) for x in ops)
+    return big_lane_sum([fe_mul2_sum(*ops) for ops in operands], strict)
+
+
+def product_term_bound_p(j: int, two_pairs: bool) -> float:
+    """DESIGN 4.6's bound on one term of a product of two to four whose factors are lazy entries in (-j p, p), in units of p: a product
+    of lines within j p is within (1 + j^2 / 70) p; the two-pair form puts two of them behind one reduction"""
+    return (2 if two_pairs else 1) * (1 + j * j / 70)
+
+
+def tree_terms(M: int, lo, hi, lo2=None, hi2=None):
+    """the M + 1 terms tree_pass adds for one iteration from its factors' line ends (lists of M limb vectors; lo2 / hi2: the second pair of
+    the two-pair form), in the kernel's order of operations.  Nodes 0, 1, inf, -1, 2"""
+    def quad(l0, h0, l1, h1):
+        return fe_mul(l0, l1), fe_mul(h0, h1), fe_mul(fe_sub(h0, l0), fe_sub(h1, l1))
+
+    def qm1(q):  # q(-1) = 2 q(inf) + 2 q(0) - q(1)
+        return carry_pass(fe_sub(fe_add(fe_add(q[2], q[2]), fe_add(q[0], q[0])), q[1]))
+
+    def qp2(q):  # q(2) = 2 q(inf) + 2 q(1) - q(0)
+        return carry_pass(fe_sub(fe_add(fe_add(q[2], q[2]), fe_add(q[1], q[1])), q[0]))
+
+    two = lo2 is not None
+    mul = (lambda a, b, c, d: fe_mul2_sum(a, b, c, d)) if two else (lambda a, b, c, d: fe_mul(a, b))
+    L2, H2 = (lo2, hi2) if two else (lo, hi)
+    if M == 1:
+        assert not two
+        return [lo[0], hi[0]]
+    if M == 2:
+        return [mul(lo[0], lo[1], L2[0], L2[1]), mul(hi[0], hi[1], H2[0], H2[1]),
+                mul(fe_sub(hi[0], lo[0]), fe_sub(hi[1], lo[1]), fe_sub(H2[0], L2[0]), fe_sub(H2[1], L2[1]))]
+    q, s = quad(lo[0], hi[0], lo[1], hi[1]), quad(L2[0], H2[0], L2[1], H2[1])
+    if M == 3:
+        f = lambda l, h: carry_pass(fe_sub(fe_add(l, l), h))  # f2(-1) = 2 lo - hi
+        return [mul(lo[2], q[0], L2[2], s[0]), mul(hi[2], q[1], H2[2], s[1]), mul(fe_sub(hi[2], lo[2]), q[2], fe_sub(H2[2], L2[2]), s[2]),
+                mul(f(lo[2], hi[2]), qm1(q), f(L2[2], H2[2]), qm1(s))]
+    assert M == 4
+    qb, sb = quad(lo[2], hi[2], lo[3], hi[3]), quad(L2[2], H2[2], L2[3], H2[3])
+    return [mul(q[0], qb[0], s[0], sb[0]), mul(q[1], qb[1], s[1], sb[1]), mul(q[2], qb[2], s[2], sb[2]),
+            mul(qm1(q), qm1(qb), qm1(s), qm1(sb)), mul(qp2(q), qp2(qb), qp2(s), qp2(sb))]
 
 
 def to_mont(r_std: int) -> int:

@@ -417,3 +417,128 @@ def test_the_lazy_sum_of_all_selector_products_stays_inside_the_top_limb():
                     assert pairs <= 16
                     worst = max(worst, (pairs * final / fm.LAZY_SUM_MAX_P, M, k, pairs))
     assert worst[0] < 1 and worst[1:] == (9, 12, 8) and 0.84 < worst[0] < 0.86, worst
+
+
+# ---- the per-lane running sums of the big rounds: tree_pass's accumulator, and what it is handed ------------------------------
+from tests import f29_pack_model as f29
+from tests.test_lane_sum_host import lane_table
+
+E255 = fm.F29_ENTRY_BOUND - 1  # the packed format's largest magnitude: 1.104 p
+
+
+def _unsettled(j, c=23 << 200):
+    """a sinking table's entry after j binds that are NOT settled (bind_f29: the table format before it was packed): c + j (delta - p)"""
+    return fm.limbs_of(c + j * (fm.DELTA - P))
+
+
+def test_the_running_sum_takes_31_unsettled_entries_at_minus_9_p_and_not_32():
+    """the accumulator's own limit, whatever hands it its terms: between two reductions limb 8 holds 282 p.  Raw entries at -9 p (a sinking
+    table after nine binds without f29_settle) leave int32 with the 32nd term, the one after which the sum would have been reduced; at
+    -8 p they stay inside for any number of iterations; at the open end of the range those entries had, -(8 + 1) p, they do not"""
+    s, r = fm.sinking_challenges(9, fm.SEED + 40)
+    tab = [fm.limbs_of(v) for v in fm.sinking_table(9, s, 1, sum(s))]
+    for rj in r:
+        tab = [fm.bind_f29(tab[2 * i], tab[2 * i + 1], rj) for i in range(len(tab) // 2)]
+    assert fm.value(tab[0]) == fm.value(_unsettled(9, sum(s))) and -9 * P <= fm.value(tab[0]) < -9 * P + (1 << 242)
+    _, peak, left = fm.big_lane_sum([_unsettled(9)] * 32, strict=False)
+    assert left == 31 and peak > fm.LAZY_SUM_MAX_P
+    with pytest.raises(AssertionError):
+        fm.big_lane_sum([_unsettled(9)] * 32)
+    acc, peak, left = fm.big_lane_sum([_unsettled(9)] * 31)
+    assert left is None and 278 < peak < 279.1 and fm.value(acc) == 31 * fm.value(_unsettled(9))
+    acc, peak, left = fm.big_lane_sum([_unsettled(8)] * 200)  # every block of 32 starts from the reduced sum
+    assert left is None and 255 < peak < 257 and fm.value(acc) % P == 200 * fm.value(_unsettled(8)) % P
+    assert fm.big_lane_sum([fm.limbs_of(1 - 9 * P)] * 32, strict=False)[2] == 31
+    print(f"\n31 terms at -9 p: {31 * 9} p of {fm.LAZY_SUM_MAX_P}; 32 terms at -8 p + the reduced sum: {peak:.1f} p")
+
+
+def test_the_two_pair_form_is_the_same_accumulator_over_half_the_terms():
+    """64 products in 32 terms: fe_mul2_sum's result is (a b + c d) / 2^261 in a window of p, so a term is two products wide"""
+    rng = random.Random(fm.SEED + 41)
+    ops = [[fm.limbs_of(rng.randrange(P)) for _ in range(4)] for _ in range(70)]
+    acc, peak, left = fm.big_lane_sum_pairs(ops)
+    inv = pow(1 << fm.K, -1, P)
+    assert left is None and fm.value(acc) % P == sum(fm.value(a) * fm.value(b) + fm.value(c) * fm.value(d) for a, b, c, d in ops) * inv % P
+    assert -6 * P < fm.value(acc) < 2 * P and peak < 33 * 2  # 70 = 2 x 32 + 6: the reduced sum and six terms, each in (-p, 2 p^2 / 2^261]
+    corner = [[fm.limbs_of(v) for v in (E255, E255, E255, E255)]] * 64  # 2 E^2 / 2^261 = 0.035 p: the window decides, not the operands
+    assert fm.big_lane_sum_pairs(corner)[1] < 33
+
+
+def _term_bound_p(M, two):
+    """|a term of tree_pass| in p for factors whose line ends lie within E = 2^255 / p = 1.104: fe_mul(a, b) is within |a| |b| / LAMBDA + 1,
+    a slope within 2 E, a quadratic's extension 2 q(inf) + 2 q(0) - q(1) within the sum, f(-1) = 2 lo - hi within 3 E"""
+    E = fm.F29_ENTRY_BOUND / P
+    mul = lambda a, b: a * b / LAMBDA
+    q0, qi = mul(E, E) + 1, mul(2 * E, 2 * E) + 1
+    ext = 2 * qi + 3 * q0
+    widest = {1: E, 2: mul(2 * E, 2 * E), 3: max(mul(2 * E, qi), mul(3 * E, ext)), 4: max(mul(qi, qi), mul(ext, ext))}[M]
+    return widest if M == 1 else (2 if two else 1) * widest + 1
+
+
+@pytest.mark.parametrize("M", [1, 2, 3, 4])
+def test_a_term_from_packed_entries_is_below_two_p(M):
+    """what the big rounds actually hand the accumulator since bound tables are packed: LoadFactor returns a canonical entry or one
+    settled into [-2^255, 2^255), however many binds lie behind it.  Every factor's pair on the corners of that box, both pairs of the
+    two-pair form alike: no term of any node reaches kBigTermWorstP p, and the model's widest stays within the bound worked out by hand"""
+    import itertools
+    ends = [fm.limbs_of(v) for v in (E255, -E255 - 1)]
+    widest = {False: 0, True: 0}
+    for combo in itertools.product(itertools.product(ends, ends), repeat=M):
+        lo, hi = [c[0] for c in combo], [c[1] for c in combo]
+        for two in ([False] if M == 1 else [False, True]):
+            terms = fm.tree_terms(M, lo, hi, lo if two else None, hi if two else None)
+            assert len(terms) == M + 1 and all(fm.fits_i32(t) for t in terms)
+            widest[two] = max(widest[two], max(abs(fm.value(t)) for t in terms) / P)
+    for two, w in widest.items():
+        assert w <= _term_bound_p(M, two) < fm.BIG_TERM_WORST_P, (M, two, w)
+    print(f"\nM = {M}: widest term {widest[False]:.3f} p (bound {_term_bound_p(M, False):.3f})" +
+          (f", two pairs {widest[True]:.3f} p (bound {_term_bound_p(M, True):.3f})" if M > 1 else ""))
+    # the accumulator over the longest stretch between two reductions, every term at the box's end: 33 x 1.104 p of the 282
+    if M == 1:
+        for e in ends:
+            acc, peak, left = fm.big_lane_sum([e] * 64)
+            assert left is None and peak < 33 * 1.105 + 0.01 < fm.LAZY_SUM_MAX_P / 7
+
+
+def test_a_sinking_table_bound_into_the_packed_format_never_sinks():
+    """the tables of tests/test_gpu_big_sum_bounds.py in the model: bound with f29_settle (load_factor.hpp), a sinking table's entries are
+    back near zero after every bind -- from the low end and from just below p -- so round 10's 32 raw terms a lane sum to less than 33 p"""
+    nv = 12
+    s, r = fm.sinking_challenges(nv, fm.SEED + 42)
+    for c in (sum(s), P - 1):
+        tab = [fm.limbs_of(v) for v in fm.sinking_table(nv, s, 1, c)]
+        for k, rj in enumerate(r[:10], start=1):
+            tab = [f29.bind_packed(tab[2 * i], tab[2 * i + 1], rj)[0] for i in range(len(tab) // 2)]
+            vals = [fm.value(e) for e in tab]
+            assert all(-P // 2 - (1 << 233) < v < P + k * (1 << 230) for v in vals) and all(f29.packable(e) for e in tab)
+            assert all(0 <= v <= k * fm.DELTA + (1 << 206) for v in vals) or c == P - 1
+            lo = tab[0::2][:64]
+            acc, peak, left = fm.big_lane_sum(lo)
+            assert left is None and peak < 33 * 1.105 and fm.value(acc) % P == sum(fm.value(e) for e in lo) % P
+
+
+def test_products_at_the_design_bound_fit_every_big_round_the_library_admits():
+    """the enumeration of lane_sum.hpp (every nv <= 40, every big round, the merged launch of 1, 2, 3, 4 and 12 rows and one launch per
+    product) against DESIGN 4.6's bound for a term of a product of two to four over entries left lazy for j = round - 1 binds,
+    (1 + j^2 / 70) p, twice that where a term holds two pairs: min(terms, 32) of them and the reduced sum stay inside 282 p.  That bound
+    predates the packed format, which keeps the factors within 1.104 p and a term below 2 p in EVERY round (the previous tests): 33 x 2 =
+    66 p.  For a raw entry counted by the range it had before (-(j + 1) p; the sinking family reached -j p) the same enumeration gives the
+    nv at which 32 terms no longer fit"""
+    tight, single_doc, single_family = (0,), [], []
+    for nv, rnd, rows, M, grid, terms, two in lane_table():
+        j, held = rnd - 1, min(terms, fm.BIG_SUM_REDUCE_EVERY)
+        assert held + 1 == min(terms, 32) + 1 and (held + 1) * fm.BIG_TERM_WORST_P <= fm.LAZY_SUM_MAX_P
+        if M >= 2:
+            tight = max(tight, (held * fm.product_term_bound_p(j, bool(two)) + 1, nv, rnd, rows, M, terms))
+        else:
+            if held * (j + 1) + 1 > fm.LAZY_SUM_MAX_P:
+                single_doc.append(nv)
+            if held * j + 1 > fm.LAZY_SUM_MAX_P:
+                single_family.append(nv)
+    assert tight[0] <= fm.LAZY_SUM_MAX_P and 270 < tight[0] < 271 and tight[2] == 16 and tight[5] >= 32, tight
+    w = fm.product_term_bound_p(15, True)
+    acc, peak, left = fm.big_lane_sum([fm.limbs_of(-int(w * P))] * 64)
+    assert left is None and tight[0] - 1.01 < peak <= tight[0]  # (the reduced sum is in [0, p): it counts for the terms' sign or against it)
+    assert min(single_doc) == 32 and min(single_family) == 33
+    print(f"\nproducts at (1 + j^2 / 70) p a pair: {tight[0]:.1f} p of {fm.LAZY_SUM_MAX_P} at nv {tight[1]} round {tight[2]} ({tight[5]} terms a lane); "
+          f"from packed entries: {33 * fm.BIG_TERM_WORST_P} p in every round")

@@ -169,7 +169,8 @@ def interactive(nv, shapes, tabs, chal, lazy_big_binds, resident="resident.slice
 @pytest.mark.parametrize("nv", [22, 23])
 def test_a_sinking_table_through_lazy_big_rounds_into_the_resident_slices(nv):
     """[[0]]: the tail starts at 2^16 pairs, after nv - 18 lazy big binds and with one more of its own in front of its first sums -- 256 RAW
-    entries a block at -(nv - 17) p, then -(nv - 16) p, ...: tail_worst_p and lazy_sum_needs_reduce at the entries' lower end.
+    entries a block, counted by tail_worst_p as if at -(nv - 17) p, then -(nv - 16) p, ...  (Since bound tables are packed the big rounds
+    settle every entry into +-1.104 p, so the tail's own binds sink from there: -1 p, -2 p, ...; the rule's count is an upper bound.)
     tail_slices_blocks' refusal (33 terms of worst_p p a lane) is NOT reached by this shape on a device that holds 256 blocks: a lane then has
     4 terms a round, and 5 * worst_p passes 282 only beyond validate_desc's 40 variables -- there is no nv at which the counter flips."""
     s, r = fm.sinking_challenges(nv, 66000 + nv)
