@@ -114,6 +114,11 @@ struct AreaLease {
     }
 };
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the error a step on instance i has just left, behind "instance i: "
+int prefix_instance(int rc, uint32_t i) {
+    const std::string why = sc_last_error();
+    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+}
 // the area on the calling thread's device, with its stream (the caller holds the lease and the device gate)
 int area_open(BatchArea &a, int dev) {
     HIP_TRY(hipSetDevice(dev));
@@ -239,8 +244,7 @@ namespace {
 // tail_slices_blocks': passes over a combination's pairs x multiplicands; up to 16 (a GKR phase's shape at 2^10: 131 against 132 us)
 // a lone instance runs batched.
 uint32_t batch_min_n(const SharedMeta &s) {
-    int L = 64;
-    while (L * s.n_combos > scd::kTsBlock) L >>= 1;
+    const int L = scd::bt_lanes(s.n_combos);
     const uint64_t pairs = 1ULL << (s.nv - 1), passes = (pairs + (uint64_t)L - 1) / (uint64_t)L;
     return passes * s.max_mult <= 16 ? 1 : 2;
 }
@@ -526,12 +530,8 @@ const char *first_structure_difference(const sc_poly_desc &a, const sc_poly_desc
 }
 
 int batch_check_desc(const sc_poly_desc *descs, uint32_t i) {
-    int rc = validate_desc(&descs[i]); // prover_init panics on a constant before anything is proved (prover.rs:50-52)
-    if (rc) {
-        const std::string why = sc_last_error();
-        return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-    }
-    return SC_OK;
+    const int rc = validate_desc(&descs[i]); // prover_init panics on a constant before anything is proved (prover.rs:50-52)
+    return rc ? prefix_instance(rc, i) : SC_OK;
 }
 int batch_check_structure(const sc_poly_desc *descs, uint32_t i) {
     if (const char *field = i ? first_structure_difference(descs[0], descs[i]) : nullptr)
@@ -647,10 +647,7 @@ extern "C" int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *
         if (state[i] == kDone) continue;
         int rc = serial.prove(&descs[i], rngs_or_null ? rngs_or_null[i] : nullptr, out_proofs + (size_t)i * nv * D * 4,
                               out_randomness_or_null ? out_randomness_or_null + (size_t)i * nv * 4 : nullptr);
-        if (rc) {
-            const std::string why = sc_last_error();
-            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-        }
+        if (rc) return prefix_instance(rc, i);
         if (took) g_stat[kStatProofRetries].fetch_add(1, std::memory_order_relaxed);
     }
     if (trace)
@@ -670,6 +667,101 @@ uint32_t gkr_batch_min_n(uint32_t dim) {
     (void)dim;
     return 1;
 }
+
+struct StageMap { // host arrays behind one another in the image, every distinct (pointer, size) once
+    struct Item {
+        const void *src;
+        size_t bytes, off;
+    };
+    std::vector<Item> items;
+    std::map<std::pair<const void *, size_t>, size_t> where;
+    size_t base = 0, bytes = 0;
+    size_t add(const void *src, size_t n_bytes) { // -> offset of the array's copy in the image
+        auto it = where.find({src, n_bytes});
+        if (it != where.end()) return it->second;
+        const size_t off = base + bytes;
+        items.push_back({src, n_bytes, off});
+        where.emplace(std::make_pair(src, n_bytes), off);
+        bytes += round_up(n_bytes, 32);
+        return off;
+    }
+    void copy_into(char *h_up) const {
+        for (const Item &it : items) std::memcpy(h_up + it.off, it.src, it.bytes);
+    }
+};
+int check_canonical(const uint64_t *elems, uint32_t n_elems, uint32_t i, const char *what) {
+    for (uint32_t k = 0; k < n_elems; ++k) {
+        sch::Fr e;
+        std::memcpy(&e, elems + 4 * (size_t)k, 32);
+        if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: %s[%u] is not a canonical field element", i, what, k);
+    }
+    return SC_OK;
+}
+
+// ---- what sc_gkr_prove_batch and sc_gkr_subclaim_batch (below) share: the callers' arrays, their checks, their place in the uploaded image
+struct GkrBatchIn {
+    uint32_t n, dim;
+    const uint64_t *const *f1_idx, *const *f1_vals;
+    const uint64_t *nnz;
+    const uint64_t *const *f2, *const *f3, *const *g;
+    bool on_device; // SC_TABLES_ON_DEVICE: read in place
+};
+// sc_gkr_prove's checks on instance i (no HIP call); uv_or_null: the subclaim call's points u | v, checked behind g
+int gkr_check_instance(const GkrBatchIn &in, uint32_t i, const uint64_t *uv_or_null) {
+    if (in.nnz[i] >= (1ULL << 32)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz too large", i);
+    if ((in.nnz[i] && (!in.f1_idx[i] || !in.f1_vals[i])) || !in.f2[i] || !in.f3[i] || !in.g[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null argument", i);
+    if (int rc = check_canonical(in.g[i], in.dim, i, "g")) return rc;
+    if (uv_or_null)
+        if (int rc = check_canonical(uv_or_null, 2 * in.dim, i, "uv")) return rc;
+    if (!in.on_device)
+        for (uint64_t k = 0; k < in.nnz[i]; ++k)
+            if ((in.f1_idx[i][k] >> (3 * in.dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 index %llu out of range", i, (unsigned long long)k);
+    return SC_OK;
+}
+// host inputs into the image, each distinct array once (one wiring predicate for many data instances is the usual case) -> per instance the
+// offsets of idx, vals, f2, f3; empty for device inputs
+std::vector<size_t> gkr_stage_inputs(const GkrBatchIn &in, StageMap &st) {
+    std::vector<size_t> offs;
+    if (in.on_device) return offs;
+    const size_t N = (size_t)1 << in.dim;
+    offs.resize((size_t)in.n * 4);
+    for (uint32_t i = 0; i < in.n; ++i) {
+        offs[4 * (size_t)i + 0] = in.nnz[i] ? st.add(in.f1_idx[i], (size_t)in.nnz[i] * 8) : st.base;
+        offs[4 * (size_t)i + 1] = in.nnz[i] ? st.add(in.f1_vals[i], (size_t)in.nnz[i] * 32) : st.base;
+        offs[4 * (size_t)i + 2] = st.add(in.f2[i], N * 32);
+        offs[4 * (size_t)i + 3] = st.add(in.f3[i], N * 32);
+    }
+    return offs;
+}
+// instance i's record: its arrays where the kernel reads them (in place, or their staged copies in the image at d_up) and its point(s) at d_g
+scd::GkrBatchInst gkr_record(const GkrBatchIn &in, uint32_t i, const std::vector<size_t> &offs, const char *d_up, const char *d_g) {
+    scd::GkrBatchInst r;
+    r.nnz = in.nnz[i];
+    r.g = reinterpret_cast<const uint4 *>(d_g);
+    if (in.on_device) {
+        r.idx = in.f1_idx[i];
+        r.vals = reinterpret_cast<const uint4 *>(in.f1_vals[i]);
+        r.f2 = reinterpret_cast<const uint4 *>(in.f2[i]);
+        r.f3 = reinterpret_cast<const uint4 *>(in.f3[i]);
+    } else {
+        r.idx = reinterpret_cast<const uint64_t *>(d_up + offs[4 * (size_t)i + 0]);
+        r.vals = reinterpret_cast<const uint4 *>(d_up + offs[4 * (size_t)i + 1]);
+        r.f2 = reinterpret_cast<const uint4 *>(d_up + offs[4 * (size_t)i + 2]);
+        r.f3 = reinterpret_cast<const uint4 *>(d_up + offs[4 * (size_t)i + 3]);
+    }
+    return r;
+}
+// device-resident lists: their indices are checked on the device, in front of the launch (the kernels themselves mask every index they use);
+// the flags (zeroed in the image) are at flag_off
+int gkr_check_idx_on_device(const scd::GkrBatchInst *d_rec, uint32_t n, uint32_t dim, char *h_up, char *d_up, size_t flag_off, hipStream_t stream) {
+    HIP_TRY(scd::launch_batch_gkr_idx_range(d_rec, n, dim, reinterpret_cast<uint32_t *>(d_up + flag_off), stream));
+    HIP_TRY(hipMemcpyAsync(h_up + flag_off, d_up + flag_off, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint32_t *fl = reinterpret_cast<const uint32_t *>(h_up + flag_off);
+    for (uint32_t i = 0; i < n; ++i)
+        if (fl[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
+    return SC_OK;
+}
 } // namespace
 
 extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
@@ -680,28 +772,19 @@ extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
     if (dim == 0) return sc_internal_fail(SC_ERR_CONSTANT_POLY, "instance 0: Attempt to prove a constant.");
     if (dim > 21) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim %u: 3*dim index bits do not fit 64-bit indices", dim);
     const bool dev_in = flags & SC_TABLES_ON_DEVICE;
+    const GkrBatchIn in = {n, dim, f1_idx, f1_vals, nnz, f2, f3, g, dev_in};
     uint64_t nnz_max = 0;
     {
         std::unordered_set<const sc_rng *> seen;
         for (uint32_t i = 0; i < n; ++i) {
             if (!rngs[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null rng", i);
             if (!seen.insert(rngs[i]).second) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: its rng is also an earlier instance's: every instance continues a transcript of its own", i);
-            if (nnz[i] >= (1ULL << 32)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz too large", i);
-            if ((nnz[i] && (!f1_idx[i] || !f1_vals[i])) || !f2[i] || !f3[i] || !g[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null argument", i);
-            for (uint32_t k = 0; k < dim; ++k) {
-                sch::Fr e;
-                std::memcpy(&e, g[i] + 4 * k, 32);
-                if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: g[%u] is not a canonical field element", i, k);
-            }
-            if (!dev_in)
-                for (uint64_t k = 0; k < nnz[i]; ++k)
-                    if ((f1_idx[i][k] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 index %llu out of range", i, (unsigned long long)k);
+            if (int rc = gkr_check_instance(in, i, nullptr)) return rc;
             nnz_max = std::max(nnz_max, nnz[i]);
         }
     }
     if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
     static const bool trace = std::getenv("SC_HOST_TRACE") != nullptr;
-    const size_t N = (size_t)1 << dim;
     std::vector<uint8_t> state(n, kGaveUp); // (what the serial plan below proves)
     bool took = false;
     const int64_t pol = scd::policy(scd::kPolBatch);
@@ -720,37 +803,13 @@ extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
         SharedMeta s;
         build_shared(&d, s);
         s.unit.push_back(unit_matrix(2, 3));
-        // the uploaded image: instance records | the matrices | the index check's flags | the points g | host inputs, each distinct array once
-        // (one wiring predicate for many data instances is the usual case)
+        // the uploaded image: instance records | the matrices | the index check's flags | the points g | host inputs
         const size_t rec_bytes = round_up((size_t)n * sizeof(scd::GkrBatchInst), 256), w_bytes = round_up((size_t)s.w_elems * 32, 256);
         const size_t flag_bytes = round_up((size_t)n * 4, 256), g_bytes = round_up((size_t)n * dim * 32, 256);
-        const size_t rec_off = 0, w_off = rec_bytes, flag_off = w_off + w_bytes, g_off = flag_off + flag_bytes, stage_off = g_off + g_bytes;
-        struct Staged {
-            const void *src;
-            size_t bytes, off;
-        };
-        std::vector<Staged> staged;
-        std::map<std::pair<const void *, size_t>, size_t> where;
-        size_t stage_bytes = 0;
-        auto stage = [&](const void *src, size_t bytes) -> size_t { // offset of the array's copy in the image
-            auto it = where.find({src, bytes});
-            if (it != where.end()) return it->second;
-            const size_t off = stage_off + stage_bytes;
-            staged.push_back({src, bytes, off});
-            where.emplace(std::make_pair(src, bytes), off);
-            stage_bytes += round_up(bytes, 32);
-            return off;
-        };
-        std::vector<size_t> offs_in; // per instance: idx, vals, f2, f3 (host inputs)
-        if (!dev_in) {
-            offs_in.resize((size_t)n * 4);
-            for (uint32_t i = 0; i < n; ++i) {
-                offs_in[4 * (size_t)i + 0] = nnz[i] ? stage(f1_idx[i], (size_t)nnz[i] * 8) : stage_off;
-                offs_in[4 * (size_t)i + 1] = nnz[i] ? stage(f1_vals[i], (size_t)nnz[i] * 32) : stage_off;
-                offs_in[4 * (size_t)i + 2] = stage(f2[i], N * 32);
-                offs_in[4 * (size_t)i + 3] = stage(f3[i], N * 32);
-            }
-        }
+        const size_t rec_off = 0, w_off = rec_bytes, flag_off = w_off + w_bytes, g_off = flag_off + flag_bytes;
+        StageMap st;
+        st.base = g_off + g_bytes;
+        const std::vector<size_t> offs_in = gkr_stage_inputs(in, st);
         BatchJob job;
         job.n = n;
         job.n_rounds = 2 * dim;
@@ -762,41 +821,23 @@ extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
         job.plan_name = "batch.gkr_one_block";
         job.size_name = "dim";
         job.size = dim;
-        job.up_bytes = stage_off + stage_bytes;
+        job.up_bytes = st.base + st.bytes;
         job.blocks_per_cu = [&](int dv) { return scd::gkr_batch_blocks_per_cu(dv, dim); };
         job.fill = [&](char *h_up, char *d_up) -> int {
             scd::GkrBatchInst *rec = reinterpret_cast<scd::GkrBatchInst *>(h_up + rec_off);
             instance_weights(s, sch::kOne.l, reinterpret_cast<sch::Fr *>(h_up + w_off));
             std::memset(h_up + flag_off, 0, flag_bytes);
-            for (const Staged &st : staged) std::memcpy(h_up + st.off, st.src, st.bytes);
+            st.copy_into(h_up);
             for (uint32_t i = 0; i < n; ++i) {
-                std::memcpy(h_up + g_off + (size_t)i * dim * 32, g[i], (size_t)dim * 32);
-                scd::GkrBatchInst &r = rec[i];
-                r.nnz = nnz[i];
-                r.g = reinterpret_cast<const uint4 *>(d_up + g_off + (size_t)i * dim * 32);
-                if (dev_in) {
-                    r.idx = f1_idx[i];
-                    r.vals = reinterpret_cast<const uint4 *>(f1_vals[i]);
-                    r.f2 = reinterpret_cast<const uint4 *>(f2[i]);
-                    r.f3 = reinterpret_cast<const uint4 *>(f3[i]);
-                } else {
-                    r.idx = reinterpret_cast<const uint64_t *>(d_up + offs_in[4 * (size_t)i + 0]);
-                    r.vals = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 1]);
-                    r.f2 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 2]);
-                    r.f3 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 3]);
-                }
+                const size_t gi = g_off + (size_t)i * dim * 32;
+                std::memcpy(h_up + gi, g[i], (size_t)dim * 32);
+                rec[i] = gkr_record(in, i, offs_in, d_up, d_up + gi);
             }
             return SC_OK;
         };
-        if (dev_in) // the lists are device memory: their indices are checked there, in front of the launch (the kernel itself masks every index it uses)
+        if (dev_in)
             job.check_on_device = [&](char *h_up, char *d_up, hipStream_t stream) -> int {
-                HIP_TRY(scd::launch_batch_gkr_idx_range(reinterpret_cast<const scd::GkrBatchInst *>(d_up + rec_off), n, dim, reinterpret_cast<uint32_t *>(d_up + flag_off), stream));
-                HIP_TRY(hipMemcpyAsync(h_up + flag_off, d_up + flag_off, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                const uint32_t *fl = reinterpret_cast<const uint32_t *>(h_up + flag_off);
-                for (uint32_t i = 0; i < n; ++i)
-                    if (fl[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
-                return SC_OK;
+                return gkr_check_idx_on_device(reinterpret_cast<const scd::GkrBatchInst *>(d_up + rec_off), n, dim, h_up, d_up, flag_off, stream);
             };
         job.launch = [&](const BatchPages &pg, int grid, hipStream_t stream) -> hipError_t {
             scd::BatchGkrArgs A;
@@ -833,10 +874,7 @@ extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
         work.emplace_back(i, *rngs[i]);
         int rc = sc_internal_gkr_prove(&work.back().second, f1_idx[i], f1_vals[i], nnz[i], dim, f2[i], f3[i], g[i], flags, out_proofs + (size_t)i * 2 * dim * 12,
                                        out_uv_or_null ? out_uv_or_null + (size_t)i * 2 * dim * 4 : nullptr, took);
-        if (rc) {
-            const std::string why = sc_last_error();
-            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-        }
+        if (rc) return prefix_instance(rc, i);
         if (took) g_stat[kStatProofRetries].fetch_add(1, std::memory_order_relaxed);
     }
     for (auto &w : work) rngs[w.first]->rng = w.second.rng;
@@ -865,28 +903,6 @@ namespace {
 // ahead there too (a whole call of 16 at nv = 14 costs 67 us, what the loop pays for little more than one instance).
 uint32_t eval_batch_min_n(uint32_t nv) { return nv <= 10 ? 1 : 16; }
 uint32_t gkr_eval_batch_min_n() { return 1; }
-
-struct StageMap { // host arrays behind one another in the image, every distinct (pointer, size) once
-    struct Item {
-        const void *src;
-        size_t bytes, off;
-    };
-    std::vector<Item> items;
-    std::map<std::pair<const void *, size_t>, size_t> where;
-    size_t base = 0, bytes = 0;
-    size_t add(const void *src, size_t n_bytes) { // -> offset of the array's copy in the image
-        auto it = where.find({src, n_bytes});
-        if (it != where.end()) return it->second;
-        const size_t off = base + bytes;
-        items.push_back({src, n_bytes, off});
-        where.emplace(std::make_pair(src, n_bytes), off);
-        bytes += round_up(n_bytes, 32);
-        return off;
-    }
-    void copy_into(char *h_up) const {
-        for (const Item &it : items) std::memcpy(h_up + it.off, it.src, it.bytes);
-    }
-};
 
 // One batched call over the work areas: `fill` writes the image into pinned memory (pointers into it are d_up + offset), one copy uploads
 // it, `launch` enqueues the kernels (it may synchronise to report an argument error found on the device), the image's out_bytes at out_off
@@ -932,18 +948,6 @@ int check_eval_desc(const sc_poly_desc *d, uint32_t i) {
     for (uint32_t u = 0; u < d->n_tables; ++u)
         if (!d->tables[u]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: table %u is null", i, u);
     return SC_OK;
-}
-int check_canonical(const uint64_t *elems, uint32_t n_elems, uint32_t i, const char *what) {
-    for (uint32_t k = 0; k < n_elems; ++k) {
-        sch::Fr e;
-        std::memcpy(&e, elems + 4 * (size_t)k, 32);
-        if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: %s[%u] is not a canonical field element", i, what, k);
-    }
-    return SC_OK;
-}
-int prefix_instance(int rc, uint32_t i) {
-    const std::string why = sc_last_error();
-    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
 }
 constexpr size_t kEvalImageMax = (size_t)1 << 30; // a batch whose staged inputs exceed this goes instance by instance
 } // namespace
@@ -1037,42 +1041,26 @@ extern "C" int sc_gkr_subclaim_batch(uint32_t n, uint32_t dim, const uint64_t *c
     if (dim == 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim 0: a GKR round has at least one variable per component");
     if (dim > 21) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim %u: 3*dim index bits do not fit 64-bit indices", dim);
     const bool dev_in = flags & SC_TABLES_ON_DEVICE;
+    const GkrBatchIn in = {n, dim, f1_idx, f1_vals, nnz, f2, f3, g, dev_in};
     uint64_t nnz_max = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (nnz[i] >= (1ULL << 32)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz too large", i);
-        if ((nnz[i] && (!f1_idx[i] || !f1_vals[i])) || !f2[i] || !f3[i] || !g[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null argument", i);
-        if (int rc = check_canonical(g[i], dim, i, "g")) return rc;
-        if (int rc = check_canonical(uv + (size_t)i * 2 * dim * 4, 2 * dim, i, "uv")) return rc;
-        if (!dev_in)
-            for (uint64_t k = 0; k < nnz[i]; ++k)
-                if ((f1_idx[i][k] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 index %llu out of range", i, (unsigned long long)k);
+        if (int rc = gkr_check_instance(in, i, uv + (size_t)i * 2 * dim * 4)) return rc;
         nnz_max = std::max(nnz_max, nnz[i]);
     }
     if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
-    const size_t N = (size_t)1 << dim;
     auto finish = [&](uint32_t i, const sch::Fr &a1, const sch::Fr &a2, const sch::Fr &a3) { // f1(g,u,v), f2(u), f3(v), their product (data_structures.rs:53-55)
         const sch::Fr e[4] = {a1, a2, a3, sch::mul(sch::mul(a1, a2), a3)};
         std::memcpy(out_evals + (size_t)i * 16, e, 128);
     };
     const int64_t pol = scd::policy(scd::kPolBatch);
     if (pol != 0 && scd::gkr_eval_batch_shape_fits(dim, nnz_max) && scd::eval_batch_shape_fits(dim) && (pol == 2 || n >= gkr_eval_batch_min_n())) {
-        // the image: instance records | the index check's flags | g | u | v per instance | (f2, f3) pointers | host inputs, each distinct array
-        // once (one wiring predicate for many data instances is the usual case) | the n x 3 values
+        // the image: instance records | the index check's flags | g | u | v per instance | (f2, f3) pointers | host inputs | the n x 3 values
         const size_t rec_bytes = round_up((size_t)n * sizeof(scd::GkrBatchInst), 256), flag_bytes = round_up((size_t)n * 4, 256);
         const size_t pt_bytes = round_up((size_t)n * 3 * dim * 32, 256), ptr_bytes = round_up((size_t)n * 2 * sizeof(void *), 256);
         const size_t flag_off = rec_bytes, pt_off = flag_off + flag_bytes, ptr_off = pt_off + pt_bytes;
         StageMap st;
         st.base = ptr_off + ptr_bytes;
-        std::vector<size_t> offs_in; // per instance: idx, vals, f2, f3 (host inputs)
-        if (!dev_in) {
-            offs_in.resize((size_t)n * 4);
-            for (uint32_t i = 0; i < n; ++i) {
-                offs_in[4 * (size_t)i + 0] = nnz[i] ? st.add(f1_idx[i], (size_t)nnz[i] * 8) : st.base;
-                offs_in[4 * (size_t)i + 1] = nnz[i] ? st.add(f1_vals[i], (size_t)nnz[i] * 32) : st.base;
-                offs_in[4 * (size_t)i + 2] = st.add(f2[i], N * 32);
-                offs_in[4 * (size_t)i + 3] = st.add(f3[i], N * 32);
-            }
-        }
+        const std::vector<size_t> offs_in = gkr_stage_inputs(in, st);
         const size_t out_off = round_up(st.base + st.bytes, 256), out_bytes = (size_t)n * 3 * 32;
         if (out_off + out_bytes <= kEvalImageMax) {
             bool took = false;
@@ -1084,37 +1072,18 @@ extern "C" int sc_gkr_subclaim_batch(uint32_t n, uint32_t dim, const uint64_t *c
                     std::memset(h_up + flag_off, 0, flag_bytes);
                     st.copy_into(h_up);
                     for (uint32_t i = 0; i < n; ++i) {
-                        char *pt = h_up + pt_off + (size_t)i * 3 * dim * 32;
-                        std::memcpy(pt, g[i], (size_t)dim * 32);
-                        std::memcpy(pt + (size_t)dim * 32, uv + (size_t)i * 2 * dim * 4, (size_t)2 * dim * 32);
-                        scd::GkrBatchInst &r = rec[i];
-                        r.nnz = nnz[i];
-                        r.g = reinterpret_cast<const uint4 *>(d_up + pt_off + (size_t)i * 3 * dim * 32);
-                        if (dev_in) {
-                            r.idx = f1_idx[i];
-                            r.vals = reinterpret_cast<const uint4 *>(f1_vals[i]);
-                            r.f2 = reinterpret_cast<const uint4 *>(f2[i]);
-                            r.f3 = reinterpret_cast<const uint4 *>(f3[i]);
-                        } else {
-                            r.idx = reinterpret_cast<const uint64_t *>(d_up + offs_in[4 * (size_t)i + 0]);
-                            r.vals = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 1]);
-                            r.f2 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 2]);
-                            r.f3 = reinterpret_cast<const uint4 *>(d_up + offs_in[4 * (size_t)i + 3]);
-                        }
-                        h_ptrs[2 * (size_t)i] = r.f2;
-                        h_ptrs[2 * (size_t)i + 1] = r.f3;
+                        const size_t pi = pt_off + (size_t)i * 3 * dim * 32; // g | u | v
+                        std::memcpy(h_up + pi, g[i], (size_t)dim * 32);
+                        std::memcpy(h_up + pi + (size_t)dim * 32, uv + (size_t)i * 2 * dim * 4, (size_t)2 * dim * 32);
+                        rec[i] = gkr_record(in, i, offs_in, d_up, d_up + pi);
+                        h_ptrs[2 * (size_t)i] = rec[i].f2;
+                        h_ptrs[2 * (size_t)i + 1] = rec[i].f3;
                     }
                 },
                 [&](char *h_up, char *d_up, hipStream_t stream) -> int {
                     const scd::GkrBatchInst *d_rec = reinterpret_cast<const scd::GkrBatchInst *>(d_up);
-                    if (dev_in) { // the lists are device memory: their indices are checked there, in front of the launch (the kernel itself masks every index it uses)
-                        HIP_TRY(scd::launch_batch_gkr_idx_range(d_rec, n, dim, reinterpret_cast<uint32_t *>(d_up + flag_off), stream));
-                        HIP_TRY(hipMemcpyAsync(h_up + flag_off, d_up + flag_off, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        const uint32_t *fl = reinterpret_cast<const uint32_t *>(h_up + flag_off);
-                        for (uint32_t i = 0; i < n; ++i)
-                            if (fl[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
-                    }
+                    if (dev_in)
+                        if (int rc = gkr_check_idx_on_device(d_rec, n, dim, h_up, d_up, flag_off, stream)) return rc;
                     uint4 *d_out = reinterpret_cast<uint4 *>(d_up + out_off);
                     HIP_TRY(scd::launch_batch_gkr_eval(d_rec, n, dim, d_out, 3, stream));
                     scd::EvalBatchArgs A; // f2 at u and f3 at v: 2 n tables of dim variables, points inside the instance's g | u | v

@@ -1,18 +1,20 @@
-// batch_round.hpp -- the round body of the batched kernels: one block holds ALL tables of an instance in LDS as nine 29-bit limbs and
-// runs a sumcheck round out of them -- the poll of the instance's own mailbox slot (the poll is the fetch), the bind in place, the sums
-// per (product, node) combination, the block reduction, finalize_message from the instance's matrices and the publication as
-// self-validating words (limb | tag << 32).  Used by k_batch_proofs (kernels_batch.hip: sc_ml_prove_batch) and by k_batch_gkr
-// (kernels_batch_gkr.hip: sc_gkr_prove_batch), which runs it twice per instance over tables it has built in LDS itself; k_batch_round
-// (kernels_batch_rounds.hip: sc_batch_prove_round) runs ONE round of it per launch and uses neither the poll nor the tagged words.
+// batch_round.hpp -- the LDS-resident round body: a block holds tables in LDS as nine 29-bit limbs and runs a sumcheck round out of
+// them -- the bind in place, the sums per (product, node) combination with their lane mapping, and the block's metadata prologue.
+// Used by k_tail_slices (kernels_tail.hip: the hot path of every proof), whose blocks hold a SLICE of every table, fetch their challenge
+// in three ways of their own and hand their sums to block 0; and by the batched kernels, whose blocks hold ALL tables of an instance and
+// add (BtBlock) the poll of the instance's own mailbox slot (the poll is the fetch), finalize_message from the instance's matrices and the
+// publication as self-validating words (limb | tag << 32): k_batch_proofs (kernels_batch.hip: sc_ml_prove_batch), k_batch_gkr
+// (kernels_batch_gkr.hip: sc_gkr_prove_batch), which runs it twice per instance over tables it has built in LDS itself, and k_batch_round
+// (kernels_batch_rounds.hip: sc_batch_prove_round), which runs ONE round per launch and uses neither the poll nor the tagged words.
 #pragma once
 #include "finalize_device.hpp"
 #include "kernel_common.hpp"
 
 namespace scd {
 
-// (an element in LDS: k_tail_slices' 48-byte slot)
-constexpr int kBtEnt = 12;
-constexpr size_t kBtLdsMax = 144 * 1024; // k_tail_slices' budget (kTsLdsMax): of the CU's 160 KB
+// an element in LDS: nine limbs in a 48-byte, 16-byte aligned slot (three ds_read_b128 / ds_write_b128 instead of nine 32-bit accesses)
+constexpr int kBtEnt = 12;               // dwords per entry
+constexpr size_t kBtLdsMax = 144 * 1024; // a launch's dynamic LDS: of the CU's 160 KB (k_tail_slices: one block per CU; its static LDS is ~3 KB)
 __device__ __forceinline__ Fe bt_lds_load(const int32_t *t) {
     const int4 a = *reinterpret_cast<const int4 *>(t), b = *reinterpret_cast<const int4 *>(t + 4), c = *reinterpret_cast<const int4 *>(t + 8);
     Fe r;
@@ -31,6 +33,23 @@ __device__ __forceinline__ Fe bt_shfl_down(const Fe &a, const int off) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) r.l[i] = __shfl_down(a.l[i], off, 64);
     return r;
+}
+
+// the launch's metadata -> the block's __shared__ copies, with the product every combination belongs to (visible behind the caller's next barrier)
+__device__ __forceinline__ void bt_load_meta(const ComboMeta &meta, const FinMeta &fin, const int n_combos, const int K, Combo *combo_sh, uint32_t *slot_table_sh, uint32_t *slot_exp_sh,
+                                             int *prod_index_sh) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kMetaCombos; i += kTsBlock) {
+        combo_sh[i] = meta.combo[i];
+        int k = 0;
+        if (i < n_combos)
+            while (k < K - 1 && fin.prod[k].partial_off != meta.combo[i].partial_off) ++k;
+        prod_index_sh[i] = k;
+    }
+    for (int i = tid; i < kMetaSlots; i += kTsBlock) {
+        slot_table_sh[i] = meta.slot_table[i];
+        slot_exp_sh[i] = meta.slot_exp[i];
+    }
 }
 
 // what the round body needs of the block and of the instance it holds (every member wave-uniform)
@@ -60,6 +79,21 @@ struct BtLane {
     uint32_t my_base[kSlots], my_exp[kSlots];
 };
 
+// the eight tagged words (limb << 32 | tag) lanes 0 .. 7 of wavefront 0 hold -> the challenge's four 64-bit limbs in r_sh (all 64 lanes call)
+__device__ __forceinline__ void bt_challenge_words(const uint64_t w, uint64_t *r_sh) {
+    const int tid = threadIdx.x;
+    const uint32_t lo32 = (uint32_t)(w >> 32);
+    const uint32_t hi32 = __shfl_down(lo32, 1, 64);
+    if (tid < 8 && (tid & 1) == 0) r_sh[tid >> 1] = (uint64_t)lo32 | ((uint64_t)hi32 << 32);
+}
+// the carry-free bind's multiplier from the challenge in r_sh: r * 2^5 as 29-bit limbs
+__device__ __forceinline__ FeU bt_bind_multiplier(const uint64_t *r_sh) {
+    FrHost rh;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rh.l[i] = r_sh[i];
+    return feu_shl5(fru_from_host(rh).v);
+}
+
 // The challenge behind the message published under `want`: the poll is the fetch (eight tagged words).  false: the wait expired, or the
 // host asked the block to drop the instance -- uniform; the give-up marker is raised (expired wait only) and every lane has passed
 // the barrier behind the stop word.  true: the challenge is in B.r_sh.
@@ -81,9 +115,7 @@ __device__ __forceinline__ bool bt_fetch_challenge(const BtBlock &B, const uint3
             __hip_atomic_store(B.h_giveup, want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             *B.stop_sh = 1;
         }
-        const uint32_t lo32 = (uint32_t)(w >> 32);
-        const uint32_t hi32 = __shfl_down(lo32, 1, 64);
-        if (tid < 8 && (tid & 1) == 0) B.r_sh[tid >> 1] = (uint64_t)lo32 | ((uint64_t)hi32 << 32);
+        bt_challenge_words(w, B.r_sh);
     }
     __syncthreads();
     if (*B.stop_sh) { // (uniform: the whole block drops the instance and takes the next ticket)
@@ -93,25 +125,27 @@ __device__ __forceinline__ bool bt_fetch_challenge(const BtBlock &B, const uint3
     return true;
 }
 
-// bind in place with the challenge in B.r_sh: entry e <- entries 2e, 2e + 1 of every table.  A pass reads everything it needs before it
-// writes (one barrier); later passes read higher entries than any earlier pass wrote (2 e'' > e for e'' > e).
-__device__ __forceinline__ void bt_bind(const BtBlock &B, uint32_t &E) {
+// bind in place: entry e <- entries 2e, 2e + 1 of each of the T.U tables (T.tabs: [table][T.cap][kBtEnt]), E entries held.  A pass reads
+// everything it needs before it writes (one barrier); later passes read higher entries than any earlier pass wrote (2 e'' > e for e'' > e).
+// canonical (wave-uniform): the results are stored reduced below p (k_tail_slices' wide lists: line_needs_canonical, kernels.h).
+// Tabs: whatever has tabs, cap and U -- a BtBlock, or k_tail_slices' three words.  They are read through the reference, not passed by value:
+// with values the batched kernels' instruction schedule moved and a lone instance's proof took 0.5 to 1.5 us longer; this form compiles
+// to the code they had (profiles/lds_round_body_ab.txt).
+template <typename Tabs>
+__device__ __forceinline__ void bt_bind_pass(const Tabs &T, uint32_t &E, const FeU &r32, const bool canonical) {
     const int tid = threadIdx.x;
-    FrHost rh;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rh.l[i] = B.r_sh[i];
-    const FeU r32 = feu_shl5(fru_from_host(rh).v); // the carry-free bind's multiplier: r * 2^5 as 29-bit limbs
-    const uint32_t half = E / 2, total = half * (uint32_t)B.U;
-    const int shH = 31 - __builtin_clz(half);
+    const uint32_t half = E / 2, total = half * (uint32_t)T.U;
+    const int shH = 31 - __builtin_clz(half); // (a power of two: no integer divisions on a latency-bound path)
     for (uint32_t i0 = 0; i0 < total; i0 += kTsBlock) {
         const uint32_t i = i0 + tid;
         const bool live = i < total;
         const uint32_t u = live ? i >> shH : 0, e = live ? i & (half - 1) : 0;
-        int32_t *const tab = B.tabs + u * B.cap * (uint32_t)kBtEnt; // (32-bit index arithmetic: LDS)
+        int32_t *const tab = T.tabs + u * T.cap * (uint32_t)kBtEnt; // (32-bit index arithmetic: LDS)
         Fe v = fe_zero();
         if (live) {
             const Fe lo = bt_lds_load(tab + 2 * e * (uint32_t)kBtEnt), hi = bt_lds_load(tab + (2 * e + 1) * (uint32_t)kBtEnt);
             v = fe_carry_pass(fe_add(lo, fe_mul_u<true>(fe_sub(hi, lo), r32)));
+            if (canonical) v = fe_from_fr(fe_to_fr(v));
         }
         __syncthreads();
         if (live) bt_lds_store(tab + e * (uint32_t)kBtEnt, v);
@@ -119,6 +153,36 @@ __device__ __forceinline__ void bt_bind(const BtBlock &B, uint32_t &E) {
     E = half;
     __syncthreads();
 }
+// ... with the challenge in B.r_sh
+__device__ __forceinline__ void bt_bind(const BtBlock &B, uint32_t &E) { bt_bind_pass(B, E, bt_bind_multiplier(B.r_sh), false); }
+
+// The product of a combination's lines at a pair, as bt_combo_sum's prod_at: T.tabs is the LDS table area, per slot of the lane's combination
+// ln.my_base is the table's base (in entries) and ln.my_exp its multiplicity, nv the node's value.  A functor and not a __forceinline__
+// function, with T read through the reference, for bt_bind_pass' reason: operator() is inlined as the lambda it replaces was, and the
+// batched kernels keep the code they had.
+template <int kSlots, typename Tabs>
+struct BtPairProduct {
+    const Tabs &T;
+    const BtLane<kSlots> &ln;
+    const int32_t &nv;
+    __device__ Fe operator()(const uint32_t pr) const {
+        Fe prod = fe_zero();
+        bool first = true;
+#pragma unroll
+        for (int sl = 0; sl < kSlots; ++sl) {
+            if (ln.my_exp[sl] == 0) break; // (slots are dense: the first empty one ends the list)
+            const int32_t *lo_p = T.tabs + (ln.my_base[sl] + 2 * pr) * (uint32_t)kBtEnt;
+            Fe val;
+            if (nv == 0) val = bt_lds_load(lo_p);
+            else if (nv == 1) val = bt_lds_load(lo_p + kBtEnt);
+            else val = fe_line(bt_lds_load(lo_p), bt_lds_load(lo_p + kBtEnt), nv);
+            uint32_t k = 0;
+            if (first) { prod = val; k = 1; first = false; }
+            for (const uint32_t e = ln.my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
+        }
+        return prod;
+    }
+};
 
 // One combination's sum: lane q of the combination's L (a power of two, in one wavefront) adds the products of pairs q, q + L, ... lazily,
 // then a shuffle tree adds the L lanes; lane q == 0 returns the total (the others partial sums).  prod_at(pair) is the product.
@@ -132,7 +196,7 @@ __device__ __forceinline__ Fe bt_combo_sum(const bool live, const uint32_t q, co
         uint32_t iter = 0;
         for (uint32_t pr = q; pr < pairs_here; pr += (uint32_t)L, ++iter) {
             acc = fe_carry_pass(fe_add(acc, prod_at(pr)));
-            if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31; reached only beyond 32 L pairs)
+            if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31; reached only beyond 32 L pairs: L <= 8 at k_tail_slices' 256 pairs a block)
         }
     }
     if (reduce_lanes) acc = fe_from_fr(fe_to_fr(acc));
@@ -148,23 +212,7 @@ __device__ __forceinline__ void bt_sum_message(const BtBlock &B, const BtLane<kS
     // ---- sums: lane (combination, q) multiplies out the combination's pairs q, q + L, ... ----------------------------------------------
     const uint32_t pairs_here = E / 2;
     const int32_t nv = ln.my_nv;
-    const Fe acc = bt_combo_sum(ln.combo_live, (uint32_t)ln.my_q, B.L, pairs_here, lazy_sum_needs_reduce(pairs_here, worst_p), [&](const uint32_t pr) -> Fe {
-        Fe prod = fe_zero();
-        bool first = true;
-#pragma unroll
-        for (int sl = 0; sl < kSlots; ++sl) {
-            if (ln.my_exp[sl] == 0) break; // (slots are dense: the first empty one ends the list)
-            const int32_t *lo_p = B.tabs + (ln.my_base[sl] + 2 * pr) * (uint32_t)kBtEnt;
-            Fe val;
-            if (nv == 0) val = bt_lds_load(lo_p);
-            else if (nv == 1) val = bt_lds_load(lo_p + kBtEnt);
-            else val = fe_line(bt_lds_load(lo_p), bt_lds_load(lo_p + kBtEnt), nv);
-            uint32_t k = 0;
-            if (first) { prod = val; k = 1; first = false; }
-            for (const uint32_t e = ln.my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
-        }
-        return prod;
-    });
+    const Fe acc = bt_combo_sum(ln.combo_live, (uint32_t)ln.my_q, B.L, pairs_here, lazy_sum_needs_reduce(pairs_here, worst_p), BtPairProduct<kSlots, BtBlock>{B, ln, nv});
     if (ln.combo_live && ln.my_q == 0) fr_store(B.fin_lds + 2 * (B.prod_index_sh[ln.my_combo] * B.D + (int)B.combo_sh[ln.my_combo].t), fe_to_fr(acc));
     __syncthreads();
     // ---- the message, from the instance's own matrices, into LDS -----------------------------------------------------------------------
@@ -184,23 +232,28 @@ __device__ __forceinline__ void bt_sum_publish(const BtBlock &B, const BtLane<kS
     __syncthreads(); // (fin_lds and msg_lds are written again by the next round)
 }
 
-// the lane's combination, from the block's copy of the metadata (call behind the barrier that follows the copy)
+// the lane's combination, from the block's copy of the metadata (call behind the barrier that follows the copy): its node and, per slot,
+// the table's LDS base (in entries) and the multiplicity
 template <int kSlots>
-__device__ __forceinline__ BtLane<kSlots> bt_lane(const BtBlock &B, const uint32_t *slot_table_sh, const uint32_t *slot_exp_sh) {
+__device__ __forceinline__ BtLane<kSlots> bt_lane(const int L, const int n_combos, const uint32_t cap, const Combo *combo_sh, const uint32_t *slot_table_sh, const uint32_t *slot_exp_sh) {
     BtLane<kSlots> ln;
     const int tid = threadIdx.x;
-    ln.my_combo = tid / B.L;
-    ln.my_q = tid % B.L;
-    ln.combo_live = ln.my_combo < B.n_combos;
-    const Combo my_c = B.combo_sh[ln.combo_live ? ln.my_combo : 0];
+    ln.my_combo = tid / L;
+    ln.my_q = tid % L;
+    ln.combo_live = ln.my_combo < n_combos;
+    const Combo my_c = combo_sh[ln.combo_live ? ln.my_combo : 0];
     ln.my_nv = node_value((int)my_c.t);
 #pragma unroll
     for (int sl = 0; sl < kSlots; ++sl) {
         const bool in = (uint32_t)sl < my_c.n_slots;
-        ln.my_base[sl] = in ? slot_table_sh[my_c.slot_off + sl] * B.cap : 0u;
+        ln.my_base[sl] = in ? slot_table_sh[my_c.slot_off + sl] * cap : 0u;
         ln.my_exp[sl] = in ? slot_exp_sh[my_c.slot_off + sl] : 0u;
     }
     return ln;
+}
+template <int kSlots>
+__device__ __forceinline__ BtLane<kSlots> bt_lane(const BtBlock &B, const uint32_t *slot_table_sh, const uint32_t *slot_exp_sh) {
+    return bt_lane<kSlots>(B.L, B.n_combos, B.cap, B.combo_sh, slot_table_sh, slot_exp_sh);
 }
 
 // eq(point, .) over dim variables into out[2^dim] (32-byte elements in LDS): precompute_eq's doubling (ark-poly: dp[b + 2^i] = dp[b] * g_i ;

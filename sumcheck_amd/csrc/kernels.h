@@ -197,6 +197,12 @@ struct TailArgs {
 // The same rounds with the tables resident in LDS (kernels_tail.hip: k_tail_slices): block g of B owns a contiguous range of every
 // table for the whole launch; one hand-over per round (its sums -> block 0) as self-validating words in `xw`.
 constexpr int kTsBlock = 256, kTsMaxBlocks = 256;
+// lanes per (product, node) combination of the LDS-resident round body (batch_round.hpp): a power of two, all of a combination's lanes in one wavefront
+__host__ __device__ constexpr int bt_lanes(int n_combos) {
+    int L = 64;
+    while (L * n_combos > kTsBlock) L >>= 1;
+    return L;
+}
 // (kLazySumMaxP and lazy_sum_needs_reduce, the rule of every lazy sum: lane_sum.hpp)
 // A line through two lazy entries leaves the entries' range: entries in (-(w - 1) p, p) put node x > 0 (x - 1 slopes beyond hi) and node -x
 // (x slopes beyond lo) within (n w - 1) p, n = ceil(D / 2) for a list of degree D.  A product is the chain prod = fe_mul(line, prod), and a

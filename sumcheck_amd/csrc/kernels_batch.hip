@@ -29,17 +29,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_proofs(const BatchArgs A, co
     const int tid = threadIdx.x;
     const int U = (int)A.n_tables;
     const uint32_t cap = 1u << A.nv; // entries per table
-    for (int i = tid; i < kMetaCombos; i += kTsBlock) {
-        combo_sh[i] = meta.combo[i];
-        int k = 0;
-        if (i < A.n_combos)
-            while (k < A.K - 1 && fin.prod[k].partial_off != meta.combo[i].partial_off) ++k;
-        prod_index_sh[i] = k;
-    }
-    for (int i = tid; i < kMetaSlots; i += kTsBlock) {
-        slot_table_sh[i] = meta.slot_table[i];
-        slot_exp_sh[i] = meta.slot_exp[i];
-    }
+    bt_load_meta(meta, fin, A.n_combos, A.K, combo_sh, slot_table_sh, slot_exp_sh, prod_index_sh);
     auto prod_of = [&](int k) -> FinProd { return fin.prod[k]; };
     BtBlock B;
     B.fin_lds = dyn_lds;                                                                                                      // finalize_message's scratch
@@ -56,9 +46,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_proofs(const BatchArgs A, co
     B.D = A.D;
     B.mail_local = A.mail_local;
     B.max_spins = A.max_spins;
-    // lanes per (product, node) combination: a power of two, all of a combination's lanes in one wavefront
-    B.L = 64;
-    while (B.L * A.n_combos > kTsBlock) B.L >>= 1;
+    B.L = bt_lanes(A.n_combos);
     __syncthreads(); // (the metadata above)
     const BtLane<kSlots> ln = bt_lane<kSlots>(B, slot_table_sh, slot_exp_sh);
     const uint32_t msg_words = (uint32_t)A.D * 8u;

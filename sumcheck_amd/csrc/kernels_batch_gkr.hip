@@ -60,14 +60,6 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, co
     __shared__ uint4 g_sh[2 * kGkrBatchMaxDim], u_sh[2 * kGkrBatchMaxDim]; // the points g and u
     const int tid = threadIdx.x;
     const uint32_t dim = A.dim, cap = 1u << dim;
-    for (int i = tid; i < kMetaCombos; i += kTsBlock) {
-        combo_sh[i] = meta.combo[i];
-        prod_index_sh[i] = 0; // (one product)
-    }
-    for (int i = tid; i < kMetaSlots; i += kTsBlock) {
-        slot_table_sh[i] = meta.slot_table[i];
-        slot_exp_sh[i] = meta.slot_exp[i];
-    }
     auto prod_of = [&](int k) -> FinProd { return fin.prod[k]; };
     // dynamic LDS: finalize scratch | message | tables 0, 1 (48 B per entry) | eq(g, .) | eq(u, .) (32 B per cell) | the accumulator (64 B per cell)
     char *const lds = reinterpret_cast<char *>(dyn_lds);
@@ -87,10 +79,11 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, co
     B.n_combos = 3;
     B.K = 1;
     B.D = 3;
-    B.L = 64; // three combinations of 64 lanes
+    B.L = bt_lanes(B.n_combos); // (three combinations of 64 lanes)
     B.mail_local = A.mail_local;
     B.max_spins = A.max_spins;
     B.Wm = A.Wm; // a coefficient of one: the same matrices for every instance
+    bt_load_meta(meta, fin, B.n_combos, B.K, combo_sh, slot_table_sh, slot_exp_sh, prod_index_sh); // (K = 1: every prod_index is 0)
     __syncthreads(); // (the metadata above)
     const BtLane<kSlots> ln = bt_lane<kSlots>(B, slot_table_sh, slot_exp_sh);
     int32_t *const tab0 = B.tabs, *const tab1 = B.tabs + cap * (uint32_t)kBtEnt;

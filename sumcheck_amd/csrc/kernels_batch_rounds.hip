@@ -40,17 +40,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_round(const BatchRoundArgs A
     const uint32_t cap = 1u << A.nv;                                 // entries per table in round 0
     const uint32_t E_in = A.round ? cap >> (A.round - 1u) : cap;     // entries per table as loaded: the tables bound max(round - 1, 0) times
     const int shE = (int)A.nv - (A.round ? (int)A.round - 1 : 0);    // log2 E_in
-    for (int i = tid; i < kMetaCombos; i += kTsBlock) {
-        combo_sh[i] = meta.combo[i];
-        int k = 0;
-        if (i < A.n_combos)
-            while (k < A.K - 1 && fin.prod[k].partial_off != meta.combo[i].partial_off) ++k;
-        prod_index_sh[i] = k;
-    }
-    for (int i = tid; i < kMetaSlots; i += kTsBlock) {
-        slot_table_sh[i] = meta.slot_table[i];
-        slot_exp_sh[i] = meta.slot_exp[i];
-    }
+    bt_load_meta(meta, fin, A.n_combos, A.K, combo_sh, slot_table_sh, slot_exp_sh, prod_index_sh);
     if (tid < 4) r_sh[tid] = A.round ? reinterpret_cast<const uint64_t *>(A.chal)[(A.chal_shared ? 0 : (size_t)inst * 4) + tid] : 0;
     if (tid == 0) stop_sh = 0;
     auto prod_of = [&](int k) -> FinProd { return fin.prod[k]; };
@@ -73,8 +63,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_round(const BatchRoundArgs A
     B.mail = nullptr;
     B.h_msg = nullptr;
     B.h_giveup = nullptr;
-    B.L = 64;
-    while (B.L * A.n_combos > kTsBlock) B.L >>= 1;
+    B.L = bt_lanes(A.n_combos);
     // ---- the instance's current entries -> LDS, slot by slot ------------------------------------------------------------------------------
     int32_t *const region = A.work + (size_t)inst * A.n_tables * 2 * cap * kBtEnt; // table u at + u * 2 * cap slots
     {

@@ -17,8 +17,9 @@
 // Same boundary as k_tail_rounds: the message of tail round j goes to the host-mapped page with sequence seq0 + j; the challenge of
 // round j >= 1 arrives in mailbox slot (sig0 + j) & 1 as eight words (limb << 32 | tag); every wait is bounded, and a block whose wait
 // expires raises the give-up marker (the host voids the proof) and the device-side stop word (the other blocks leave at their next poll).
-#include "finalize_device.hpp"
-#include "kernel_common.hpp"
+// The LDS slots, the bind in place, the sums and the lane mapping are batch_round.hpp's, shared with the batched kernels; what is here is
+// the tail's own: how a challenge arrives, the load of round 0, the merge of blocks, the hand-over to block 0 and the write-back.
+#include "batch_round.hpp"
 
 #include <algorithm>
 
@@ -26,27 +27,6 @@ namespace scd {
 
 constexpr uint32_t kTsStop = 3; // word of TailArgs::sync: non-zero = leave
 
-// an element in LDS: nine limbs in a 48-byte, 16-byte aligned slot (three ds_read_b128 / ds_write_b128 instead of nine 32-bit accesses)
-constexpr int kTsEnt = 12; // dwords per entry
-__device__ __forceinline__ Fe ts_lds_load(const int32_t *t) {
-    const int4 a = *reinterpret_cast<const int4 *>(t), b = *reinterpret_cast<const int4 *>(t + 4), c = *reinterpret_cast<const int4 *>(t + 8);
-    Fe r;
-    r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-    r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-    r.l[8] = c.x;
-    return r;
-}
-__device__ __forceinline__ void ts_lds_store(int32_t *t, const Fe &v) {
-    *reinterpret_cast<int4 *>(t) = make_int4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    *reinterpret_cast<int4 *>(t + 4) = make_int4(v.l[4], v.l[5], v.l[6], v.l[7]);
-    t[8] = v.l[8];
-}
-__device__ __forceinline__ Fe fe_shfl_down(const Fe &a, const int off) {
-    Fe r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.l[i] = __shfl_down(a.l[i], off, 64);
-    return r;
-}
 // Hand-over words ("granules"): value | tag << 32, eight bytes, self-validating.  They travel two at a time: ONE 16-byte write-through
 // (sc1) store per lane -- a narrower sc1 store is a fabric write of its own and costs 2.7x (8 B) to 6x (4 B) per byte -- and 16-byte sc1
 // loads, both through a buffer descriptor over the hand-over area (aux = 16 = sc1); an 8-byte half is never torn.
@@ -75,7 +55,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
     const TailArgs &A = S.base;
     extern __shared__ uint4 dyn_lds[];
     uint4 *fin_lds = dyn_lds;                                                                     // finalize_message's scratch
-    int32_t *tabs = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(dyn_lds) + S.fin_bytes); // [table][entry][kTsEnt]
+    int32_t *tabs = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(dyn_lds) + S.fin_bytes); // [table][entry][kBtEnt]
     __shared__ uint64_t r_sh[4];
     __shared__ uint32_t stop_sh;
     __shared__ Combo combo_sh[kMetaCombos];
@@ -87,20 +67,10 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
     uint32_t g = blockIdx.x, B = gridDim.x; // this block's index among the B blocks still at work (both shrink when blocks merge)
     const int U = A.n_tables;
     const uint32_t cap = S.lds_entries; // entries per table the LDS area holds
-    for (int i = tid; i < kMetaCombos; i += kTsBlock) {
-        combo_sh[i] = meta.combo[i];
-        int k = 0;
-        if (i < A.n_combos)
-            while (k < A.K - 1 && fin.prod[k].partial_off != meta.combo[i].partial_off) ++k;
-        prod_index_sh[i] = k;
-    }
-    for (int i = tid; i < kMetaSlots; i += kTsBlock) {
-        slot_table_sh[i] = meta.slot_table[i];
-        slot_exp_sh[i] = meta.slot_exp[i];
-    }
+    bt_load_meta(meta, fin, A.n_combos, A.K, combo_sh, slot_table_sh, slot_exp_sh, prod_index_sh);
     if (tid == 0) stop_sh = 0;
     auto prod_of = [&](int k) -> FinProd { return fin.prod[k]; };
-    auto tab_at = [&](int u, uint32_t e) -> int32_t * { return tabs + ((uint32_t)u * cap + e) * (uint32_t)kTsEnt; }; // (32-bit index arithmetic: LDS)
+    auto tab_at = [&](int u, uint32_t e) -> int32_t * { return tabs + ((uint32_t)u * cap + e) * (uint32_t)kBtEnt; }; // (32-bit index arithmetic: LDS)
     const uint32_t wait_spins = A.max_spins > (1u << 20) ? A.max_spins : (1u << 20); // hand-overs between blocks: bounded, but never by the patience for the host
     uint32_t *stop_word = A.sync + kTsStop;
     uint32_t *giveup = A.sig + 1;
@@ -108,23 +78,11 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
         __hip_atomic_store(giveup, marker, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(stop_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
-    // lanes per (product, node) combination: a power of two, all of a combination's lanes in one wavefront
-    int L = 64;
-    while (L * A.n_combos > kTsBlock) L >>= 1;
-    const int my_combo = tid / L, my_q = tid % L;
-    const bool combo_live = my_combo < A.n_combos;
+    const int L = bt_lanes(A.n_combos);
     const uint32_t wpb = (uint32_t)A.n_combos * 8; // words of a block's sums
     __syncthreads(); // (the metadata above)
-    // this lane's combination, once: its node and, per slot, the table's LDS base (in entries) and the multiplicity
-    const Combo my_c = combo_sh[combo_live ? my_combo : 0];
-    const int32_t my_nv = node_value((int)my_c.t);
-    uint32_t my_base[kSlots], my_exp[kSlots];
-#pragma unroll
-    for (int sl = 0; sl < kSlots; ++sl) {
-        const bool in = (uint32_t)sl < my_c.n_slots;
-        my_base[sl] = in ? slot_table_sh[my_c.slot_off + sl] * cap : 0u;
-        my_exp[sl] = in ? slot_exp_sh[my_c.slot_off + sl] : 0u;
-    }
+    const BtLane<kSlots> ln = bt_lane<kSlots>(L, A.n_combos, cap, combo_sh, slot_table_sh, slot_exp_sh);
+    const struct { int32_t *tabs; uint32_t cap; int U; } T = {tabs, cap, U}; // (what bt_bind_pass and BtPairProduct read of a block)
 
     uint64_t n_pairs = A.first_pairs; // pairs of the round in hand, over all blocks
     uint32_t E = 0;                   // entries per table this block holds
@@ -194,9 +152,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
                     give_up(want);
                     stop_sh = 1;
                 }
-                const uint32_t lo32 = (uint32_t)(w >> 32);
-                const uint32_t hi32 = __shfl_down(lo32, 1, 64);
-                if (tid < 8 && (tid & 1) == 0) r_sh[tid >> 1] = (uint64_t)lo32 | ((uint64_t)hi32 << 32);
+                bt_challenge_words(w, r_sh);
             }
             __syncthreads();
             // no challenge (the interactive protocol's verifier took longer than the kernel's patience, or the host asked it to leave):
@@ -205,12 +161,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
         }
         TS_STAMP(j, 1); // challenge in hand
         FeU r32;
-        if (has_bind) {
-            FrHost rh;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) rh.l[i] = r_sh[i];
-            r32 = feu_shl5(fru_from_host(rh).v); // the carry-free bind's multiplier: r * 2^5 as 29-bit limbs
-        }
+        if (has_bind) r32 = bt_bind_multiplier(r_sh);
         // ---- the slice: loaded from the caller's / the big rounds' tables in round 0 (bound on the way in), bound in place afterwards ----
         if (j == 0) {
             E = (uint32_t)((2 * n_pairs) / B); // entries per table and block of THIS round's tables
@@ -237,32 +188,13 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
                     v = sf29 ? fe_load_f29(src, ge) : fe_from_fr(fr_load(src + 2 * ge));
                 }
                 if (canonical) v = fe_from_fr(fe_to_fr(v));
-                ts_lds_store(tab_at((int)u, e), v);
+                bt_lds_store(tab_at((int)u, e), v);
             }
             if (has_bind) binds += 1;
             __syncthreads();
         } else {
-            // in place: entry e <- entries 2e, 2e + 1.  A pass reads everything it needs before it writes (one barrier); later passes
-            // read higher entries than any earlier pass wrote (2 e'' > e for e'' > e).
-            const uint32_t half = E / 2, total = half * (uint32_t)U;
-            const int shH = 31 - __builtin_clz(half);
-            const bool canonical = bind_stores_canonical(true);
-            for (uint32_t i0 = 0; i0 < total; i0 += kTsBlock) {
-                const uint32_t i = i0 + tid;
-                const bool live = i < total;
-                const uint32_t u = live ? i >> shH : 0, e = live ? i & (half - 1) : 0;
-                Fe v = fe_zero();
-                if (live) {
-                    const Fe lo = ts_lds_load(tab_at((int)u, 2 * e)), hi = ts_lds_load(tab_at((int)u, 2 * e + 1));
-                    v = fe_carry_pass(fe_add(lo, fe_mul_u<true>(fe_sub(hi, lo), r32)));
-                    if (canonical) v = fe_from_fr(fe_to_fr(v));
-                }
-                __syncthreads();
-                if (live) ts_lds_store(tab_at((int)u, e), v);
-            }
-            E = half;
+            bt_bind_pass(T, E, r32, bind_stores_canonical(true));
             binds += 1;
-            __syncthreads();
         }
         // ---- fewer pairs than blocks: groups of R adjacent blocks ship their last entry of every table to the group's first block
         // and leave; the survivors hold R entries each and carry on (R = 16, or all that are left) ----------------------------------------
@@ -326,46 +258,21 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
         }
         TS_STAMP(j, 2); // slice bound (and, where blocks merged, collected)
         // ---- sums: lane (combination, q) multiplies out the combination's pairs q, q + L, ... of this block ---------------------------
-        const uint32_t pairs_here = E / 2;
-        Fe acc = fe_zero();
-        if (combo_live) {
-            const int32_t nv = my_nv;
-            uint32_t iter = 0;
-            for (uint32_t pr = (uint32_t)my_q; pr < pairs_here; pr += (uint32_t)L, ++iter) {
-                Fe prod = fe_zero();
-                bool first = true;
-#pragma unroll
-                for (int sl = 0; sl < kSlots; ++sl) {
-                    if (my_exp[sl] == 0) break; // (slots are dense: the first empty one ends the list)
-                    const int32_t *lo_p = tabs + (my_base[sl] + 2 * pr) * (uint32_t)kTsEnt;
-                    Fe val;
-                    if (nv == 0) val = ts_lds_load(lo_p);
-                    else if (nv == 1) val = ts_lds_load(lo_p + kTsEnt);
-                    else val = fe_line(ts_lds_load(lo_p), ts_lds_load(lo_p + kTsEnt), nv);
-                    uint32_t k = 0;
-                    if (first) { prod = val; k = 1; first = false; }
-                    for (const uint32_t e = my_exp[sl]; k < e; ++k) prod = fe_mul<true>(val, prod);
-                }
-                acc = fe_carry_pass(fe_add(acc, prod));
-                if ((iter & 31u) == 31u) acc = fe_from_fr(fe_to_fr(acc)); // (keeps the top limb far from 2^31: reached where a lane has 32 pairs or more, L <= 8 at 256 pairs a block)
-            }
-        }
-        // one accumulator takes the block's whole sum of a combination after the tree: every lane's sum is made canonical first where pairs x
-        // (worst product in p) would leave its int32 top limb (kernels.h: kLazySumMaxP; wave-uniform; the bound grows by p with every bind)
-        if (lazy_sum_needs_reduce(pairs_here, S.worst_p + (uint32_t)j)) acc = fe_from_fr(fe_to_fr(acc));
-        for (int off = L >> 1; off >= 1; off >>= 1) acc = fe_carry_pass(fe_add(acc, fe_shfl_down(acc, off)));
+        const uint32_t pairs_here = E / 2; // (the worst product, S.worst_p p as loaded, grows by p with every bind)
+        const Fe acc = bt_combo_sum(ln.combo_live, (uint32_t)ln.my_q, L, pairs_here, lazy_sum_needs_reduce(pairs_here, S.worst_p + (uint32_t)j),
+                                    BtPairProduct<kSlots, decltype(T)>{T, ln, ln.my_nv});
         TS_STAMP(j, 3); // this block's sums
         if (B == 1) {
-            if (combo_live && my_q == 0) fr_store(fin_lds + 2 * (prod_index_sh[my_combo] * A.D + (int)combo_sh[my_combo].t), fe_to_fr(acc));
+            if (ln.combo_live && ln.my_q == 0) fr_store(fin_lds + 2 * (prod_index_sh[ln.my_combo] * A.D + (int)combo_sh[ln.my_combo].t), fe_to_fr(acc));
         } else {
             // ---- this block's sums -> block 0.  The canonical 32-bit words are ADDED, by the memory system, into 64-bit accumulators:
             // (1 << 44 | word) per block, so that a word whose top bits read the number of its contributors IS complete -- block 0's poll
             // of the accumulators is the fetch of the sums (a few hundred words whatever the number of blocks).  Eight groups of blocks
             // (g & 7) keep a sum below 32 p (fe_to_fr takes up to 282 p); a ring of four accumulator sets, the one of round j + 2 zeroed by block 0.
-            if (combo_live && my_q == 0) {
+            if (ln.combo_live && ln.my_q == 0) {
                 const Fr sv = fe_to_fr(acc);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) part_sh[my_combo * 8 + i] = sv.v[i];
+                for (int i = 0; i < 8; ++i) part_sh[ln.my_combo * 8 + i] = sv.v[i];
             }
             __syncthreads();
             const uint32_t groups = B < 8u ? B : 8u, per_group = B / groups;
@@ -453,7 +360,7 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
         for (uint32_t i = tid; i < total; i += kTsBlock) {
             const uint32_t u = i >> shE, e = i & (E - 1);
             uint4 *dst = (binds & 1) ? A.t.b0[u] : A.t.b1[u];
-            fr_store(dst + 2 * ((uint64_t)g * E + e), fe_to_fr(ts_lds_load(tab_at((int)u, e))));
+            fr_store(dst + 2 * ((uint64_t)g * E + e), fe_to_fr(bt_lds_load(tab_at((int)u, e))));
         }
     }
 }
@@ -463,17 +370,15 @@ __global__ __launch_bounds__(kTsBlock) void k_tail_slices(const TailSlicesArgs S
 static size_t ts_lds_entries(uint64_t first_pairs, int B) { return (size_t)std::max<uint64_t>(2 * first_pairs / (uint64_t)B, B > 1 ? 16 : 0); }
 static size_t ts_fin_bytes(int K, int D) { return ((size_t)K * D * (D + 2) * 32 + 15) & ~(size_t)15; }
 static size_t ts_stage_bytes(int n_combos, int B) { return B > 1 ? 8 * (size_t)n_combos * 64 + 8 * (size_t)n_combos * 32 + 16 : 0; }
-constexpr size_t kTsLdsMax = 144 * 1024; // of the CU's 160 KB (one block per CU; its static LDS is ~3 KB)
 
 int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_combos, int max_multiplicands, int max_blocks, uint32_t worst_p) {
     if (max_blocks < 1) return 0;
     if (first_pairs == 0 || (first_pairs & (first_pairs - 1)) != 0 || first_pairs > kTsMaxPairs) return 0;
+    const int L = bt_lanes(n_combos);
     if (first_pairs > kSmallRoundPairs) {
         // Above the big / small round boundary the fused tree kernels stream the tables at memory speed; a resident block, one wavefront
         // per SIMD, beats them only while its lanes have few dependent products in a row: passes over its pairs x multiplicands <= 12
         // (config 2's and the GKR phases' shapes up to 2^16 pairs, two products of three up to 2^15; config 3's shape not at all).
-        int L = 64;
-        while (L * n_combos > kTsBlock) L >>= 1;
         const uint64_t pairs_b = first_pairs / kTsMaxBlocks, passes = (pairs_b + L - 1) / L;
         if (passes * (uint64_t)max_multiplicands > 12) return 0;
     }
@@ -484,14 +389,10 @@ int tail_slices_blocks(uint64_t first_pairs, int n_tables, int K, int D, int n_c
     while (B > max_blocks) B >>= 1; // (every block must be resident: they hand over to each other)
     // a lane adds its share of a combination's products lazily and reduces its sum every 32 of them (and, by lazy_sum_needs_reduce, in front
     // of the shuffle tree): up to 33 terms of worst_p p each meet in its int32 top limb, which holds kLazySumMaxP p
-    {
-        int L = 64;
-        while (L * n_combos > kTsBlock) L >>= 1;
-        const uint64_t passes = (first_pairs / (uint64_t)B + L - 1) / L;
-        if (lazy_sum_needs_reduce(std::min<uint64_t>(passes, 32) + 1, worst_p)) return 0;
-    }
-    const size_t bytes = ts_fin_bytes(K, D) + ts_lds_entries(first_pairs, B) * (size_t)n_tables * (kTsEnt * 4) + ts_stage_bytes(n_combos, B);
-    return bytes <= kTsLdsMax ? B : 0; // (more blocks than kTsMaxBlocks would be needed: the caller runs this round as launches and asks again)
+    const uint64_t passes = (first_pairs / (uint64_t)B + L - 1) / L;
+    if (lazy_sum_needs_reduce(std::min<uint64_t>(passes, 32) + 1, worst_p)) return 0;
+    const size_t bytes = ts_fin_bytes(K, D) + ts_lds_entries(first_pairs, B) * (size_t)n_tables * (kBtEnt * 4) + ts_stage_bytes(n_combos, B);
+    return bytes <= kBtLdsMax ? B : 0; // (more blocks than kTsMaxBlocks would be needed: the caller runs this round as launches and asks again)
 }
 
 hipError_t ensure_dynamic_lds(const void *kernel, int bytes, bool (&done)[64]) {
@@ -507,7 +408,7 @@ hipError_t ensure_dynamic_lds(const void *kernel, int bytes, bool (&done)[64]) {
 template <int kSlots>
 static hipError_t tail_slices_attr() { // (more dynamic LDS than the default 64 KB limit of a launch)
     static bool done[64] = {};
-    return ensure_dynamic_lds(reinterpret_cast<const void *>(k_tail_slices<kSlots>), (int)kTsLdsMax, done);
+    return ensure_dynamic_lds(reinterpret_cast<const void *>(k_tail_slices<kSlots>), (int)kBtLdsMax, done);
 }
 template <int kSlots>
 static int tail_slices_max_blocks_t(int device) {
@@ -517,7 +418,7 @@ static int tail_slices_max_blocks_t(int device) {
     int per_cu = 0;
     hipDeviceProp_t prop;
     if (tail_slices_attr<kSlots>() != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tail_slices<kSlots>, kTsBlock, kTsLdsMax) != hipSuccess || per_cu < 1 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tail_slices<kSlots>, kTsBlock, kBtLdsMax) != hipSuccess || per_cu < 1 ||
         hipGetDeviceProperties(&prop, device) != hipSuccess || prop.multiProcessorCount < 1) {
         (void)hipGetLastError();
         c = -1;
@@ -542,9 +443,9 @@ hipError_t launch_tail_slices(TailSlicesArgs args, const ComboMeta &meta, const 
     if (B < 1 || B > kTsMaxBlocks || (B & (B - 1)) != 0) return hipErrorInvalidValue;
     args.fin_bytes = (uint32_t)ts_fin_bytes(args.base.K, args.base.D);
     args.lds_entries = (uint32_t)ts_lds_entries(args.base.first_pairs, B);
-    args.stage_off = (uint32_t)((args.fin_bytes + (size_t)args.lds_entries * args.base.n_tables * (kTsEnt * 4) + 15) & ~(size_t)15);
+    args.stage_off = (uint32_t)((args.fin_bytes + (size_t)args.lds_entries * args.base.n_tables * (kBtEnt * 4) + 15) & ~(size_t)15);
     const size_t lds = args.stage_off + ts_stage_bytes(args.base.n_combos, B);
-    if (lds > kTsLdsMax) return hipErrorInvalidValue;
+    if (lds > kBtLdsMax) return hipErrorInvalidValue;
     if (max_multiplicands > kMaxWideM) return hipErrorInvalidValue;
     return max_multiplicands > kMaxFusedM ? launch_tail_slices_t<kMaxWideM>(args, meta, fin, lds, stream) : launch_tail_slices_t<kMaxFusedM>(args, meta, fin, lds, stream);
 }

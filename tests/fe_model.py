@@ -276,7 +276,7 @@ def bind_f29(lo, hi, r_std: int):
 
 
 def bind_lds(lo, hi, r_mont: int):
-    """bt_bind's and k_tail_slices' bind in LDS: lo + fe_mul_u(hi - lo, 32 r), r the challenge as stored (Montgomery form), one carry pass"""
+    """bt_bind_pass (batch_round.hpp: bt_bind's and k_tail_slices' bind in LDS): lo + fe_mul_u(hi - lo, 32 r), r the challenge as stored (Montgomery form), one carry pass"""
     return carry_pass(fe_add(lo, fe_shl5_mul_u(fe_sub(hi, lo), r_mont)))
 
 
@@ -338,13 +338,13 @@ def selector_table(nv: int, s, sel: int, m: int, c: int, flip: bool = False):
     return [P - 1 if (x >> sel) & 1 == const_bit else half[(x & lo_mask) | ((x >> (sel + 1)) << sel)] for x in range(1 << nv)]
 
 
-# ---- every factor of a product at its range end at once: the product loop of k_tail_slices and bt_sum_message -------------------
+# ---- every factor of a product at its range end at once: BtPairProduct, the product loop of k_tail_slices and bt_sum_message --
 MAX_WIDE_M = 12             # kernels.h: kMaxWideM
 LINE_REACH_MAX_P = 70       # kernels.h: kLineReachMaxP = floor(2^261 / p)
 
 
 def product_chain(vals, strict: bool = True):
-    """kernels_tail.hip's and bt_sum_message's product loop: the first factor is handed on as the running product, every further one is
+    """BtPairProduct (batch_round.hpp: the one product loop of k_tail_slices and bt_sum_message): the first factor is handed on as the running product, every further one is
     fe_mul(val, prod) -- val the FIRST operand (BOX_MUL_A), the running product the SECOND (BOX_MUL_B), every result an int32 vector.
     A multiplicity e is the same value e times in `vals` (the exponent loop).  -> (product, peak |fe_mul result|, what was left: a set of
     "mul_a", "mul_b", "int32"); strict: leaving anything is an AssertionError"""
