@@ -634,6 +634,85 @@ struct GKRRoundSumcheckSubClaim {
     }
 };
 
+// n x the two prover states of GKRRoundSumcheck::prove of ONE dim behind one sc_gkr_batch_prover handle (GKRRoundSumcheck::prover_init_batch):
+// the interactive rounds under the caller's transcript.  2 dim calls of prove_round -- phase one's messages, then phase two's --, then finish.
+class GKRBatchProverState {
+  public:
+    size_t n = 0, dim = 0;
+    struct Final { // per instance, from finish: the subclaim's oracle values at no extra pass
+        std::vector<Fr> u, v;
+        Fr f1_guv, f2_u, f2u_f3v; // f1(g,u,v), f2(u), f2(u) f3(v); f1_guv * f2u_f3v is the verifier's expected evaluation
+    };
+    GKRBatchProverState() = default;
+    GKRBatchProverState(sc_gkr_batch_prover *h, size_t n_, size_t dim_) : n(n_), dim(dim_), h_(h) {}
+    GKRBatchProverState(GKRBatchProverState &&o) noexcept { *this = std::move(o); }
+    GKRBatchProverState &operator=(GKRBatchProverState &&o) noexcept {
+        if (h_) sc_gkr_batch_prover_free(h_);
+        n = o.n;
+        dim = o.dim;
+        h_ = o.h_;
+        o.h_ = nullptr;
+        return *this;
+    }
+    ~GKRBatchProverState() {
+        if (h_) sc_gkr_batch_prover_free(h_);
+    }
+    // one message per instance.  v_msgs: empty exactly on the first call; afterwards one VerifierMsg per instance, or a single one for all
+    std::vector<ProverMsg> prove_round(const std::vector<VerifierMsg> &v_msgs = {}) {
+        std::vector<Fr> r, flat(std::max<size_t>(n, 1) * 3);
+        if (!v_msgs.empty()) r = challenges(v_msgs);
+        check(sc_gkr_batch_prove_round(h_, r.empty() ? nullptr : r[0].l, v_msgs.size() == 1 && n != 1 ? 1u : 0u, flat[0].l));
+        std::vector<ProverMsg> out;
+        for (size_t i = 0; i < n; ++i) out.push_back(ProverMsg{std::vector<Fr>(flat.begin() + 3 * i, flat.begin() + 3 * i + 3)});
+        return out;
+    }
+    // the last challenge v_{dim-1}, after 2 dim rounds; the handle is exhausted until reset
+    std::vector<Final> finish(const std::vector<VerifierMsg> &v_msgs) {
+        const std::vector<Fr> r = challenges(v_msgs);
+        std::vector<Fr> uv(std::max<size_t>(n * 2 * dim, 1)), fin(std::max<size_t>(n, 1) * 3);
+        check(sc_gkr_batch_prover_finish(h_, r[0].l, v_msgs.size() == 1 && n != 1 ? 1u : 0u, uv[0].l, fin[0].l));
+        std::vector<Final> out(n);
+        for (size_t i = 0; i < n; ++i) {
+            out[i].u.assign(uv.begin() + i * 2 * dim, uv.begin() + i * 2 * dim + dim);
+            out[i].v.assign(uv.begin() + i * 2 * dim + dim, uv.begin() + (i + 1) * 2 * dim);
+            out[i].f1_guv = fin[3 * i];
+            out[i].f2_u = fin[3 * i + 1];
+            out[i].f2u_f3v = fin[3 * i + 2];
+        }
+        return out;
+    }
+    size_t round() const {
+        uint32_t r = 0;
+        check(sc_gkr_batch_prover_state(h_, 0, nullptr, nullptr, nullptr, &r));
+        return r;
+    }
+    std::vector<Fr> randomness(size_t i) const { // u followed by the v's received so far
+        std::vector<Fr> buf(std::max<size_t>(2 * dim, 1));
+        uint32_t cnt = 0;
+        check(sc_gkr_batch_prover_state(h_, (uint32_t)i, buf[0].l, &cnt, nullptr, nullptr));
+        buf.resize(cnt);
+        return buf;
+    }
+    std::vector<DenseMultilinearExtension> tables(size_t i) const { // the current phase's two tables, canonical
+        const size_t t = round(), pr = t > dim ? t - dim : t, nv = dim - (pr > 0 ? pr - 1 : 0);
+        std::vector<Fr> buf(size_t(2) << nv);
+        check(sc_gkr_batch_prover_state(h_, (uint32_t)i, nullptr, nullptr, buf[0].l, nullptr));
+        return {DenseMultilinearExtension{nv, std::vector<Fr>(buf.begin(), buf.begin() + (size_t(1) << nv))},
+                DenseMultilinearExtension{nv, std::vector<Fr>(buf.begin() + (size_t(1) << nv), buf.end())}};
+    }
+    void reset() { check(sc_gkr_batch_prover_reset(h_)); }
+    sc_gkr_batch_prover *raw() { return h_; }
+    std::vector<Fr> challenges(const std::vector<VerifierMsg> &v_msgs) const {
+        if (v_msgs.size() != n && v_msgs.size() != 1) throw Panic(SC_ERR_BAD_ARG, "one VerifierMsg per instance, or a single one for all");
+        std::vector<Fr> r;
+        for (const VerifierMsg &m : v_msgs) r.push_back(m.randomness);
+        return r;
+    }
+
+  private:
+    sc_gkr_batch_prover *h_ = nullptr;
+};
+
 struct GKRRoundSumcheck {
     // verifier_init{max_multiplicands: 2} + (feed, verify_round) x dim + check_and_generate_subclaim (mod.rs:157-166, 173-182)
     static std::pair<std::vector<Fr>, Fr> verify_phase(Blake2b512Rng &rng, const Proof &msgs, size_t dim, const Fr &asserted_sum) {
@@ -725,6 +804,28 @@ struct GKRRoundSumcheck {
             for (size_t i = 0; i < n; ++i) (*uv_or_null)[i].assign(uv.begin() + i * 2 * dim, uv.begin() + (i + 1) * 2 * dim);
         }
         return out;
+    }
+    // n x the interactive prover of ONE dim behind one handle (sc_gkr_batch_prover_init): the caller owns the transcript.  Pointers may repeat.
+    static GKRBatchProverState prover_init_batch(const std::vector<const SparseMultilinearExtension *> &f1s, const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                 const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs) {
+        const size_t n = f1s.size();
+        if (f2s.size() != n || f3s.size() != n || gs.size() != n) throw Panic(SC_ERR_BAD_ARG, "one f1, f2, f3 and g per instance");
+        const size_t dim = n && f2s[0] ? f2s[0]->num_vars : 0;
+        std::vector<const uint64_t *> idx(n + 1), vals(n + 1), p2(n + 1), p3(n + 1), pg(n + 1);
+        std::vector<uint64_t> nnz(n + 1);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f1s[i] || !f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f1s[i]->num_vars != 3 * dim || f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            idx[i] = f1s[i]->indices.data();
+            vals[i] = f1s[i]->values.empty() ? nullptr : f1s[i]->values[0].l;
+            nnz[i] = f1s[i]->indices.size();
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+            pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+        }
+        sc_gkr_batch_prover *h = nullptr;
+        check(sc_gkr_batch_prover_init((uint32_t)n, (uint32_t)dim, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), 0, &h));
+        return GKRBatchProverState(h, n, dim);
     }
 };
 

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch and the sc_batch_prover_* family (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -370,6 +370,49 @@ SC_API int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
                               const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
                               const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
                               uint32_t flags, uint64_t *out_proofs, uint64_t *out_uv_or_null);
+/* ---- n x the interactive rounds of GKRRoundSumcheck::prove (mod.rs:93-139) behind one handle, under the caller's transcript ----------
+ * sc_gkr_prove_batch keeps the crate's Blake2b transcript inside the call, one per instance.  GKRRoundSumcheck::prove is where the
+ * reference most plainly takes rng: &mut impl FeedableRNG: a GKR prover runs one round sumcheck per layer or per copy of a sub-circuit
+ * under ONE transcript, often with one challenge per round for all of them.  This family is to sc_gkr_prove_batch what sc_batch_prover_*
+ * is to sc_ml_prove_batch: the caller hashes (on as many threads as it likes) and hands in every challenge; a proof is 2 x dim round
+ * calls -- phase one's dim messages, then phase two's -- and one call of sc_gkr_batch_prover_finish.  Within sc_gkr_prove_batch's envelope
+ * [dim <= 9, nnz <= 64 x 2^dim] a round call is one upload of the challenges, ONE kernel launch [a block per instance; the call that
+ * starts phase two: two launches back to back], one copy back and one synchronisation, and nothing on the GPU ever waits for the host.
+ * The calls are TOTAL over shapes: beyond the envelope, or with policy "batch" = 0 when the handle is built, the handle holds per
+ * instance what sc_gkr_prove's path holds [the two dense tables by its route, an ordinary prover per phase, device-side waits off] and
+ * a round is a loop of sc_prove_round, with the same bits.  THREADING: as for sc_batch_prover_*. */
+typedef struct sc_gkr_batch_prover sc_gkr_batch_prover;   /* n x the two ProverStates of GKRRoundSumcheck::prove (mod.rs:93-139), one dim */
+/* SC_API_GKRB is SC_API: the marker of this family, for the reason SC_API_EXT has one [tests/test_gkr_batch_rounds_host.py compares
+ * these prototypes with the shim's declarations]. */
+#define SC_API_GKRB SC_API /* [nothing but this comment may follow on the line] */
+/* Arguments, meaning and checks are sc_gkr_prove_batch's, without the rngs [pointers may repeat across instances; SC_TABLES_ON_DEVICE as
+ * there; g[i] is host memory].  Everything the host can check is checked before any HIP call: errors start with "instance %u: ", the
+ * lowest failing instance decides; n == 0 is SC_ERR_BAD_ARG, dim == 0 SC_ERR_CONSTANT_POLY.  An out-of-range index in a device-resident
+ * list is found on the device in front of any kernel that follows the indices [SC_ERR_BAD_ARG "instance %u: f1 has an index out of
+ * range"].  Every input is COPIED, once per distinct pointer: nothing of the caller's is read after the call returns. */
+SC_API_GKRB int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
+                                         const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags,
+                                         sc_gkr_batch_prover **out);
+/* Called 2 x dim times: call t < dim returns phase one's message t of every instance, call dim .. 2 dim - 1 phase two's.  r_or_null: NULL
+ * exactly on call 0; afterwards the previous round's challenges, n x 4 limbs instance-major, or -- r_shared != 0 -- 4 limbs for all
+ * instances [the challenge handed to call dim is u_{dim-1}].  out_evals: n x 3 x 4 limbs.  Instance i's 2 x dim messages are bit for bit
+ * what GKRRoundSumcheck::prove computes for the same challenges.  Misuse maps to sc_batch_prove_round's status codes:
+ * SC_ERR_FIRST_ROUND_HAS_MSG, SC_ERR_MISSING_MSG, SC_ERR_NOT_ACTIVE after 2 x dim rounds; a non-canonical challenge is SC_ERR_BAD_ARG
+ * "instance %u: challenge is not canonical".  An argument error leaves the handle exactly where it was. */
+SC_API_GKRB int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t *r_or_null, uint32_t r_shared, uint64_t *out_evals);
+/* After 2 x dim rounds: takes the last challenge v_{dim-1} [r as above].  out_uv_or_null: n x 2 x dim x 4 limbs in sc_gkr_prove_batch's
+ * layout [a shared challenge is expanded]; out_final_or_null: n x 3 x 4 limbs -- f1(g,u,v), f2(u), f2(u) f3(v): phase two's two tables
+ * bound to one entry and the scalar from the phase change, so the subclaim's oracle queries cost no extra pass; the product of the first
+ * and the third is what the verifier compares with its expected evaluation.  Afterwards the handle is exhausted until it is reset. */
+SC_API_GKRB int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_t *r, uint32_t r_shared, uint64_t *out_uv_or_null, uint64_t *out_final_or_null);
+/* sc_batch_prover_state's job for ONE instance.  *round: 0 .. 2 dim; randomness: u followed by the v's received so far [up to 2 dim x 4
+ * limbs]; tables_out: the current phase's two tables, 2 x 2^(dim - bound) canonical elements, bound = max(the phase's round - 1, 0) --
+ * phase one's until call dim has been answered.  Every pointer but bp may be NULL. */
+SC_API_GKRB int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness,
+                                          uint64_t *tables_out, uint32_t *round);
+/* Rewind to round 0 over the inputs the handle holds, without reallocating and without rebuilding phase one's tables.  New inputs: a new handle. */
+SC_API_GKRB int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp);
+SC_API_GKRB void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp);
 /* f4 -- the same two initialisations with f1's non-zeros SPREAD OVER SEVERAL GPUs (worth it from dim ~ 24).
  * Every rank passes a disjoint subset of f1's (index, value) pairs -- any partition -- and all of f3 / g.  A rank's scatter is a
  * partial sum of a_hg, so the ranks' dense tables are added with ONE table-sized integer all-reduce of the widened limbs
@@ -476,7 +519,7 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "wait_spins" (2^22)      bound of a device-side wait for a challenge, in polls (tests shorten it to exercise the give-up path)
  *   "staged_init" (1)        0: sc_prover_init over HOST tables copies them whole before round 1 instead of in chunks with round 1 computed
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
- *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, sc_batch_prover_init: 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
+ *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, sc_batch_prover_init, sc_gkr_batch_prover_init (plans batch.gkr_rounds_one_block / batch.gkr_rounds_serial): 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
  *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
  *   "lag_single" (2)         big rounds that a table named only by single-table products skips after round 1 (0: none .. 4): its products' messages come
  *                            from class sums of the table, and one pass binds the table with every challenge it missed before the next round

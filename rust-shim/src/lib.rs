@@ -5,6 +5,7 @@
 //! |---|---|
 //! | [`prover_init`], [`prove_round`]            | `IPForMLSumcheck::{prover_init, prove_round}` `src/ml_sumcheck/protocol/prover.rs:49,74` |
 //! | [`prove`], [`prove_as_subprotocol`]         | `MLSumcheck::{prove, prove_as_subprotocol}` `src/ml_sumcheck/mod.rs:42,50` |
+//! | [`gkr_prover_init_batch`], [`gkr_prove_round_batch`], [`gkr_finish_batch`] | (new) the rounds of many small `GKRRoundSumcheck::prove` under the caller's transcript (`rng: &mut impl FeedableRNG`), one call per round |
 //! | [`prover_init_batch`], [`prove_round_batch`] | (new) `states.par_iter_mut().zip(msgs).map(prove_round)`: one round of many small provers in one call, the caller's transcript |
 //! | [`prove_batch`]                            | (new) `polys.par_iter().map(MLSumcheck::prove)`: many small instances of one structure in one call |
 //! | [`evaluate`]                                | `ListOfProductsOfPolynomials::evaluate` `src/ml_sumcheck/data_structures.rs:99` |
@@ -63,6 +64,10 @@ pub struct sc_comm {
 }
 #[repr(C)]
 pub struct sc_batch_prover {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct sc_gkr_batch_prover {
     _private: [u8; 0],
 }
 
@@ -644,6 +649,139 @@ pub fn gkr_prove_batch<F: Limbs4>(instances: &mut [GkrInstance<F>]) -> Vec<HipGK
                 phase2_sumcheck_msgs: msgs(dim),
                 u: w[..dim].iter().map(|l| F::from_limbs(*l)).collect(),
                 v: w[dim..2 * dim].iter().map(|l| F::from_limbs(*l)).collect(),
+            }
+        })
+        .collect()
+}
+
+// The batched interactive GKR rounds (`sc_gkr_batch_prover_*`): private declarations behind the safe wrappers below.
+extern "C" {
+    fn sc_gkr_batch_prover_init(n: u32, dim: u32, f1_idx: *const *const u64, f1_vals: *const *const u64, nnz: *const u64, f2: *const *const u64,
+                                f3: *const *const u64, g: *const *const u64, flags: u32, out: *mut *mut sc_gkr_batch_prover) -> c_int;
+    fn sc_gkr_batch_prove_round(bp: *mut sc_gkr_batch_prover, r_or_null: *const u64, r_shared: u32, out_evals: *mut u64) -> c_int;
+    fn sc_gkr_batch_prover_finish(bp: *mut sc_gkr_batch_prover, r: *const u64, r_shared: u32, out_uv_or_null: *mut u64, out_final_or_null: *mut u64) -> c_int;
+    fn sc_gkr_batch_prover_state(bp: *mut sc_gkr_batch_prover, instance: u32, randomness: *mut u64, n_randomness: *mut u32, tables_out: *mut u64,
+                                 round: *mut u32) -> c_int;
+    fn sc_gkr_batch_prover_reset(bp: *mut sc_gkr_batch_prover) -> c_int;
+    fn sc_gkr_batch_prover_free(bp: *mut sc_gkr_batch_prover);
+}
+
+/// One instance of [`gkr_prover_init_batch`]: what [`gkr_prove`] takes, without the transcript.
+pub struct GkrRoundsInstance<'a, F: Limbs4> {
+    pub f1: &'a SparseMultilinearExtension<F>,
+    pub f2: &'a DenseMultilinearExtension<F>,
+    pub f3: &'a DenseMultilinearExtension<F>,
+    pub g: &'a [F],
+}
+
+/// n x the two `ProverState`s of `GKRRoundSumcheck::prove` of ONE `dim` behind one `sc_gkr_batch_prover` handle ([`gkr_prover_init_batch`]).
+pub struct HipGkrBatchProverState<F: Limbs4> {
+    handle: *mut sc_gkr_batch_prover,
+    pub n: usize,
+    pub dim: usize,
+    _f: core::marker::PhantomData<F>,
+}
+
+impl<F: Limbs4> Drop for HipGkrBatchProverState<F> {
+    fn drop(&mut self) {
+        unsafe { sc_gkr_batch_prover_free(self.handle) }
+    }
+}
+
+impl<F: Limbs4> HipGkrBatchProverState<F> {
+    /// round calls answered so far: 0 ..= 2 dim
+    pub fn round(&self) -> usize {
+        let mut r = 0u32;
+        check(unsafe { sc_gkr_batch_prover_state(self.handle, 0, core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(), &mut r) });
+        r as usize
+    }
+    /// `u` followed by the `v`s instance `i` has received so far
+    pub fn randomness(&self, i: usize) -> Vec<F> {
+        let mut rand = vec![[0u64; 4]; (2 * self.dim).max(1)];
+        let mut n_rand = 0u32;
+        check(unsafe { sc_gkr_batch_prover_state(self.handle, i as u32, rand.as_mut_ptr() as *mut u64, &mut n_rand, core::ptr::null_mut(), core::ptr::null_mut()) });
+        rand[..n_rand as usize].iter().map(|l| F::from_limbs(*l)).collect()
+    }
+    /// rewind to round 0 over the inputs the handle holds (phase one's tables are not rebuilt)
+    pub fn reset(&mut self) {
+        check(unsafe { sc_gkr_batch_prover_reset(self.handle) });
+    }
+}
+
+/// What [`gkr_finish_batch`] returns per instance: the points and the subclaim's oracle values, at no extra pass over the tables.
+pub struct GkrBatchFinal<F: Limbs4> {
+    pub u: Vec<F>,
+    pub v: Vec<F>,
+    /// f1(g, u, v)
+    pub f1_guv: F,
+    /// f2(u)
+    pub f2_u: F,
+    /// f2(u) f3(v); `f1_guv * f2u_f3v` is what the verifier compares with its expected evaluation
+    pub f2u_f3v: F,
+}
+
+/// n x the prover of `GKRRoundSumcheck::prove` for instances of ONE `dim` behind one handle (`sc_gkr_batch_prover_init`); every input is copied.
+pub fn gkr_prover_init_batch<F: Limbs4>(instances: &[GkrRoundsInstance<F>]) -> HipGkrBatchProverState<F> {
+    let n = instances.len();
+    let dim = if n > 0 { instances[0].f2.num_vars } else { 0 };
+    let mut arrays = Vec::with_capacity(n);
+    let mut gls: Vec<Vec<[u64; 4]>> = Vec::with_capacity(n);
+    for inst in instances.iter() {
+        assert_eq!(inst.f1.num_vars, 3 * dim);
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        arrays.push(sparse_arrays(inst.f1));
+        gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+    }
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let f2: Vec<*const u64> = instances.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = instances.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = gls.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let mut handle: *mut sc_gkr_batch_prover = core::ptr::null_mut();
+    check(unsafe {
+        sc_gkr_batch_prover_init(n as u32, dim as u32, idx.as_ptr(), vals.as_ptr(), nnz.as_ptr(), f2.as_ptr(), f3.as_ptr(), g.as_ptr(), 0, &mut handle)
+    });
+    HipGkrBatchProverState { handle, n, dim, _f: core::marker::PhantomData }
+}
+
+fn gkr_batch_challenges<F: Limbs4>(state: &HipGkrBatchProverState<F>, v_msgs: &[VerifierMsg<F>]) -> (Vec<[u64; 4]>, u32) {
+    assert!(v_msgs.len() == state.n || v_msgs.len() == 1, "one VerifierMsg per instance, or a single one for all");
+    (v_msgs.iter().map(|m| m.randomness.to_limbs()).collect(), if v_msgs.len() == 1 && state.n != 1 { 1 } else { 0 })
+}
+
+/// One round of every instance in one FFI call (`sc_gkr_batch_prove_round`): call it 2 dim times -- phase one's messages, then phase
+/// two's.  `None` on the first call, afterwards the previous round's challenges: one per instance, or a single one shared by all.
+pub fn gkr_prove_round_batch<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, v_msgs: Option<&[VerifierMsg<F>]>) -> Vec<ProverMsg<F>> {
+    let mut out = vec![[0u64; 4]; state.n.max(1) * 3];
+    match v_msgs {
+        None => check(unsafe { sc_gkr_batch_prove_round(state.handle, core::ptr::null(), 0, out.as_mut_ptr() as *mut u64) }),
+        Some(ms) => {
+            let (r, shared) = gkr_batch_challenges(state, ms);
+            check(unsafe { sc_gkr_batch_prove_round(state.handle, r.as_ptr() as *const u64, shared, out.as_mut_ptr() as *mut u64) })
+        }
+    }
+    (0..state.n).map(|i| prover_msg(&out[3 * i..3 * i + 3])).collect()
+}
+
+/// The last challenge `v_{dim-1}` after 2 dim rounds (`sc_gkr_batch_prover_finish`); the handle is exhausted until it is reset.
+pub fn gkr_finish_batch<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, v_msgs: &[VerifierMsg<F>]) -> Vec<GkrBatchFinal<F>> {
+    let (r, shared) = gkr_batch_challenges(state, v_msgs);
+    let (n, dim) = (state.n, state.dim);
+    let mut uv = vec![[0u64; 4]; (n * 2 * dim).max(1)];
+    let mut fin = vec![[0u64; 4]; n.max(1) * 3];
+    check(unsafe { sc_gkr_batch_prover_finish(state.handle, r.as_ptr() as *const u64, shared, uv.as_mut_ptr() as *mut u64, fin.as_mut_ptr() as *mut u64) });
+    (0..n)
+        .map(|i| {
+            let w = &uv[i * 2 * dim..(i + 1) * 2 * dim];
+            GkrBatchFinal {
+                u: w[..dim].iter().map(|l| F::from_limbs(*l)).collect(),
+                v: w[dim..].iter().map(|l| F::from_limbs(*l)).collect(),
+                f1_guv: F::from_limbs(fin[3 * i]),
+                f2_u: F::from_limbs(fin[3 * i + 1]),
+                f2u_f3v: F::from_limbs(fin[3 * i + 2]),
             }
         })
         .collect()

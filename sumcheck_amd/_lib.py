@@ -136,6 +136,17 @@ SIGNATURES_EXT = {
     "sc_batch_prover_free": (None, [_V]),
 }
 
+# ... and with SC_API_GKRB: the interactive rounds of a batch of GKR round proofs (sc_gkr_batch_prover_*), also within ABI version 5
+SIGNATURES_GKRB = {
+    "sc_gkr_batch_prover_init": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V), C.c_uint32,
+                                           C.POINTER(_V)]),
+    "sc_gkr_batch_prove_round": (C.c_int, [_V, _V, C.c_uint32, _V]),
+    "sc_gkr_batch_prover_finish": (C.c_int, [_V, _V, C.c_uint32, _V, _V]),
+    "sc_gkr_batch_prover_state": (C.c_int, [_V, C.c_uint32, _V, u32p, _V, u32p]),
+    "sc_gkr_batch_prover_reset": (C.c_int, [_V]),
+    "sc_gkr_batch_prover_free": (None, [_V]),
+}
+
 ABI_VERSION = 5  # SC_ABI_VERSION of include/sumcheck_hip.h as declared above
 _lib = None
 
@@ -173,7 +184,7 @@ def lib():
         # An A/B run against an OLDER build (tools/ab.sh) sets SC_AB_ALLOW_MISSING=1 next to SC_LIB_PATH: entry points that build lacks
         # become stubs that raise when called.  Without it every declared symbol must resolve, whatever file SC_LIB_PATH names.
         allow_missing = os.environ.get("SC_AB_ALLOW_MISSING") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()) + list(SIGNATURES_GKRB.items()):
             try:
                 fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:

@@ -699,13 +699,8 @@ int check_canonical(const uint64_t *elems, uint32_t n_elems, uint32_t i, const c
 }
 
 // ---- what sc_gkr_prove_batch and sc_gkr_subclaim_batch (below) share: the callers' arrays, their checks, their place in the uploaded image
-struct GkrBatchIn {
-    uint32_t n, dim;
-    const uint64_t *const *f1_idx, *const *f1_vals;
-    const uint64_t *nnz;
-    const uint64_t *const *f2, *const *f3, *const *g;
-    bool on_device; // SC_TABLES_ON_DEVICE: read in place
-};
+// (GkrBatchIn: prover_internal.hpp)
+} // namespace
 // sc_gkr_prove's checks on instance i (no HIP call); uv_or_null: the subclaim call's points u | v, checked behind g
 int gkr_check_instance(const GkrBatchIn &in, uint32_t i, const uint64_t *uv_or_null) {
     if (in.nnz[i] >= (1ULL << 32)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz too large", i);
@@ -718,6 +713,7 @@ int gkr_check_instance(const GkrBatchIn &in, uint32_t i, const uint64_t *uv_or_n
             if ((in.f1_idx[i][k] >> (3 * in.dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 index %llu out of range", i, (unsigned long long)k);
     return SC_OK;
 }
+namespace {
 // host inputs into the image, each distinct array once (one wiring predicate for many data instances is the usual case) -> per instance the
 // offsets of idx, vals, f2, f3; empty for device inputs
 std::vector<size_t> gkr_stage_inputs(const GkrBatchIn &in, StageMap &st) {
@@ -751,6 +747,7 @@ scd::GkrBatchInst gkr_record(const GkrBatchIn &in, uint32_t i, const std::vector
     }
     return r;
 }
+} // namespace
 // device-resident lists: their indices are checked on the device, in front of the launch (the kernels themselves mask every index they use);
 // the flags (zeroed in the image) are at flag_off
 int gkr_check_idx_on_device(const scd::GkrBatchInst *d_rec, uint32_t n, uint32_t dim, char *h_up, char *d_up, size_t flag_off, hipStream_t stream) {
@@ -762,7 +759,6 @@ int gkr_check_idx_on_device(const scd::GkrBatchInst *d_rec, uint32_t n, uint32_t
         if (fl[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: f1 has an index out of range", i);
     return SC_OK;
 }
-} // namespace
 
 extern "C" int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
                                   const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags, uint64_t *out_proofs, uint64_t *out_uv_or_null) {

@@ -6,9 +6,12 @@
 // publication as self-validating words (limb | tag << 32): k_batch_proofs (kernels_batch.hip: sc_ml_prove_batch), k_batch_gkr
 // (kernels_batch_gkr.hip: sc_gkr_prove_batch), which runs it twice per instance over tables it has built in LDS itself, and k_batch_round
 // (kernels_batch_rounds.hip: sc_batch_prove_round), which runs ONE round per launch and uses neither the poll nor the tagged words.
+// bg_build_eq and bg_accumulate, the two pieces of a GKR phase's initialisation, are here as well: k_batch_gkr uses them inside its persistent
+// block, k_batch_gkr_phase (kernels_batch_gkr_rounds.hip: sc_gkr_batch_prover_*) as plain launches that write k_batch_round's work areas.
 #pragma once
 #include "finalize_device.hpp"
 #include "kernel_common.hpp"
+#include "wide_cell.hpp"
 
 namespace scd {
 
@@ -27,6 +30,13 @@ __device__ __forceinline__ void bt_lds_store(int32_t *t, const Fe &v) {
     *reinterpret_cast<int4 *>(t) = make_int4(v.l[0], v.l[1], v.l[2], v.l[3]);
     *reinterpret_cast<int4 *>(t + 4) = make_int4(v.l[4], v.l[5], v.l[6], v.l[7]);
     t[8] = v.l[8];
+}
+// a slot of a batch work area (global memory, kernels.h: batch_rounds_off): the LDS slot verbatim, three 16-byte words, the last one's upper lanes zero
+__device__ __forceinline__ Fe br_slot_load(const int32_t *t) { return bt_lds_load(t); }
+__device__ __forceinline__ void br_slot_store(int32_t *t, const Fe &v) {
+    *reinterpret_cast<int4 *>(t) = make_int4(v.l[0], v.l[1], v.l[2], v.l[3]);
+    *reinterpret_cast<int4 *>(t + 4) = make_int4(v.l[4], v.l[5], v.l[6], v.l[7]);
+    *reinterpret_cast<int4 *>(t + 8) = make_int4(v.l[8], 0, 0, 0);
 }
 __device__ __forceinline__ Fe bt_shfl_down(const Fe &a, const int off) {
     Fe r;
@@ -278,6 +288,35 @@ __device__ __forceinline__ void bg_build_eq(uint4 *out, uint4 *tmp, const uint4 
     for (uint32_t b = tid; b < (1u << dim); b += kTsBlock) {
         const Fr l = fr_load(lo + 2 * (b & ((1u << kl) - 1u)));
         fr_store(out + 2 * b, kh ? fr_mul(l, fr_load(hi + 2 * (b >> kl))) : l);
+    }
+    __syncthreads();
+}
+
+// A GKR phase's table from the instance's non-zeros (k_batch_gkr, k_batch_gkr_phase).  kPhase 1: cell x, term eq(g,z) * v * f3[y];
+// kPhase 2: cell y, term eq(g,z) * eq(u,x) * v.  The cells (eight uint64 lanes of 32-bit limbs each, lane-major: cell[j << dim | c],
+// neighbouring cells in neighbouring banks) are zeroed, filled with LDS atomic adds (exact in any order) and folded mod p; store(c, value)
+// takes cell c's element: an LDS table, or a slot of a work area.  Every index is masked to dim bits per component before it addresses
+// LDS or f3.  Ends behind a barrier.
+template <int kPhase, typename Store>
+__device__ __forceinline__ void bg_accumulate(uint64_t *cell, const GkrBatchInst &I, const uint32_t dim, const uint4 *eq_g, const uint4 *eq_u, const Store &store) {
+    const uint32_t tid = threadIdx.x, cap = 1u << dim, mask = cap - 1u;
+    for (uint32_t i = tid; i < 8u * cap; i += kTsBlock) cell[i] = 0;
+    __syncthreads();
+    for (uint64_t i = tid; i < I.nnz; i += kTsBlock) {
+        const uint64_t id = I.idx[i];
+        const uint32_t z = (uint32_t)id & mask, x = (uint32_t)(id >> dim) & mask, y = (uint32_t)(id >> (2 * dim)) & mask;
+        const Fr a = fr_mul(fr_load(eq_g + 2 * z), fr_load(I.vals + 2 * i));
+        const Fr t = kPhase == 1 ? fr_mul(a, fr_load(I.f3 + 2 * (size_t)y)) : fr_mul(a, fr_load(eq_u + 2 * x));
+        const uint32_t c = kPhase == 1 ? x : y;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) __hip_atomic_fetch_add(cell + (((uint32_t)j << dim) | c), (uint64_t)t.v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    for (uint32_t c = tid; c < cap; c += kTsBlock) {
+        uint64_t lane[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lane[j] = cell[((uint32_t)j << dim) | c];
+        store(c, fe_from_fr(wide_fold_cell(lane)));
     }
     __syncthreads();
 }

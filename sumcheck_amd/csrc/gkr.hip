@@ -1010,6 +1010,63 @@ extern "C" int sc_gkr_phase_two(const uint64_t *f1g_idx, const uint64_t *f1g_val
     return SC_OK;
 }
 
+// One dense table of GKRRoundSumcheck::prove from device-resident inputs whose indices have been checked, by the route sc_gkr_prove
+// takes: the bucketed kernels where they pay, the list form otherwise or when a bucket is crowded (gkr_batch_rounds.hip: the serial plan
+// of sc_gkr_batch_prover_*).  phase 1: h_g from (f1, f3, g), mod.rs:30-38; phase 2: f1(g, u, .) from (f1, g, u), mod.rs:31 and 62.
+// Repeated indices add up.  d_out: 2^dim elements of device memory, complete when the call returns.
+int sc_internal_gkr_dense_table(int phase, const uint64_t *d_idx, const void *d_vals_v, uint64_t nnz, uint32_t dim, const void *d_f3_v, const uint64_t *g, const uint64_t *u_or_null,
+                                void *d_out_v) {
+    GkrGate gate_;
+    G_TRY(hipSetDevice(sc_internal_device()));
+    const Fr *d_vals = static_cast<const Fr *>(d_vals_v), *d_f3 = static_cast<const Fr *>(d_f3_v);
+    Fr *d_out = static_cast<Fr *>(d_out_v);
+    const sch::Fr *gp = reinterpret_cast<const sch::Fr *>(g), *up = reinterpret_cast<const sch::Fr *>(u_or_null);
+    const uint64_t N = 1ULL << dim;
+    hipStream_t s = nullptr;
+    int rc = SC_OK;
+    if (nnz == 0) {
+        G_TRY(hipMemsetAsync(d_out, 0, N * 32, s));
+        G_TRY(hipStreamSynchronize(s));
+        return SC_OK;
+    }
+    DevBuf mem;
+    (void)mem.reserve(gkr_scratch_estimate(nnz, N));
+    bool done = false;
+    if (bucketed_form_pays(nnz, dim)) {
+        EqSplit eq_g{nullptr, nullptr, 0}, eq_u{nullptr, nullptr, 0};
+        if ((rc = build_eq_split(mem, gp, dim, &eq_g, s))) return rc;
+        if (phase == 1) {
+            if ((rc = bucketed_dense<1>(mem, d_idx, d_vals, nnz, dim, eq_g, eq_u, d_f3, false, d_out, &done, s))) return rc;
+        } else {
+            if ((rc = build_eq_split(mem, up, dim, &eq_u, s))) return rc;
+            if ((rc = bucketed_dense<2>(mem, d_idx, d_vals, nnz, dim, eq_g, eq_u, d_f3, false, d_out, &done, s))) return rc;
+        }
+    }
+    if (!done) {
+        uint64_t *d_idx_s = nullptr, *d_gi = nullptr;
+        Fr *d_vals_s = nullptr, *d_gv = nullptr;
+        unsigned int *d_n1 = nullptr;
+        uint64_t n1 = 0;
+        G_TRY(mem.alloc(&d_idx_s, nnz));
+        G_TRY(mem.alloc(&d_vals_s, nnz));
+        G_TRY(mem.alloc(&d_gi, nnz));
+        G_TRY(mem.alloc(&d_gv, nnz));
+        G_TRY(mem.alloc(&d_n1, 1));
+        if ((rc = sort_sparse(mem, d_idx, d_vals, nnz, 3 * dim, d_idx_s, d_vals_s, s))) return rc;
+        if (phase == 1) {
+            if ((rc = phase_one_device(mem, d_idx_s, d_vals_s, nnz, dim, d_f3, gp, d_out, d_gi, d_gv, d_n1, &n1, s))) return rc;
+        } else {
+            if ((rc = sparse_fix(mem, d_idx_s, d_vals_s, nnz, gp, dim, d_gi, d_gv, d_n1, s))) return rc;
+            unsigned int h_n1 = 0;
+            G_TRY(hipMemcpyAsync(&h_n1, d_n1, sizeof(h_n1), hipMemcpyDeviceToHost, s));
+            G_TRY(hipStreamSynchronize(s));
+            if ((rc = phase_two_device(mem, d_gi, d_gv, h_n1, dim, up, d_out, s))) return rc;
+        }
+    }
+    G_TRY(hipStreamSynchronize(s));
+    return SC_OK;
+}
+
 int sc_internal_allreduce_lanes(sc_comm *c, uint64_t *d_lanes, size_t n_words, hipStream_t s); // comm.hip
 int sc_internal_comm_ranks(sc_comm *c);
 

@@ -1,0 +1,432 @@
+// gkr_batch_rounds.hip -- sc_gkr_batch_prover_*: n x the two ProverStates of GKRRoundSumcheck::prove (reference
+// src/gkr_round_sumcheck/mod.rs:93-139) of one dim behind ONE handle, a round of all n instances per call, under the caller's transcript.
+// What batch_rounds.hip is to sc_ml_prove_batch, this is to sc_gkr_prove_batch: the caller hands in every challenge (one per instance, or
+// one shared by all), so a round is launched after its challenges are known and nothing on the GPU ever waits for the host.  A proof is
+// 2 x dim round calls -- phase one's dim messages, then phase two's -- and sc_gkr_batch_prover_finish.  Two plans, chosen when the handle
+// is built, same bits:
+//   batch.gkr_rounds_one_block  two work areas of k_batch_round's layout (U = 2): A for phase one, B for phase two.  k_batch_gkr_phase<1>
+//                               (kernels_batch_gkr_rounds.hip) fills A's depth 0 once, at init -- it is never written again, so a reset
+//                               rewinds counters --; round call dim launches k_batch_gkr_phase<2> in front of its k_batch_round, which
+//                               binds what is left of f2 with u_{dim-1} and fills B from the challenges the handle has kept on the
+//                               device.  Per round call: one upload of the challenges, one launch (call dim: two, back to back), one copy
+//                               back, one synchronisation;
+//   batch.gkr_rounds_serial     per instance the two dense tables by the route sc_gkr_prove takes (sc_internal_gkr_dense_table) and an
+//                               ordinary sc_prover per phase (device-side waits off, no resident kernel); a round is a loop of
+//                               sc_prove_round, the phase change and finish go through sc_prover_bind_final: dim > 9, nnz beyond
+//                               64 x 2^dim, policy "batch" = 0.
+// The handle copies every input once per distinct pointer (phase two needs f1 and f3 again): nothing of the caller's is read after init.
+#include "prover_internal.hpp"
+
+struct sc_gkr_batch_prover {
+    int device = 0;
+    uint32_t n = 0, dim = 0, round = 0; // round: round calls answered so far, 0 .. 2 dim
+    bool exhausted = false;
+    bool one_block = false;
+    std::vector<std::vector<sch::Fr>> randomness; // per challenge received (u, then v): n elements, or ONE for a shared challenge
+    std::vector<uint64_t> nnz;
+    std::vector<sch::Fr> g;                        // n x dim
+    std::vector<scd::GkrBatchInst> rec;            // the instances' arrays in the handle's copy (d_in), g in d_up
+    hipStream_t stream = nullptr;
+    char *d_buf = nullptr; // device, ONE allocation: area A | area B (one block) | matrices | records | index flags | g | challenges | messages | f2(u) | export area | inputs | serial tables
+    char *d_in = nullptr;  // (inside d_buf) the inputs, every distinct array once
+    char *h_pin = nullptr; // pinned: matrices | ... | export area
+    size_t work_bytes = 0, w_off = 0, rec_off = 0, flag_off = 0, g_off = 0, u_off = 0, msg_off = 0, f2u_off = 0, exp_off = 0, pin_bytes = 0; // (offsets into h_pin; d_buf: + 2 work_bytes)
+    SharedMeta s; // one product of two tables with a coefficient of one: both phases (start_phase{1,2}_sumcheck, mod.rs:45-54, 66-82)
+    // ---- batch.gkr_rounds_serial ----
+    std::vector<sc_prover *> p1, p2;
+    char *d_tabs = nullptr; // (inside d_buf) per instance h_g | f1(g, u, .) | f2(u) f3, 2^dim elements each
+    char *d_fin = nullptr;  // (inside d_buf) bind_final's n x 2 elements
+    std::vector<sch::Fr> f2u; // n: f2(u), from the phase change
+};
+
+namespace {
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+const sch::Fr &challenge_of(const std::vector<sch::Fr> &c, uint32_t i) { return c.size() == 1 ? c[0] : c[i]; }
+
+void destroy(sc_gkr_batch_prover *bp) {
+    if (!bp) return;
+    for (sc_prover *p : bp->p1)
+        if (p) sc_prover_free(p);
+    for (sc_prover *p : bp->p2)
+        if (p) sc_prover_free(p);
+    if (bp->d_buf || bp->h_pin || bp->stream) {
+        DeviceGate gate_(bp->device);
+        (void)hipSetDevice(bp->device);
+        if (bp->stream) (void)hipStreamSynchronize(bp->stream);
+        if (bp->d_buf) (void)hipFree(bp->d_buf);
+        if (bp->h_pin) (void)hipHostFree(bp->h_pin);
+        if (bp->stream) (void)hipStreamDestroy(bp->stream);
+        (void)hipGetLastError();
+    }
+    delete bp;
+}
+
+int prefix(int rc, uint32_t i) {
+    const std::string why = sc_last_error();
+    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+}
+
+// the challenges of a call: canonical checks (no HIP call), then as the handle records them
+int take_challenges(const sc_gkr_batch_prover *bp, const uint64_t *r, uint32_t r_shared, std::vector<sch::Fr> &out) {
+    out.resize(r_shared ? 1 : bp->n);
+    std::memcpy(out.data(), r, out.size() * 32);
+    for (size_t i = 0; i < out.size(); ++i)
+        if (sch::geq_p(out[i])) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: challenge is not canonical", (uint32_t)i);
+    return SC_OK;
+}
+
+// challenge number j (0-based: u_0 .. u_{dim-1}, v_0 ..) of every instance -> the handle's device copy, [j][instance]; a shared one is expanded
+int upload_challenge(sc_gkr_batch_prover *bp, uint32_t j, const std::vector<sch::Fr> &chal) {
+    const size_t off = bp->u_off + (size_t)j * bp->n * 32;
+    sch::Fr *h = reinterpret_cast<sch::Fr *>(bp->h_pin + off);
+    for (uint32_t i = 0; i < bp->n; ++i) h[i] = challenge_of(chal, i);
+    HIP_TRY(hipMemcpyAsync(bp->d_buf + 2 * bp->work_bytes + off, h, (size_t)bp->n * 32, hipMemcpyHostToDevice, bp->stream));
+    return SC_OK;
+}
+
+// the descriptor of a phase: one product of the two tables, coefficient one
+struct PhaseDesc {
+    uint32_t offs[2] = {0, 2}, idx2[2] = {0, 1};
+    const uint64_t *tabs[2] = {nullptr, nullptr};
+    sc_poly_desc d;
+    PhaseDesc(uint32_t dim, uint32_t flags) {
+        std::memset(&d, 0, sizeof(d));
+        d.num_vars = dim;
+        d.max_multiplicands = 2;
+        d.n_products = 1;
+        d.coeffs = sch::kOne.l;
+        d.prod_offsets = offs;
+        d.prod_indices = idx2;
+        d.n_tables = 2;
+        d.tables = tabs;
+        d.flags = flags;
+    }
+};
+
+char *serial_table(const sc_gkr_batch_prover *bp, uint32_t i, uint32_t which) { return bp->d_tabs + ((size_t)i * 3 + which) * ((size_t)32 << bp->dim); }
+
+// a prover of the serial plan over two tables of the handle's (borrowed; device-side waits off, no resident kernel), or the old one rewound over them
+int serial_prover(sc_gkr_batch_prover *bp, sc_prover **p, const void *t0, const void *t1) {
+    PhaseDesc pd(bp->dim, SC_TABLES_ON_DEVICE | SC_TABLES_BORROW | SC_NO_DEVICE_POLLING);
+    pd.tabs[0] = static_cast<const uint64_t *>(t0);
+    pd.tabs[1] = static_cast<const uint64_t *>(t1);
+    if (*p) return sc_prover_reset(*p, pd.tabs, SC_TABLES_ON_DEVICE);
+    int rc = sc_prover_init(&pd.d, p);
+    if (rc == SC_OK) rc = sc_prover_set_resident(*p, 0);
+    return rc;
+}
+
+// the serial plan's phase change for instance i: f2(u) from phase one's prover, f1(g, u, .), f2(u) f3, phase two's prover
+int serial_phase_two(sc_gkr_batch_prover *bp, uint32_t i, const std::vector<sch::Fr> &u_last) {
+    const uint32_t dim = bp->dim;
+    sc_prover *p = bp->p1[i];
+    char *fin = bp->d_fin + (size_t)i * 64;
+    if (int rc = sc_prover_bind_final(p, challenge_of(u_last, i).l, reinterpret_cast<uint64_t *>(fin))) return rc;
+    {
+        DeviceGate gate_(bp->device);
+        HIP_TRY(hipMemcpyAsync(&bp->f2u[i], fin + 32, 32, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    std::vector<sch::Fr> u(dim);
+    for (uint32_t j = 0; j + 1 < dim; ++j) u[j] = challenge_of(bp->randomness[j], i);
+    u[dim - 1] = challenge_of(u_last, i);
+    const scd::GkrBatchInst &I = bp->rec[i];
+    if (int rc = sc_internal_gkr_dense_table(2, I.idx, I.vals, bp->nnz[i], dim, I.f3, bp->g[(size_t)i * dim].l, u[0].l, serial_table(bp, i, 1))) return rc;
+    if (int rc = sc_dense_scale(reinterpret_cast<const uint64_t *>(I.f3), 1ULL << dim, bp->f2u[i].l, reinterpret_cast<uint64_t *>(serial_table(bp, i, 2)), SC_TABLES_ON_DEVICE)) return rc; // mod.rs:71-75
+    return serial_prover(bp, &bp->p2[i], serial_table(bp, i, 1), serial_table(bp, i, 2));
+}
+
+} // namespace
+
+extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2,
+                                        const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags, sc_gkr_batch_prover **out) {
+    // ---- everything the host can check, before any HIP call (sc_gkr_prove_batch's checks: the lowest failing instance decides) ----
+    if (!f1_idx || !f1_vals || !nnz || !f2 || !f3 || !g || !out) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (n == 0) return sc_internal_fail(SC_ERR_BAD_ARG, "n == 0: a batch handle holds at least one instance");
+    if (dim == 0) return sc_internal_fail(SC_ERR_CONSTANT_POLY, "instance 0: Attempt to prove a constant.");
+    if (dim > 21) return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0: dim %u: 3*dim index bits do not fit 64-bit indices", dim);
+    const bool dev_in = flags & SC_TABLES_ON_DEVICE;
+    const GkrBatchIn in = {n, dim, f1_idx, f1_vals, nnz, f2, f3, g, dev_in};
+    uint64_t nnz_max = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int rc = gkr_check_instance(in, i, nullptr)) return rc;
+        nnz_max = std::max(nnz_max, nnz[i]);
+    }
+    if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
+    sc_gkr_batch_prover *bp = new (std::nothrow) sc_gkr_batch_prover();
+    if (!bp) return sc_internal_fail(SC_ERR_OOM, "out of host memory");
+    bp->device = sc_internal_device_ref();
+    bp->n = n;
+    bp->dim = dim;
+    bp->nnz.assign(nnz, nnz + n);
+    bp->g.resize((size_t)n * dim);
+    for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g[(size_t)i * dim], g[i], (size_t)dim * 32);
+    bp->one_block = scd::policy(scd::kPolBatch) != 0 && scd::gkr_batch_shape_fits(dim, nnz_max);
+    const size_t N = (size_t)1 << dim;
+    auto build = [&]() -> int {
+        PhaseDesc pd(dim, 0);
+        build_shared(&pd.d, bp->s);
+        bp->s.unit.push_back(unit_matrix(2, 3));
+        // ---- the handle's copy of the inputs: every distinct (pointer, size) once ----
+        std::map<std::pair<const void *, size_t>, size_t> where;
+        std::vector<std::pair<const void *, size_t>> items;
+        size_t in_bytes = 0;
+        auto add = [&](const void *src, size_t bytes) -> size_t {
+            auto it = where.find({src, bytes});
+            if (it != where.end()) return it->second;
+            const size_t off = in_bytes;
+            where.emplace(std::make_pair(src, bytes), off);
+            items.emplace_back(src, bytes);
+            in_bytes += up256(bytes);
+            return off;
+        };
+        std::vector<size_t> offs((size_t)n * 4, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            offs[4 * (size_t)i + 0] = nnz[i] ? add(f1_idx[i], (size_t)nnz[i] * 8) : 0;
+            offs[4 * (size_t)i + 1] = nnz[i] ? add(f1_vals[i], (size_t)nnz[i] * 32) : 0;
+            offs[4 * (size_t)i + 2] = add(f2[i], N * 32);
+            offs[4 * (size_t)i + 3] = add(f3[i], N * 32);
+        }
+        bp->work_bytes = bp->one_block ? up256((size_t)n * 2 * 2 * (scd::kBatchRoundSlotBytes << dim)) : 0;
+        bp->w_off = 0;
+        bp->rec_off = bp->w_off + up256((size_t)bp->s.w_elems * 32);
+        bp->flag_off = bp->rec_off + up256((size_t)n * sizeof(scd::GkrBatchInst));
+        bp->g_off = bp->flag_off + up256((size_t)n * 4);
+        bp->u_off = bp->g_off + up256((size_t)n * dim * 32);
+        bp->msg_off = bp->u_off + up256((size_t)2 * dim * n * 32);
+        bp->f2u_off = bp->msg_off + up256((size_t)n * 3 * 32);
+        bp->exp_off = bp->f2u_off + up256((size_t)n * 32);
+        bp->pin_bytes = bp->exp_off + up256(std::max(2 * N * 32, (size_t)n * 2 * 32)); // one instance's tables (state), or every instance's final values
+        {
+            DeviceGate gate_(bp->device);
+            HIP_TRY(hipSetDevice(bp->device));
+            HIP_TRY(hipStreamCreateWithFlags(&bp->stream, hipStreamNonBlocking));
+            const size_t tabs_bytes = bp->one_block ? 0 : (size_t)n * 3 * N * 32, fin_bytes = bp->one_block ? 0 : up256((size_t)n * 64);
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), 2 * bp->work_bytes + bp->pin_bytes + in_bytes + tabs_bytes + fin_bytes)); // (one allocation: a handle's life is short)
+            bp->d_in = bp->d_buf + 2 * bp->work_bytes + bp->pin_bytes;
+            if (!bp->one_block) {
+                bp->d_tabs = bp->d_in + in_bytes;
+                bp->d_fin = bp->d_tabs + tabs_bytes;
+            }
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bp->h_pin), bp->pin_bytes, hipHostMallocDefault));
+            if (dev_in) HIP_TRY(hipDeviceSynchronize()); // the inputs' producers are waited for, as a copy on their stream would
+            size_t off = 0;
+            for (const auto &it : items) {
+                HIP_TRY(hipMemcpyAsync(bp->d_in + off, it.first, it.second, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, bp->stream));
+                off += up256(it.second);
+            }
+            char *d_up = bp->d_buf + 2 * bp->work_bytes;
+            instance_weights(bp->s, sch::kOne.l, reinterpret_cast<sch::Fr *>(bp->h_pin + bp->w_off));
+            std::memset(bp->h_pin + bp->flag_off, 0, up256((size_t)n * 4));
+            std::memcpy(bp->h_pin + bp->g_off, bp->g.data(), (size_t)n * dim * 32);
+            bp->rec.resize(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                scd::GkrBatchInst &r = bp->rec[i];
+                r.nnz = nnz[i];
+                r.idx = reinterpret_cast<const uint64_t *>(bp->d_in + offs[4 * (size_t)i + 0]);
+                r.vals = reinterpret_cast<const uint4 *>(bp->d_in + offs[4 * (size_t)i + 1]);
+                r.f2 = reinterpret_cast<const uint4 *>(bp->d_in + offs[4 * (size_t)i + 2]);
+                r.f3 = reinterpret_cast<const uint4 *>(bp->d_in + offs[4 * (size_t)i + 3]);
+                r.g = reinterpret_cast<const uint4 *>(d_up + bp->g_off + (size_t)i * dim * 32);
+            }
+            std::memcpy(bp->h_pin + bp->rec_off, bp->rec.data(), (size_t)n * sizeof(scd::GkrBatchInst));
+            HIP_TRY(hipMemcpyAsync(d_up, bp->h_pin, bp->u_off, hipMemcpyHostToDevice, bp->stream));
+            const scd::GkrBatchInst *d_rec = reinterpret_cast<const scd::GkrBatchInst *>(d_up + bp->rec_off);
+            // device-resident lists: an index out of range is found here, in front of any kernel that follows the indices (host lists: checked above)
+            if (dev_in)
+                if (int rc = gkr_check_idx_on_device(d_rec, n, dim, bp->h_pin, d_up, bp->flag_off, bp->stream)) return rc;
+            if (bp->one_block) {
+                scd::BatchGkrPhaseArgs A;
+                std::memset(&A, 0, sizeof(A));
+                A.inst = d_rec;
+                A.work_a = reinterpret_cast<int32_t *>(bp->d_buf);
+                A.n = n;
+                A.dim = dim;
+                HIP_TRY(scd::launch_batch_gkr_phase(1, A, bp->stream));
+            }
+            HIP_TRY(hipStreamSynchronize(bp->stream)); // nothing of the caller's is read after the call returns
+        }
+        if (bp->one_block) return SC_OK;
+        bp->p1.assign(n, nullptr);
+        bp->p2.assign(n, nullptr);
+        bp->f2u.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const scd::GkrBatchInst &I = bp->rec[i];
+            int rc = sc_internal_gkr_dense_table(1, I.idx, I.vals, nnz[i], dim, I.f3, bp->g[(size_t)i * dim].l, nullptr, serial_table(bp, i, 0)); // mod.rs:30-38
+            if (rc == SC_OK) rc = serial_prover(bp, &bp->p1[i], serial_table(bp, i, 0), I.f2);
+            if (rc) return prefix(rc, i);
+        }
+        return SC_OK;
+    };
+    if (int rc = build()) {
+        const std::string why = sc_last_error(); // (the frees below may run library calls of their own)
+        destroy(bp);
+        return sc_internal_fail(rc, "%s", why.c_str());
+    }
+    *out = bp;
+    return SC_OK;
+}
+
+extern "C" void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp) { destroy(bp); }
+
+extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t *r_or_null, uint32_t r_shared, uint64_t *out_evals) {
+    if (!bp || !out_evals) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    // validation, sc_batch_prove_round's precedence; every check comes before the first change to the handle
+    if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
+    if (r_or_null && bp->round == 0) return sc_internal_fail(SC_ERR_FIRST_ROUND_HAS_MSG, "first round should be prover first.");
+    if (!r_or_null && bp->round > 0) return sc_internal_fail(SC_ERR_MISSING_MSG, "verifier message is empty");
+    if (bp->round + 1 > 2 * bp->dim) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
+    std::vector<sch::Fr> chal;
+    if (r_or_null)
+        if (int rc = take_challenges(bp, r_or_null, r_shared, chal)) return rc;
+    const uint32_t n = bp->n, dim = bp->dim, t = bp->round, phase = t / dim, r = t % dim;
+    if (bp->one_block) {
+        const SharedMeta &s = bp->s;
+        DeviceGate gate_(bp->device);
+        HIP_TRY(hipSetDevice(bp->device));
+        char *d_up = bp->d_buf + 2 * bp->work_bytes;
+        if (r_or_null)
+            if (int rc = upload_challenge(bp, t - 1, chal)) return rc;
+        if (t == dim) { // the phase change: f2(u), f1(g, u, .), f2(u) f3 -> area B
+            scd::BatchGkrPhaseArgs P;
+            std::memset(&P, 0, sizeof(P));
+            P.inst = reinterpret_cast<const scd::GkrBatchInst *>(d_up + bp->rec_off);
+            P.work_a = reinterpret_cast<int32_t *>(bp->d_buf);
+            P.work_b = reinterpret_cast<int32_t *>(bp->d_buf + bp->work_bytes);
+            P.u = reinterpret_cast<const uint4 *>(d_up + bp->u_off);
+            P.f2u = reinterpret_cast<uint4 *>(d_up + bp->f2u_off);
+            P.n = n;
+            P.dim = dim;
+            HIP_TRY(scd::launch_batch_gkr_phase(2, P, bp->stream));
+        }
+        scd::BatchRoundArgs A;
+        std::memset(&A, 0, sizeof(A));
+        A.work = reinterpret_cast<int32_t *>(bp->d_buf + (phase ? bp->work_bytes : 0));
+        A.Wm = reinterpret_cast<const uint4 *>(d_up + bp->w_off);
+        A.w_stride = 0; // a coefficient of one: the same matrices for every instance
+        A.chal = r ? reinterpret_cast<const uint4 *>(d_up + bp->u_off + (size_t)(t - 1) * n * 32) : nullptr;
+        A.chal_shared = 0;
+        A.out = reinterpret_cast<uint4 *>(d_up + bp->msg_off);
+        A.n = n;
+        A.n_tables = 2;
+        A.nv = dim;
+        A.round = r;
+        A.n_combos = s.n_combos;
+        A.K = 1;
+        A.D = 3;
+        HIP_TRY(scd::launch_batch_round(A, s.combo, s.fin, bp->stream));
+        scd::plan_hit(scd::kPlanBatchGkrRoundsOneBlock);
+        HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->msg_off, d_up + bp->msg_off, (size_t)n * 96, hipMemcpyDeviceToHost, bp->stream));
+        HIP_TRY(hipStreamSynchronize(bp->stream));
+        std::memcpy(out_evals, bp->h_pin + bp->msg_off, (size_t)n * 96);
+    } else {
+        scd::plan_hit(scd::kPlanBatchGkrRoundsSerial);
+        for (uint32_t i = 0; i < n; ++i) {
+            int rc = SC_OK;
+            if (t == dim) rc = serial_phase_two(bp, i, chal);
+            if (rc == SC_OK) rc = sc_prove_round(phase ? bp->p2[i] : bp->p1[i], r ? challenge_of(chal, i).l : nullptr, out_evals + (size_t)i * 12);
+            if (rc) {
+                bp->exhausted = true; // (a failure part of the way through the batch: the handle needs a reset)
+                return prefix(rc, i);
+            }
+        }
+    }
+    if (r_or_null) bp->randomness.push_back(std::move(chal));
+    bp->round++;
+    return SC_OK;
+}
+
+extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_t *r, uint32_t r_shared, uint64_t *out_uv_or_null, uint64_t *out_final_or_null) {
+    if (!bp || !r) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    if (bp->exhausted || bp->round != 2 * bp->dim) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "finish needs a prover that has answered its last round");
+    std::vector<sch::Fr> chal;
+    if (int rc = take_challenges(bp, r, r_shared, chal)) return rc;
+    const uint32_t n = bp->n, dim = bp->dim;
+    std::vector<sch::Fr> fin((size_t)n * 3); // f1(g,u,v), f2(u), f2(u) f3(v)
+    if (bp->one_block) {
+        DeviceGate gate_(bp->device);
+        HIP_TRY(hipSetDevice(bp->device));
+        char *d_up = bp->d_buf + 2 * bp->work_bytes;
+        if (int rc = upload_challenge(bp, 2 * dim - 1, chal)) return rc;
+        HIP_TRY(scd::launch_batch_rounds_export(reinterpret_cast<const int32_t *>(bp->d_buf + bp->work_bytes), 0, n, 2, dim, dim - 1,
+                                                reinterpret_cast<const uint4 *>(d_up + bp->u_off + (size_t)(2 * dim - 1) * n * 32), 0u, reinterpret_cast<uint4 *>(d_up + bp->exp_off),
+                                                bp->stream));
+        HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->f2u_off, d_up + bp->f2u_off, bp->exp_off - bp->f2u_off + (size_t)n * 64, hipMemcpyDeviceToHost, bp->stream));
+        HIP_TRY(hipStreamSynchronize(bp->stream));
+        const sch::Fr *f2u = reinterpret_cast<const sch::Fr *>(bp->h_pin + bp->f2u_off), *ex = reinterpret_cast<const sch::Fr *>(bp->h_pin + bp->exp_off);
+        for (uint32_t i = 0; i < n; ++i) {
+            fin[3 * (size_t)i + 0] = ex[2 * (size_t)i];
+            fin[3 * (size_t)i + 1] = f2u[i];
+            fin[3 * (size_t)i + 2] = ex[2 * (size_t)i + 1];
+        }
+    } else {
+        for (uint32_t i = 0; i < n; ++i) {
+            sc_prover *p = bp->p2[i];
+            char *d = bp->d_fin + (size_t)i * 64;
+            sch::Fr two[2];
+            int rc = sc_prover_bind_final(p, challenge_of(chal, i).l, reinterpret_cast<uint64_t *>(d));
+            if (rc == SC_OK) {
+                DeviceGate gate_(bp->device);
+                hipError_t e = hipMemcpyAsync(two, d, 64, hipMemcpyDeviceToHost, p->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    rc = sc_internal_fail(SC_ERR_HIP, "copying the final table values failed: %s", hipGetErrorString(e));
+                }
+            }
+            if (rc) {
+                bp->exhausted = true;
+                return prefix(rc, i);
+            }
+            fin[3 * (size_t)i + 0] = two[0];
+            fin[3 * (size_t)i + 1] = bp->f2u[i];
+            fin[3 * (size_t)i + 2] = two[1];
+        }
+    }
+    bp->randomness.push_back(std::move(chal));
+    bp->exhausted = true;
+    if (out_uv_or_null)
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t j = 0; j < 2 * dim; ++j) std::memcpy(out_uv_or_null + ((size_t)i * 2 * dim + j) * 4, &challenge_of(bp->randomness[j], i), 32);
+    if (out_final_or_null) std::memcpy(out_final_or_null, fin.data(), fin.size() * 32);
+    return SC_OK;
+}
+
+extern "C" int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness, uint64_t *tables_out, uint32_t *round) {
+    if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (instance >= bp->n) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: the handle holds %u instances", instance, bp->n);
+    if (randomness)
+        for (size_t j = 0; j < bp->randomness.size(); ++j) std::memcpy(randomness + 4 * j, &challenge_of(bp->randomness[j], instance), 32);
+    if (n_randomness) *n_randomness = (uint32_t)bp->randomness.size();
+    if (round) *round = bp->round;
+    if (!tables_out) return SC_OK;
+    if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "tables were consumed by sc_gkr_batch_prover_finish");
+    // the current phase's two tables: phase one's until round call dim has built phase two's; bound = the phase's max(round - 1, 0)
+    const uint32_t dim = bp->dim, phase = bp->round > dim ? 1u : 0u, pr = bp->round - phase * dim, bound = pr > 0 ? pr - 1 : 0;
+    if (!bp->one_block) return sc_prover_state(phase ? bp->p2[instance] : bp->p1[instance], nullptr, nullptr, tables_out, nullptr);
+    const size_t bytes = (size_t)2 * ((size_t)32 << (dim - bound));
+    DeviceGate gate_(bp->device);
+    HIP_TRY(hipSetDevice(bp->device));
+    char *d_up = bp->d_buf + 2 * bp->work_bytes;
+    HIP_TRY(scd::launch_batch_rounds_export(reinterpret_cast<const int32_t *>(bp->d_buf + (phase ? bp->work_bytes : 0)), instance, 1, 2, dim, bound, nullptr, 0,
+                                            reinterpret_cast<uint4 *>(d_up + bp->exp_off), bp->stream));
+    HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->exp_off, d_up + bp->exp_off, bytes, hipMemcpyDeviceToHost, bp->stream));
+    HIP_TRY(hipStreamSynchronize(bp->stream));
+    std::memcpy(tables_out, bp->h_pin + bp->exp_off, bytes);
+    return SC_OK;
+}
+
+extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
+    if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (!bp->one_block)
+        for (uint32_t i = 0; i < bp->n; ++i) // phase one's provers borrow the handle's own tables: rewound in place (phase two's are rewound over new tables at the phase change)
+            if (int rc = sc_prover_reset(bp->p1[i], nullptr, SC_TABLES_ON_DEVICE)) return prefix(rc, i);
+    // (one block: area A's depth 0 was never overwritten)
+    bp->round = 0;
+    bp->exhausted = false;
+    bp->randomness.clear();
+    return SC_OK;
+}

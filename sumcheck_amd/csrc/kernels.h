@@ -343,6 +343,20 @@ hipError_t launch_batch_rounds_load(const uint4 *const *tables, uint32_t n, uint
 // chal (first + count elements, or ONE when chal_shared) every pair of entries is bound once more on the way out (bind_final)
 hipError_t launch_batch_rounds_export(const int32_t *work, uint32_t first, uint32_t count, uint32_t n_tables, uint32_t nv, uint32_t bound, const uint4 *chal_or_null,
                                       uint32_t chal_shared, uint4 *out, hipStream_t stream);
+// Batched interactive GKR rounds (kernels_batch_gkr_rounds.hip): sc_gkr_batch_prover_*.  The two initialisations of GKRRoundSumcheck::prove
+// as plain launches, one block per instance, that WRITE k_batch_round's work areas (U = 2) instead of staying inside a persistent block:
+//   k_batch_gkr_phase<1>  eq(g, .), h_g through bg_accumulate<1>'s cells -> area A, table 0, depth 0; f2 -> area A, table 1, depth 0;
+//   k_batch_gkr_phase<2>  the two entries left of area A's table 1 (depth dim - 1) bound with u_{dim-1}: f2(u), canonical, kept in f2u[i];
+//                         eq(g, .), eq(u, .), f1(g, u, .) through bg_accumulate<2> -> area B, table 0; f3 * f2(u) -> area B, table 1.
+// Dynamic LDS: eq(g, .) | eq(u, .) | the cells, 128 B x 2^dim (64 KB at dim 9); no tables.  The envelope is gkr_batch_shape_fits'.
+struct BatchGkrPhaseArgs {
+    const GkrBatchInst *inst;   // device, n records
+    int32_t *work_a, *work_b;   // device: n x 2 x 2 x 2^dim slots each (phase 1 writes A; phase 2 reads A and writes B)
+    const uint4 *u;             // device: the challenges the handle has received, [challenge j][instance] elements (phase 2 reads j < dim)
+    uint4 *f2u;                 // device: n elements (phase 2 writes)
+    uint32_t n, dim;
+};
+hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -408,6 +422,8 @@ enum Plan {
     kPlanGkrBucketedCounted,  // ... counting sort into buckets
     kPlanGkrListForm,         // ... sort + merge + scatter
     kPlanGkrCoeffFromBound,   // phase two's coefficient f2(u) from phase one's bound table
+    kPlanBatchGkrRoundsOneBlock, // sc_gkr_batch_prove_round: k_batch_round over the work areas k_batch_gkr_phase<1|2> fill, one launch per round for the whole batch
+    kPlanBatchGkrRoundsSerial, // ... a loop of sc_prove_round over n ordinary provers per phase inside the handle (dim or nnz beyond the envelope, policy "batch" = 0)
     kPlanGkrSharded,          // sc_gkr_prove_sharded
     kPlanBatchRoundsOneBlock, // sc_batch_prove_round: k_batch_round, one block per instance, one launch per round for the whole batch
     kPlanBatchRoundsSerial,   // ... a loop of sc_prove_round over n handles inside the batch handle (shapes beyond the envelope, policy "batch" = 0)

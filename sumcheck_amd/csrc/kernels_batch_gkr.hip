@@ -19,36 +19,10 @@
 #include <algorithm>
 
 #include "batch_round.hpp"
-#include "wide_cell.hpp"
 
 namespace scd {
 
-// kPhase 1: cell x, term eq(g,z) * v * f3[y]; kPhase 2: cell y, term eq(g,z) * eq(u,x) * v.  The cells (lane-major: cell[j << dim | c],
-// neighbouring cells in neighbouring banks) are zeroed, filled and folded into table `dst`.  Ends behind a barrier.
-template <int kPhase>
-__device__ __forceinline__ void bg_accumulate(uint64_t *cell, int32_t *dst, const GkrBatchInst &I, const uint32_t dim, const uint4 *eq_g, const uint4 *eq_u) {
-    const uint32_t tid = threadIdx.x, cap = 1u << dim, mask = cap - 1u;
-    for (uint32_t i = tid; i < 8u * cap; i += kTsBlock) cell[i] = 0;
-    __syncthreads();
-    for (uint64_t i = tid; i < I.nnz; i += kTsBlock) {
-        const uint64_t id = I.idx[i];
-        const uint32_t z = (uint32_t)id & mask, x = (uint32_t)(id >> dim) & mask, y = (uint32_t)(id >> (2 * dim)) & mask; // (masked: see the head of the file)
-        const Fr a = fr_mul(fr_load(eq_g + 2 * z), fr_load(I.vals + 2 * i));
-        const Fr t = kPhase == 1 ? fr_mul(a, fr_load(I.f3 + 2 * (size_t)y)) : fr_mul(a, fr_load(eq_u + 2 * x));
-        const uint32_t c = kPhase == 1 ? x : y;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) __hip_atomic_fetch_add(cell + (((uint32_t)j << dim) | c), (uint64_t)t.v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __syncthreads();
-    for (uint32_t c = tid; c < cap; c += kTsBlock) {
-        uint64_t lane[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) lane[j] = cell[((uint32_t)j << dim) | c];
-        bt_lds_store(dst + c * (uint32_t)kBtEnt, fe_from_fr(wide_fold_cell(lane)));
-    }
-    __syncthreads();
-}
-
+// (bg_accumulate, the cells both phases are added up in: batch_round.hpp -- shared with k_batch_gkr_phase, kernels_batch_gkr_rounds.hip)
 __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, const ComboMeta meta, const FinMeta fin) {
     constexpr int kSlots = 2; // one product of two tables
     extern __shared__ uint4 dyn_lds[];
@@ -106,7 +80,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, co
         if ((uint32_t)tid < 2 * dim) g_sh[tid] = I.g[tid];
         __syncthreads();
         bg_build_eq(eq_g, reinterpret_cast<uint4 *>(cell), g_sh, dim);
-        bg_accumulate<1>(cell, tab0, I, dim, eq_g, eq_u);
+        bg_accumulate<1>(cell, I, dim, eq_g, eq_u, [&](const uint32_t c, const Fe &v) { bt_lds_store(tab0 + c * (uint32_t)kBtEnt, v); });
         // ---- phase one: dim rounds over (h_g, f2); EVERY challenge is fetched, the last one too ------------------------------------------
         uint32_t E = cap;
         bool dropped = false;
@@ -127,7 +101,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr(const BatchGkrArgs A, co
         __syncthreads(); // (every lane has read it)
         for (uint32_t e = tid; e < cap; e += kTsBlock) bt_lds_store(tab1 + e * (uint32_t)kBtEnt, fe_from_fr(fr_mul(fr_load(I.f3 + 2 * (size_t)e), f2u)));
         bg_build_eq(eq_u, reinterpret_cast<uint4 *>(cell), u_sh, dim);
-        bg_accumulate<2>(cell, tab0, I, dim, eq_g, eq_u);
+        bg_accumulate<2>(cell, I, dim, eq_g, eq_u, [&](const uint32_t c, const Fe &v) { bt_lds_store(tab0 + c * (uint32_t)kBtEnt, v); });
         // ---- phase two: dim rounds over (f1_gu, f2(u) f3), messages dim .. 2 dim - 1 -----------------------------------------------------
         E = cap;
         for (uint32_t r = 0; r < dim; ++r) {

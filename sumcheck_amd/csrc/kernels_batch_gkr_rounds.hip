@@ -1,0 +1,64 @@
+// kernels_batch_gkr_rounds.hip -- the two initialisations of many small GKR round proofs as plain launches (k_batch_gkr_phase<1|2>):
+// sc_gkr_batch_prover_*, the interactive rounds of GKRRoundSumcheck::prove (reference src/gkr_round_sumcheck/mod.rs:93-139) under the
+// caller's transcript.
+//
+// k_batch_gkr (kernels_batch_gkr.hip) builds both phases' tables inside ONE persistent block that then waits for the host's challenges.
+// Here the caller hands in every challenge, so nothing waits: the rounds are k_batch_round's (kernels_batch_rounds.hip, one launch per
+// round out of a device work area), and what is left of k_batch_gkr are its two initialisations, one block per instance each, that write
+// their tables into a work area as 48-byte slots instead of keeping them in LDS:
+//   phase<1>  (once, when the handle is built)  eq(g, .) by bg_build_eq; h_g[x] = sum eq(g,z) * v * f3[y] (mod.rs:30-38) through
+//             bg_accumulate<1>'s cells -> area A, table 0, depth 0; f2 -> area A, table 1, depth 0.  Depth 0 is never written again.
+//   phase<2>  (in front of round dim's launch)  what is left of area A's table 1 -- two entries at depth dim - 1 -- bound with u_{dim-1},
+//             k_batch_rounds_export's arithmetic (entries in (-(dim - 1) p, p), dim <= 9): f2(u), canonical, stored per instance for the
+//             caller's subclaim; eq(g, .) and eq(u, .); f1(g, u, .)[y] = sum eq(g,z) * eq(u,x) * v (mod.rs:62) through bg_accumulate<2>
+//             -> area B, table 0, depth 0; f3 * f2(u) (fr_mul: mod.rs:71-75, literally) -> area B, table 1, depth 0.
+// Every index is masked to dim bits per component before it addresses LDS or f3 (bg_accumulate); an index with a bit at or above 3 dim
+// is an argument error that k_batch_gkr_idx_range reports in front of the first launch that follows the indices.
+// LDS: eq(g, .) | eq(u, .) (32 B per cell) | the accumulator (64 B per cell, also bg_build_eq's scratch): 128 B x 2^dim; no tables.
+#include "batch_round.hpp"
+
+namespace scd {
+
+template <int kPhase>
+__global__ __launch_bounds__(kTsBlock) void k_batch_gkr_phase(const BatchGkrPhaseArgs A) {
+    extern __shared__ uint4 dyn_lds[];
+    __shared__ uint4 g_sh[2 * kGkrBatchMaxDim], u_sh[2 * kGkrBatchMaxDim]; // the points g and u
+    const uint32_t tid = threadIdx.x, inst = blockIdx.x; // (the grid is exactly n blocks)
+    const uint32_t dim = A.dim, cap = 1u << dim;
+    uint4 *const eq_g = dyn_lds, *const eq_u = eq_g + 2 * (size_t)cap;
+    uint64_t *const cell = reinterpret_cast<uint64_t *>(eq_u + 2 * (size_t)cap);
+    const GkrBatchInst I = A.inst[inst];
+    const size_t region = (size_t)inst * 2 * 2 * cap * kBtEnt; // the instance's two tables, table u at + u * 2 * cap slots
+    int32_t *const dst = (kPhase == 1 ? A.work_a : A.work_b) + region;
+    if (tid < 2 * dim) {
+        g_sh[tid] = I.g[tid];
+        if (kPhase == 2) u_sh[tid] = A.u[2 * ((size_t)(tid >> 1) * A.n + inst) + (tid & 1u)];
+    }
+    __syncthreads();
+    bg_build_eq(eq_g, reinterpret_cast<uint4 *>(cell), g_sh, dim);
+    if (kPhase == 1) {
+        bg_accumulate<1>(cell, I, dim, eq_g, eq_g, [&](const uint32_t c, const Fe &v) { br_slot_store(dst + (size_t)c * kBtEnt, v); });
+        for (uint32_t e = tid; e < cap; e += kTsBlock) br_slot_store(dst + ((size_t)2 * cap + e) * kBtEnt, fe_from_fr(fr_load(I.f2 + 2 * (size_t)e)));
+    } else {
+        // f2(u): every lane binds the same two entries (uniform loads), lane 0 keeps the result
+        const int32_t *src = A.work_a + region + ((size_t)2 * cap + batch_rounds_off(dim, dim - 1u)) * kBtEnt;
+        const FeU r32 = feu_shl5(fr_load(u_sh + 2 * (dim - 1u)).v);
+        const Fe lo = br_slot_load(src), hi = br_slot_load(src + kBtEnt);
+        const Fr f2u = fe_to_fr(fe_carry_pass(fe_add(lo, fe_mul_u<true>(fe_sub(hi, lo), r32))));
+        if (tid == 0) fr_store(A.f2u + 2 * (size_t)inst, f2u);
+        bg_build_eq(eq_u, reinterpret_cast<uint4 *>(cell), u_sh, dim);
+        bg_accumulate<2>(cell, I, dim, eq_g, eq_u, [&](const uint32_t c, const Fe &v) { br_slot_store(dst + (size_t)c * kBtEnt, v); });
+        for (uint32_t e = tid; e < cap; e += kTsBlock) br_slot_store(dst + ((size_t)2 * cap + e) * kBtEnt, fe_from_fr(fr_mul(fr_load(I.f3 + 2 * (size_t)e), f2u)));
+    }
+}
+
+hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream) {
+    if ((phase != 1 && phase != 2) || args.n == 0 || !gkr_batch_shape_fits(args.dim, 0) || !args.inst || !args.work_a) return hipErrorInvalidValue;
+    if (phase == 2 && (!args.work_b || !args.u || !args.f2u)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)128 << args.dim; // (at most 64 KB: within a launch's default limit)
+    if (phase == 1) hipLaunchKernelGGL(k_batch_gkr_phase<1>, dim3(args.n), dim3(kTsBlock), lds, stream, args);
+    else hipLaunchKernelGGL(k_batch_gkr_phase<2>, dim3(args.n), dim3(kTsBlock), lds, stream, args);
+    return hipGetLastError();
+}
+
+} // namespace scd

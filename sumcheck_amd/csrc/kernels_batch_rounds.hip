@@ -18,13 +18,7 @@
 namespace scd {
 
 static_assert(kBatchRoundSlotBytes == kBtEnt * sizeof(int32_t), "the work area holds LDS slots verbatim");
-// a slot of the work area (global memory): three 16-byte words, the last one's upper lanes zero
-__device__ __forceinline__ Fe br_slot_load(const int32_t *t) { return bt_lds_load(t); }
-__device__ __forceinline__ void br_slot_store(int32_t *t, const Fe &v) {
-    *reinterpret_cast<int4 *>(t) = make_int4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    *reinterpret_cast<int4 *>(t + 4) = make_int4(v.l[4], v.l[5], v.l[6], v.l[7]);
-    *reinterpret_cast<int4 *>(t + 8) = make_int4(v.l[8], 0, 0, 0);
-}
+// (a slot of the work area: br_slot_load / br_slot_store, batch_round.hpp)
 
 template <int kSlots>
 __global__ __launch_bounds__(kTsBlock) void k_batch_round(const BatchRoundArgs A, const ComboMeta meta, const FinMeta fin) {

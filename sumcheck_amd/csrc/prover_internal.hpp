@@ -281,6 +281,20 @@ void instance_weights(const SharedMeta &s, const uint64_t *coeffs, sch::Fr *out)
 const char *first_structure_difference(const sc_poly_desc &a, const sc_poly_desc &b);    // the first field in which two descriptors of a batch differ, or null
 int batch_check_desc(const sc_poly_desc *descs, uint32_t i);      // validate_desc on instance i, its error text behind "instance %u: "
 int batch_check_structure(const sc_poly_desc *descs, uint32_t i); // SC_ERR_BAD_ARG "instance %u differs from instance 0 in %s: a batch has one structure"
+// what the batched GKR entry points share (sc_gkr_prove_batch, sc_gkr_subclaim_batch, sc_gkr_batch_prover_init): the callers' arrays ...
+struct GkrBatchIn {
+    uint32_t n, dim;
+    const uint64_t *const *f1_idx, *const *f1_vals;
+    const uint64_t *nnz;
+    const uint64_t *const *f2, *const *f3, *const *g;
+    bool on_device; // SC_TABLES_ON_DEVICE: read in place
+};
+int gkr_check_instance(const GkrBatchIn &in, uint32_t i, const uint64_t *uv_or_null); // ... sc_gkr_prove's checks on instance i (no HIP call), errors behind "instance %u: "
+// ... and the check of device-resident index lists in front of any kernel that follows them (flags: n zeroed words at flag_off of the image)
+int gkr_check_idx_on_device(const scd::GkrBatchInst *d_rec, uint32_t n, uint32_t dim, char *h_up, char *d_up, size_t flag_off, hipStream_t stream);
+// ---- gkr.hip ----
+int sc_internal_gkr_dense_table(int phase, const uint64_t *d_idx, const void *d_vals, uint64_t nnz, uint32_t dim, const void *d_f3, const uint64_t *g, const uint64_t *u_or_null,
+                                void *d_out); // one dense table of a GKR proof by sc_gkr_prove's route, device-resident inputs
 // ---- comm.hip ----
 struct NcclApi {
     void *lib = nullptr;

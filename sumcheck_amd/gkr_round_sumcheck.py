@@ -314,9 +314,103 @@ class GKRRoundSumcheck:
         return out
 
     @staticmethod
+    def prover_init_batch(f1s: Sequence[SparseMultilinearExtension], f2s: Sequence[DenseMultilinearExtension],
+                          f3s: Sequence[DenseMultilinearExtension], gs) -> "GKRBatchProverState":
+        """n x the two prover states of GKRRoundSumcheck.prove of one dim behind one handle (sc_gkr_batch_prover_init): the interactive
+        rounds under the CALLER's transcript -- 2 dim calls of prove_round, then finish.  Inputs as for prove_batch (all on the host or
+        all on the GPU; the same object may stand for several instances); they are copied: nothing is read after this returns."""
+        n = len(f1s)
+        assert len(f2s) == n and len(f3s) == n and len(gs) == n, "one f1, f2, f3 and g per instance"
+        dim = f2s[0].num_vars if n else 0
+        ons = [m.on_device for m in list(f1s) + list(f2s) + list(f3s)]
+        dev = bool(ons) and all(ons)
+        assert dev or not any(ons), "mixing host and device inputs is not supported"
+        g_arr = []
+        for i in range(n):
+            assert f2s[i].num_vars == dim and f3s[i].num_vars == dim and f1s[i].num_vars == 3 * dim, f"instance {i}: a batch has one dim"
+            g_arr.append(_np64(gs[i]).reshape(-1, 4))
+            assert g_arr[i].shape[0] == dim
+        if dev:
+            import torch
+            torch.cuda.current_stream(f2s[0].evaluations.device).synchronize()  # the library works on its own stream
+
+        def ptrs(vals):
+            return (C.c_void_p * max(n, 1))(*[C.cast(v, C.c_void_p) for v in vals])
+
+        f1p = [f._ptrs() for f in f1s]
+        nnz = (C.c_uint64 * max(n, 1))(*[f.nnz for f in f1s])
+        h = C.c_void_p()
+        check(lib().sc_gkr_batch_prover_init(n, dim, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
+                                             ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), SC_TABLES_ON_DEVICE if dev else 0, C.byref(h)))
+        return GKRBatchProverState(h, n, dim)
+
+    @staticmethod
     def verify(rng: Blake2b512Rng, f2_num_vars: int, proof: GKRProof, claimed_sum) -> GKRRoundSumcheckSubClaim:
         """mod.rs:147-192"""
         dim = f2_num_vars
         u, exp1 = _verify_phase(rng, proof.phase1_sumcheck_msgs, dim, claimed_sum)
         v, exp2 = _verify_phase(rng, proof.phase2_sumcheck_msgs, dim, exp1)
         return GKRRoundSumcheckSubClaim(u, v, exp2)
+
+
+class GKRBatchProverState:
+    """The handle of GKRRoundSumcheck.prover_init_batch (sc_gkr_batch_prover_*): n instances, 2 dim rounds, one call per round."""
+
+    def __init__(self, h, n: int, dim: int):
+        self._h, self.n, self.dim = h, n, dim
+
+    def _chal(self, r, shared: bool):
+        a = np.ascontiguousarray(_np64(r).reshape(-1, 4))
+        assert a.shape[0] == (1 if shared else self.n), "one challenge per instance, or one for all with shared=True"
+        return a
+
+    def prove_round(self, r=None, shared: bool = False) -> np.ndarray:
+        """-> (n, 3, 4): message t of phase one (calls 0 .. dim-1), then of phase two.  r: None exactly on the first call, afterwards the
+        previous round's challenges, (n, 4) or -- shared -- (4,)"""
+        out = np.empty((self.n, 3, 4), dtype=np.uint64)
+        a = None if r is None else self._chal(r, shared)
+        check(lib().sc_gkr_batch_prove_round(self._h, None if a is None else _ptr(a), 1 if shared else 0, _ptr(out)))
+        return out
+
+    def finish(self, r, shared: bool = False):
+        """the last challenge v_{dim-1} -> (uv (n, 2, dim, 4), final (n, 3, 4): f1(g,u,v), f2(u), f2(u) f3(v))"""
+        a = self._chal(r, shared)
+        uv = np.empty((self.n, 2, self.dim, 4), dtype=np.uint64)
+        fin = np.empty((self.n, 3, 4), dtype=np.uint64)
+        check(lib().sc_gkr_batch_prover_finish(self._h, _ptr(a), 1 if shared else 0, _ptr(uv), _ptr(fin)))
+        return uv, fin
+
+    @property
+    def round(self) -> int:
+        rnd = C.c_uint32()
+        check(lib().sc_gkr_batch_prover_state(self._h, 0, None, None, None, C.byref(rnd)))
+        return int(rnd.value)
+
+    def randomness(self, i: int) -> np.ndarray:
+        """u followed by the v's instance i has received so far"""
+        out = np.zeros((2 * self.dim, 4), dtype=np.uint64)
+        k = C.c_uint32()
+        check(lib().sc_gkr_batch_prover_state(self._h, i, _ptr(out), C.byref(k), None, None))
+        return out[: k.value].copy()
+
+    def tables(self, i: int) -> np.ndarray:
+        """the current phase's two tables of instance i, canonical: (2, 2^(dim - bound), 4)"""
+        t = self.round
+        pr = t - self.dim if t > self.dim else t
+        out = np.empty((2, 1 << (self.dim - max(pr - 1, 0)), 4), dtype=np.uint64)
+        check(lib().sc_gkr_batch_prover_state(self._h, i, None, None, _ptr(out), None))
+        return out
+
+    def reset(self) -> None:
+        check(lib().sc_gkr_batch_prover_reset(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            lib().sc_gkr_batch_prover_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
