@@ -646,6 +646,7 @@ int sparse_fix(DevBuf &mem, const uint64_t *d_idx, const Fr *d_vals, uint64_t n,
         if (rc_eq) return rc_eq;
         hipLaunchKernelGGL(k_sparse_scale, dim3(grid_for(n)), dim3(kBlock), 0, s, d_idx, d_vals, (const uint32_t *)nullptr, eq, k, n, key, w);
     } else {
+        scd::plan_hit(scd::kPlanGkrEqDirect);
         Fr *d_point = nullptr;
         G_TRY(mem.alloc(&d_point, k));
         G_TRY(hipMemcpyAsync(d_point, point, (size_t)k * 32, hipMemcpyHostToDevice, s));

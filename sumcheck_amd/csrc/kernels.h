@@ -421,6 +421,7 @@ enum Plan {
     kPlanGkrBucketedGrouped,  // GKR initialisation: buckets of an index-ordered list (k_bucket_bounds)
     kPlanGkrBucketedCounted,  // ... counting sort into buckets
     kPlanGkrListForm,         // ... sort + merge + scatter
+    kPlanGkrEqDirect,         // ... the list form's fold with eq evaluated per entry (k_sparse_scale_direct: 2^k > 8 n + 1024, no eq table)
     kPlanGkrCoeffFromBound,   // phase two's coefficient f2(u) from phase one's bound table
     kPlanBatchGkrRoundsOneBlock, // sc_gkr_batch_prove_round: k_batch_round over the work areas k_batch_gkr_phase<1|2> fill, one launch per round for the whole batch
     kPlanBatchGkrRoundsSerial, // ... a loop of sc_prove_round over n ordinary provers per phase inside the handle (dim or nnz beyond the envelope, policy "batch" = 0)

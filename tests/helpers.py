@@ -67,6 +67,19 @@ def random_case(rng: np.random.Generator, nv: int, shapes, n_tables: int, seed: 
     return tabs, coefs
 
 
+def merge_repeated(idx, vals):
+    """a sparse list whose indices may repeat -> (sorted distinct indices, the sums of their values): the map the oracle takes"""
+    idx = np.asarray(idx, dtype=np.uint64).reshape(-1)
+    order = np.argsort(idx, kind="stable")
+    si, sv = idx[order], np.asarray(vals, dtype=np.uint64).reshape(-1, 4)[order]
+    ui, start = np.unique(si, return_index=True)
+    if ui.shape[0] == si.shape[0]:
+        return si, sv
+    ints = cref.mont_to_ints(sv)
+    merged = [sum(ints[a:b]) % cref.P for a, b in zip(start, list(start[1:]) + [len(si)])]
+    return ui, cref.ints_to_mont(merged)
+
+
 def desc_from(nv, shapes, tabs, coefs) -> cref.PolyDesc:
     """flatten like add_product does (first-occurrence order)"""
     order, remap = [], {}

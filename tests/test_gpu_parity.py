@@ -1067,14 +1067,8 @@ def test_gkr_prove_bucketed_initialisation(case, request):
         idx = idx[rng.permutation(idx.shape[0])]
     vals, f2, f3, g = (cref.synth_table(77, 1, idx.shape[0]), cref.synth_table(77, 2, n), cref.synth_table(77, 3, n), cref.synth_table(77, 4, dim))
     if case == "duplicates":  # the oracle takes a map: give it the merged list
-        order = np.argsort(idx, kind="stable")
-        si, sv = idx[order], vals[order]
-        ui, start = np.unique(si, return_index=True)
-        ints = field.to_ints(sv)
-        merged = []
-        for a, b in zip(start, list(start[1:]) + [len(si)]):
-            merged.append(sum(ints[a:b]) % field.P)
-        oi, ov = ui, H.mont(merged)
+        oi, ov = H.merge_repeated(idx, vals)
+        assert oi.shape[0] < idx.shape[0]
     else:
         oi, ov = idx, vals
     if case == "list_form":  # sort + merge instead of the bucketed kernels
