@@ -378,7 +378,11 @@ struct IPForMLSumcheck {
         check(sc_prove_round(state.raw(), v_msg ? v_msg->randomness.l : nullptr, m.evaluations[0].l));
         return m;
     }
-    // n x prover_init of ONE structure behind one handle (sc_batch_prover_init); the tables are copied
+    // n x prover_init of ONE structure behind one handle (sc_batch_prover_init); the tables are copied.  Shapes beyond one block's LDS run n
+    // ordinary provers inside the handle (plan batch.rounds_serial) unless sc_set_policy("batch_slices", 1) is in effect when the handle is built
+    // (default 0): then, for 1 <= num_vars <= 16, products of at most eight multiplicands and a work area (96 bytes x n x tables x 2^num_vars)
+    // of at most 16 GiB, the rounds whose tables do not fit one block give every instance to several blocks (plan batch.rounds_slices: two
+    // launches a round) and the later rounds run as within the envelope, with the same bits
     static BatchProverState prover_init_batch(const std::vector<const ListOfProductsOfPolynomials *> &polynomials) {
         std::vector<std::unique_ptr<ListOfProductsOfPolynomials::Desc>> keep;
         std::vector<sc_poly_desc> descs;

@@ -276,6 +276,15 @@ SC_API int sc_ml_prove_batch(const sc_poly_desc *descs, uint32_t n, sc_rng *cons
  * device's tail slot play no part).  The calls are TOTAL over shapes: beyond the envelope, or with policy "batch" = 0 when the handle is
  * built, the handle holds n ordinary provers (device-side waits off, no resident kernel) and a round is a loop of sc_prove_round, with the
  * same bits; with policy "batch" = 1 or 2 the kernel runs for every n that fits.
+ * SLICED ROUNDS [policy "batch_slices" = 1 when the handle is built; default 0]: shapes beyond one block's LDS keep the work area and the
+ * per-round sequence -- 1 <= num_vars <= 16, products of at most eight multiplicands, a structure that travels as kernel arguments, a work
+ * area [96 bytes x n x tables x 2^num_vars] of at most 16 GiB.  A round whose tables as loaded do not fit one block gives every instance to
+ * several blocks, each a contiguous slice of every table [binding is LSB-first: a slice binds to a slice], as TWO plain launches -- the
+ * slices' sums into a device array, then one block per instance that adds them and forms the message --; from the first round that fits,
+ * the one-launch round above runs on the same work area.  Plan counters: batch.rounds_slices per sliced round call, batch.rounds_one_block
+ * for the others.  State, bind_final, reset, push_randomness and every status code are the same for all three plans.  Measured against
+ * the serial plan [tools/batch_round_slices_bench.py, profiles/batch_round_slices_bench.json]: ahead 9-12x at n = 16 and 26-138x at n = 256,
+ * behind at n = 1 [0.77-0.87x]; the default stays 0.
  * THREADING: one handle, one host thread at a time; distinct handles are independent (the library serialises its HIP calls per device). */
 typedef struct sc_batch_prover sc_batch_prover; /* n x ProverState (prover.rs:19-33) of ONE structure */
 /* SC_API_EXT is SC_API.  It marks the entry points whose prototypes name an opaque type younger than the type table of the header-vs-shim
@@ -524,6 +533,9 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "lag_single" (2)         big rounds that a table named only by single-table products skips after round 1 (0: none .. 4): its products' messages come
  *                            from class sums of the table, and one pass binds the table with every challenge it missed before the next round
  *                            (or anything else) reads it.  The proof does not depend on the value.
+ *   "batch_slices" (0)       sc_batch_prover_init: 1 a shape beyond one block's LDS, up to 2^16 entries per table, runs its first rounds sliced over
+ *                            several blocks per instance (plan batch.rounds_slices) instead of the serial plan; read when a handle is built; "batch" = 0
+ *                            still forces the serial plan.  0 until the sliced plan has been measured.
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);
 SC_API int sc_get_policy(const char *key, int64_t *value);

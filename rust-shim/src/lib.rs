@@ -421,6 +421,11 @@ impl<F: Limbs4> HipBatchProverState<F> {
 }
 
 /// n x `IPForMLSumcheck::prover_init` for polynomials of ONE structure behind one handle (`sc_batch_prover_init`); the tables are copied.
+/// Shapes beyond one block's LDS run n ordinary provers inside the handle (plan `batch.rounds_serial`) unless the library policy
+/// `batch_slices` is 1 when the handle is built (`sc_set_policy`; default 0): then, for 1 <= num_vars <= 16, products of at most eight
+/// multiplicands and a work area (96 bytes x n x tables x 2^num_vars) of at most 16 GiB, the rounds whose tables do not fit one block give
+/// every instance to several blocks (plan `batch.rounds_slices`: two launches a round) and the later rounds run as within the envelope,
+/// with the same bits.
 pub fn prover_init_batch<F: Limbs4>(polynomials: &[ListOfProductsOfPolynomials<F>]) -> HipBatchProverState<F> {
     assert!(!polynomials.is_empty(), "a batch handle holds at least one instance");
     let flats: Vec<Flattened> = polynomials.iter().map(flatten).collect();

@@ -1,30 +1,37 @@
 // batch_rounds.hip -- sc_batch_prover_*: n x IPForMLSumcheck::{prover_init, prove_round} (reference src/ml_sumcheck/protocol/prover.rs:49-153)
 // of one structure behind ONE handle, a round of all n instances per call.  The interactive half of the batched provers (batch.hip is the
 // non-interactive one): the caller owns the transcript(s) and hands in every challenge, so a round is launched after its challenges
-// are known and nothing on the GPU ever waits for the host.  Two plans, chosen when the handle is built, same bits:
+// are known and nothing on the GPU ever waits for the host.  Three plans, chosen when the handle is built (batch_slices.hpp: bs_plan), same bits:
 //   batch.rounds_one_block  k_batch_round (kernels_batch_rounds.hip): one block per instance, one launch per round for the whole batch.  The
 //                           per-round sequence is fixed: upload the challenges, one launch, one copy back, one synchronisation.  The
 //                           tables live in a device work area as 48-byte LDS slots, every binding depth in a region of its own;
+//   batch.rounds_slices     policy "batch_slices" = 1, shapes beyond one block's LDS up to 2^16 entries: the same work area and per-round
+//                           sequence, but the rounds whose tables as loaded do not fit one block run as k_batch_round_slices +
+//                           k_batch_round_fin (kernels_batch_round_slices.hip: several blocks per instance, their sums through a device
+//                           array of partials); from the first round that fits, k_batch_round, counted as batch.rounds_one_block;
 //   batch.rounds_serial     n ordinary sc_prover handles inside the batch handle (device-side waits off, no resident kernel) over the
 //                           handle's own copy of the tables; a round is a loop of sc_prove_round: shapes beyond one block's LDS
-//                           (batch_shape_fits), policy "batch" = 0.
+//                           (batch_shape_fits) unless sliced, policy "batch" = 0.
+#include "batch_slices.hpp"
 #include "prover_internal.hpp"
 
 struct sc_batch_prover {
     int device = 0;
     uint32_t n = 0, nv = 0, U = 0, D = 0, round = 0; // round: rounds proved so far
     bool exhausted = false;
-    bool one_block = false;
+    int plan = scd::kBrSerial; // scd::BatchRoundsPlan; kBrOneBlock and kBrSlices share the work area and everything that reads it
+    bool work_area() const { return plan != scd::kBrSerial; }
     std::vector<std::vector<sch::Fr>> randomness; // per challenge received: n elements, or ONE for a shared challenge
     // the descriptors' structure (host copies: a reset checks new descriptors against it)
     uint32_t max_mult = 0, K = 0, flags = 0;
     std::vector<uint32_t> prod_offsets, prod_indices;
     hipStream_t stream = nullptr;
-    // ---- batch.rounds_one_block ----
+    // ---- batch.rounds_one_block, batch.rounds_slices ----
     SharedMeta s;
-    char *d_buf = nullptr;   // device: work area | matrices | table pointers | challenges | messages | export area | staged host tables
+    char *d_buf = nullptr;   // device: work area | matrices | table pointers | challenges | messages | export area | staged host tables | partials (sliced rounds)
     char *h_pin = nullptr;   // pinned: matrices | table pointers | challenges | messages | export area | staged host tables
     size_t work_bytes = 0, w_off = 0, ptr_off = 0, chal_off = 0, msg_off = 0, exp_off = 0, stage_off = 0, pin_bytes = 0, exp_bytes = 0; // (offsets into h_pin; d_buf: + work_bytes)
+    size_t part_off = 0;     // the partials, into d_buf (behind the mirror of h_pin)
     // ---- batch.rounds_serial ----
     std::vector<sc_prover *> provers;
     char *d_orig = nullptr;  // device: the handle's copy of the tables, [instance][table][2^nv] elements (the n handles borrow it)
@@ -176,7 +183,10 @@ extern "C" int sc_batch_prover_init(const sc_poly_desc *descs, uint32_t n, sc_ba
     }
     if (scd::policy(scd::kPolBatch) != 0 && bp->K > 0) {
         build_shared(&d0, bp->s);
-        bp->one_block = bp->s.fits_args && scd::batch_shape_fits(bp->s.nv, bp->s.U, (int)bp->s.K, (int)bp->s.D, bp->s.max_mult);
+        const SharedMeta &s = bp->s;
+        bp->plan = scd::bs_plan(n, s.nv, s.U, (int)s.K, (int)s.D, s.max_mult, s.n_combos, s.fits_args, scd::policy(scd::kPolBatch), scd::policy(scd::kPolBatchSlices));
+        // (batch_slices.hpp spells batch_shape_fits out for the host tests: the launchers are guarded by the kernels' own)
+        if (bp->plan != scd::kBrSerial && scd::batch_shape_fits(s.nv, s.U, (int)s.K, (int)s.D, s.max_mult) != (bp->plan == scd::kBrOneBlock)) bp->plan = scd::kBrSerial;
     }
     const size_t table_bytes = (size_t)32 << bp->nv;
     auto build = [&]() -> int {
@@ -185,7 +195,7 @@ extern "C" int sc_batch_prover_init(const sc_poly_desc *descs, uint32_t n, sc_ba
             HIP_TRY(hipSetDevice(bp->device));
             HIP_TRY(hipStreamCreateWithFlags(&bp->stream, hipStreamNonBlocking));
         }
-        if (!bp->one_block) {
+        if (!bp->work_area()) {
             {
                 DeviceGate gate_(bp->device);
                 HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_orig), (size_t)n * bp->U * table_bytes));
@@ -206,8 +216,10 @@ extern "C" int sc_batch_prover_init(const sc_poly_desc *descs, uint32_t n, sc_ba
         bp->exp_off = bp->msg_off + up256((size_t)n * bp->D * 32);
         bp->stage_off = bp->exp_off + up256(bp->exp_bytes);
         bp->pin_bytes = bp->stage_off + (host_tables ? (size_t)n * bp->U * table_bytes : 0);
+        bp->part_off = bp->work_bytes + up256(bp->pin_bytes);
+        const size_t part_bytes = bp->plan == scd::kBrSlices ? (size_t)scd::bs_partials_bytes(n, s.nv, s.U, (int)s.K, (int)s.D, s.n_combos) : 0;
         DeviceGate gate_(bp->device);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), bp->work_bytes + bp->pin_bytes));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), bp->part_off + part_bytes));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bp->h_pin), bp->pin_bytes, hipHostMallocDefault));
         return load_one_block(bp, descs);
     };
@@ -233,7 +245,7 @@ extern "C" int sc_batch_prove_round(sc_batch_prover *bp, const uint64_t *r_or_nu
     if (r_or_null)
         if (int rc = take_challenges(bp, r_or_null, r_shared, chal)) return rc;
     const uint32_t n = bp->n, D = bp->D;
-    if (bp->one_block) {
+    if (bp->work_area()) {
         const SharedMeta &s = bp->s;
         DeviceGate gate_(bp->device);
         HIP_TRY(hipSetDevice(bp->device));
@@ -257,8 +269,13 @@ extern "C" int sc_batch_prove_round(sc_batch_prover *bp, const uint64_t *r_or_nu
         A.n_combos = s.n_combos;
         A.K = (int)s.K;
         A.D = (int)s.D;
-        HIP_TRY(scd::launch_batch_round(A, s.combo, s.fin, bp->stream));
-        scd::plan_hit(scd::kPlanBatchRoundsOneBlock);
+        if (bp->plan == scd::kBrSlices && scd::bs_round_sliced(s.nv, bp->round, s.U, (int)s.K, (int)s.D, s.max_mult)) {
+            HIP_TRY(scd::launch_batch_round_slices(A, reinterpret_cast<uint4 *>(bp->d_buf + bp->part_off), s.combo, s.fin, bp->stream));
+            scd::plan_hit(scd::kPlanBatchRoundsSlices);
+        } else {
+            HIP_TRY(scd::launch_batch_round(A, s.combo, s.fin, bp->stream));
+            scd::plan_hit(scd::kPlanBatchRoundsOneBlock);
+        }
         HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->msg_off, d_up + bp->msg_off, (size_t)n * D * 32, hipMemcpyDeviceToHost, bp->stream));
         HIP_TRY(hipStreamSynchronize(bp->stream));
         std::memcpy(out_evals, bp->h_pin + bp->msg_off, (size_t)n * D * 32);
@@ -295,7 +312,7 @@ extern "C" int sc_batch_prover_state(sc_batch_prover *bp, uint32_t instance, uin
     if (round) *round = bp->round;
     if (!tables_out) return SC_OK;
     if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "tables were consumed by sc_batch_prover_bind_final");
-    if (!bp->one_block) return sc_prover_state(bp->provers[instance], nullptr, nullptr, tables_out, nullptr);
+    if (!bp->work_area()) return sc_prover_state(bp->provers[instance], nullptr, nullptr, tables_out, nullptr);
     const uint32_t bound = bp->round > 0 ? bp->round - 1 : 0;
     const size_t bytes = (size_t)bp->U * ((size_t)32 << (bp->nv - bound));
     DeviceGate gate_(bp->device);
@@ -315,7 +332,7 @@ extern "C" int sc_batch_prover_bind_final(sc_batch_prover *bp, const uint64_t *r
     if (int rc = take_challenges(bp, r, r_shared, chal)) return rc;
     const uint32_t n = bp->n, U = bp->U;
     const size_t bytes = (size_t)n * U * 32;
-    if (bp->one_block) {
+    if (bp->work_area()) {
         DeviceGate gate_(bp->device);
         HIP_TRY(hipSetDevice(bp->device));
         char *d_up = bp->d_buf + bp->work_bytes;
@@ -368,16 +385,16 @@ extern "C" int sc_batch_prover_reset(sc_batch_prover *bp, const sc_poly_desc *de
         own.flags = descs[0].flags;
         if (const char *field = first_structure_difference(own, descs[0]))
             return sc_internal_fail(SC_ERR_BAD_ARG, "instance 0 differs from the handle's structure in %s: a reset does not reallocate", field);
-        if (bp->one_block && !(descs[0].flags & SC_TABLES_ON_DEVICE) && (bp->flags & SC_TABLES_ON_DEVICE))
+        if (bp->work_area() && !(descs[0].flags & SC_TABLES_ON_DEVICE) && (bp->flags & SC_TABLES_ON_DEVICE))
             return sc_internal_fail(SC_ERR_BAD_ARG, "a handle built over device tables has no staging area for host tables: a reset does not reallocate");
-        if (bp->one_block) {
+        if (bp->work_area()) {
             DeviceGate gate_(bp->device);
             HIP_TRY(hipSetDevice(bp->device));
             if (int rc = load_one_block(bp, descs)) return rc;
         } else {
             if (int rc = load_serial(bp, descs)) return rc;
         }
-    } else if (!bp->one_block) {
+    } else if (!bp->work_area()) {
         for (uint32_t i = 0; i < bp->n; ++i) { // the handles borrow the batch handle's own copy of the tables: rewound in place
             int rc = sc_prover_reset(bp->provers[i], nullptr, SC_TABLES_ON_DEVICE);
             if (rc) {
@@ -385,7 +402,7 @@ extern "C" int sc_batch_prover_reset(sc_batch_prover *bp, const sc_poly_desc *de
                 return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
             }
         }
-    } // (one block, the same tables: round 0's slots were never overwritten)
+    } // (a work area, the same tables: round 0's slots were never overwritten)
     bp->round = 0;
     bp->exhausted = false;
     bp->randomness.clear();

@@ -336,7 +336,31 @@ struct BatchRoundArgs {
     int n_combos, K, D;
     uint32_t fin_bytes;         // (filled in by the launcher: LDS layout -- finalize scratch | message | tables)
 };
-hipError_t launch_batch_round(BatchRoundArgs args, const ComboMeta &meta, const FinMeta &fin, hipStream_t stream); // shapes of batch_shape_fits
+hipError_t launch_batch_round(BatchRoundArgs args, const ComboMeta &meta, const FinMeta &fin, hipStream_t stream); // rounds whose tables AS LOADED (nv - max(round - 1, 0) variables) are a shape of batch_shape_fits
+// The rounds of the same work area whose tables as loaded do not fit one block (kernels_batch_round_slices.hip; the rule, the slice size and
+// the partials' size: batch_slices.hpp): k_batch_round_slices, n << slices_log2 blocks, each a slice of 2^slice_log2 entries of every table
+// of its instance -- load, bind, sums into partials[instance][slice][combination], store --, then k_batch_round_fin, one block per
+// instance: the partials' sums, finalize_message, the message.  Two plain launches on one stream; nothing waits, no atomics.
+struct BatchRoundSlicesArgs {
+    int32_t *work;              // as in BatchRoundArgs
+    const uint4 *chal;
+    uint32_t chal_shared;
+    uint4 *partials;            // device: (n << slices_log2) x n_combos elements, canonical
+    uint32_t n_tables, nv, round;
+    int n_combos, K;
+    uint32_t slice_log2, slices_log2; // log2 E_s, log2 S: E_s << slices_log2 entries per table as loaded
+};
+struct BatchRoundFinArgs {
+    const uint4 *partials;
+    const uint4 *Wm;            // as in BatchRoundArgs
+    uint32_t w_stride;
+    uint4 *out;
+    uint32_t slices_log2;
+    int n_combos, K, D;
+    uint32_t fin_bytes;         // LDS layout: finalize scratch | message
+};
+// args as for launch_batch_round (fin_bytes is not read); partials: bs_partials_bytes of the handle's shape
+hipError_t launch_batch_round_slices(BatchRoundArgs args, uint4 *partials, const ComboMeta &meta, const FinMeta &fin, hipStream_t stream);
 // canonical tables (tables[i * n_tables + u]: 2^nv entries, reference layout) -> the work area's round-0 slots
 hipError_t launch_batch_rounds_load(const uint4 *const *tables, uint32_t n, uint32_t n_tables, uint32_t nv, int32_t *work, hipStream_t stream);
 // instances [first, first + count): the tables bound `bound` times -> canonical elements, out[(i - first) * n_tables + u][entry]; with
@@ -376,6 +400,7 @@ enum PolicyKey {
     kPolStagedInit,       // "staged_init"        1: sc_prover_init over HOST tables copies them in chunks and computes round 1 under the copy (shapes of the merged big-round kernel, >= 2^18 entries)
     kPolBatch,            // "batch"              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
     kPolLagSingle,        // "lag_single"         tables that only single-table products name skip this many big rounds after the first (0: off .. 4): class sums stand in for them (lag_index.hpp)
+    kPolBatchSlices,      // "batch_slices"       sc_batch_prover_init: 1 shapes beyond one block's LDS (to 2^16 entries) run their first rounds sliced over several blocks per instance (batch_slices.hpp); 0 they take the serial plan
     kPolCount
 };
 int64_t policy(int key);
@@ -418,6 +443,7 @@ enum Plan {
     kPlanShardedHost,         // ... the caller's host transport
     kPlanShardedP2P,          // ... k_p2p_allreduce
     kPlanShardedGatherTail,   // bind + all-gather + replicated tail
+    kPlanBatchRoundsSlices,   // sc_batch_prove_round: k_batch_round_slices + k_batch_round_fin, several blocks per instance, two launches for a round of the whole batch (the rounds whose tables do not fit one block; policy "batch_slices" = 1)
     kPlanGkrBucketedGrouped,  // GKR initialisation: buckets of an index-ordered list (k_bucket_bounds)
     kPlanGkrBucketedCounted,  // ... counting sort into buckets
     kPlanGkrListForm,         // ... sort + merge + scatter

@@ -123,7 +123,7 @@ static size_t br_lds_bytes(uint32_t nv, uint32_t round, uint32_t n_tables, int K
 }
 
 hipError_t launch_batch_round(BatchRoundArgs args, const ComboMeta &meta, const FinMeta &fin, hipStream_t stream) {
-    if (args.n == 0 || args.round >= args.nv || !batch_shape_fits(args.nv, args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM)) return hipErrorInvalidValue;
+    if (args.n == 0 || args.round >= args.nv || args.nv > 16 || !batch_shape_fits(args.nv - (args.round ? args.round - 1 : 0), args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM)) return hipErrorInvalidValue;
     if (args.n_combos < 1 || args.n_combos > kMetaCombos || !args.work || !args.Wm || !args.out || (args.round && !args.chal)) return hipErrorInvalidValue;
     static bool done[64] = {}; // (more dynamic LDS than the default 64 KB limit of a launch)
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_batch_round<kMaxFusedM>), (int)kBtLdsMax, done); e != hipSuccess) return e;

@@ -454,7 +454,11 @@ class IPForMLSumcheck:
 
     @staticmethod
     def prover_init_batch(polynomials: Sequence[ListOfProductsOfPolynomials]) -> BatchProverState:
-        """n x prover_init (prover.rs:49-69) of ONE structure behind one handle (sc_batch_prover_init); the tables are copied"""
+        """n x prover_init (prover.rs:49-69) of ONE structure behind one handle (sc_batch_prover_init); the tables are copied.
+        Shapes beyond one block's LDS run n ordinary provers inside the handle (plan batch.rounds_serial) -- unless the handle is built under
+        `_lib.policy(batch_slices=1)` (default 0): then, for 1 <= num_vars <= 16, products of at most eight multiplicands and a work area
+        (96 bytes x n x tables x 2^num_vars) of at most 16 GiB, the rounds whose tables do not fit one block give every instance to several
+        blocks (plan batch.rounds_slices: two launches a round) and the later rounds run as within the envelope, with the same bits"""
         descs, keep = _batch_descs(polynomials)
         _sync_device_tables(polynomials, descs)
         h = C.c_void_p()
