@@ -810,6 +810,7 @@ struct GKRRoundSumcheck {
         return out;
     }
     // n x the interactive prover of ONE dim behind one handle (sc_gkr_batch_prover_init): the caller owns the transcript.  Pointers may repeat.
+    // Plans: dim <= 9 runs one block per instance; with policy "batch_slices" = 1 set when the handle is built, dim 10 .. 16 (nnz <= 64 x 2^dim, at most 16 GiB) gives every instance to many blocks (plan batch.gkr_rounds_slices: same bits); other shapes take the serial plan.
     static GKRBatchProverState prover_init_batch(const std::vector<const SparseMultilinearExtension *> &f1s, const std::vector<const DenseMultilinearExtension *> &f2s,
                                                  const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs) {
         const size_t n = f1s.size();

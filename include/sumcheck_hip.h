@@ -389,7 +389,13 @@ SC_API int sc_gkr_prove_batch(uint32_t n, uint32_t dim, sc_rng *const *rngs,
  * starts phase two: two launches back to back], one copy back and one synchronisation, and nothing on the GPU ever waits for the host.
  * The calls are TOTAL over shapes: beyond the envelope, or with policy "batch" = 0 when the handle is built, the handle holds per
  * instance what sc_gkr_prove's path holds [the two dense tables by its route, an ordinary prover per phase, device-side waits off] and
- * a round is a loop of sc_prove_round, with the same bits.  THREADING: as for sc_batch_prover_*. */
+ * a round is a loop of sc_prove_round, with the same bits.
+ * DIM 10 .. 16 [policy "batch_slices" = 1 when the handle is built; default 0; nnz <= 64 x 2^dim; two work areas and the accumulator cells,
+ * 448 B x 2^dim per instance, at most 16 GiB]: plan batch.gkr_rounds_slices keeps the work areas and the per-call sequence; each of the two
+ * initialisations is a memset and two launches that give an instance to many blocks [the terms are added into wide integer cells in device
+ * memory: exact in any order, the same bits], and for dim >= 11 rounds 0 .. dim - 10 of each phase are the two launches of the sliced rounds
+ * above.  Counted once per round call, 2 x dim per proof; state, finish, reset, the shared challenge and every status are unchanged.
+ * THREADING: as for sc_batch_prover_*. */
 typedef struct sc_gkr_batch_prover sc_gkr_batch_prover;   /* n x the two ProverStates of GKRRoundSumcheck::prove (mod.rs:93-139), one dim */
 /* SC_API_GKRB is SC_API: the marker of this family, for the reason SC_API_EXT has one [tests/test_gkr_batch_rounds_host.py compares
  * these prototypes with the shim's declarations]. */
@@ -398,7 +404,9 @@ typedef struct sc_gkr_batch_prover sc_gkr_batch_prover;   /* n x the two ProverS
  * there; g[i] is host memory].  Everything the host can check is checked before any HIP call: errors start with "instance %u: ", the
  * lowest failing instance decides; n == 0 is SC_ERR_BAD_ARG, dim == 0 SC_ERR_CONSTANT_POLY.  An out-of-range index in a device-resident
  * list is found on the device in front of any kernel that follows the indices [SC_ERR_BAD_ARG "instance %u: f1 has an index out of
- * range"].  Every input is COPIED, once per distinct pointer: nothing of the caller's is read after the call returns. */
+ * range"].  Every input is COPIED, once per distinct pointer: nothing of the caller's is read after the call returns.  The plan is chosen
+ * here, from policy "batch", policy "batch_slices", dim and the largest nnz [batch.gkr_rounds_one_block: dim <= 9; batch.gkr_rounds_slices:
+ * dim 10 .. 16 under "batch_slices" = 1; batch.gkr_rounds_serial: everything else], and phase one's tables are built before the call returns. */
 SC_API_GKRB int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
                                          const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags,
                                          sc_gkr_batch_prover **out);
@@ -528,14 +536,16 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *   "wait_spins" (2^22)      bound of a device-side wait for a challenge, in polls (tests shorten it to exercise the give-up path)
  *   "staged_init" (1)        0: sc_prover_init over HOST tables copies them whole before round 1 instead of in chunks with round 1 computed
  *                            under the copy (shapes of the merged big-round kernel from 2^18 entries per table)
- *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, sc_batch_prover_init, sc_gkr_batch_prover_init (plans batch.gkr_rounds_one_block / batch.gkr_rounds_serial): 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
+ *   "batch" (1)              sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, sc_batch_prover_init, sc_gkr_batch_prover_init (plans batch.gkr_rounds_one_block / batch.gkr_rounds_slices / batch.gkr_rounds_serial): 0 always the serial plan; 1 the batched kernel where the shape fits it and n is at or above
  *                            the measured crossover; 2 the batched kernel for every n that fits (tests, A/B runs)
  *   "lag_single" (2)         big rounds that a table named only by single-table products skips after round 1 (0: none .. 4): its products' messages come
  *                            from class sums of the table, and one pass binds the table with every challenge it missed before the next round
  *                            (or anything else) reads it.  The proof does not depend on the value.
- *   "batch_slices" (0)       sc_batch_prover_init: 1 a shape beyond one block's LDS, up to 2^16 entries per table, runs its first rounds sliced over
+ *   "batch_slices" (0)       sc_batch_prover_init, sc_gkr_batch_prover_init: 1 a shape beyond one block's LDS, up to 2^16 entries per table, runs its first rounds sliced over
  *                            several blocks per instance (plan batch.rounds_slices) instead of the serial plan; read when a handle is built; "batch" = 0
- *                            still forces the serial plan.  0 until the sliced plan has been measured.
+ *                            still forces the serial plan.  0 until the sliced plan has been measured.  For sc_gkr_batch_prover_init the key opens
+ *                            dim 10 .. 16 [nnz <= 64 x 2^dim, at most 16 GiB of work areas and cells] to plan batch.gkr_rounds_slices: both
+ *                            initialisations spread over many blocks per instance, the first rounds of each phase sliced (dim >= 11).
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);
 SC_API int sc_get_policy(const char *key, int64_t *value);

@@ -726,6 +726,9 @@ pub struct GkrBatchFinal<F: Limbs4> {
 }
 
 /// n x the prover of `GKRRoundSumcheck::prove` for instances of ONE `dim` behind one handle (`sc_gkr_batch_prover_init`); every input is copied.
+/// `dim <= 9` runs one block per instance; with policy `batch_slices` = 1 (`sc_set_policy`) when the handle is built, `dim` 10 to 16 with at
+/// most 64 x 2^dim non-zeros and 16 GiB gives every instance to many blocks (plan `batch.gkr_rounds_slices`: same bits); other shapes take
+/// the serial plan.
 pub fn gkr_prover_init_batch<F: Limbs4>(instances: &[GkrRoundsInstance<F>]) -> HipGkrBatchProverState<F> {
     let n = instances.len();
     let dim = if n > 0 { instances[0].f2.num_vars } else { 0 };

@@ -292,6 +292,28 @@ __device__ __forceinline__ void bg_build_eq(uint4 *out, uint4 *tmp, const uint4 
     __syncthreads();
 }
 
+// The first half of bg_build_eq alone, for blocks that keep eq(point, .) as its two factors (k_batch_gkr_terms, dim up to 16: the outer
+// product would not fit LDS): lo[2^kl] over the low kl = ceil(dim / 2) variables, hi[2^kh] over the rest, so that
+// eq(point, b) = lo[b & (2^kl - 1)] * hi[b >> kl] (hi[0] = 1 when kh = 0).  Lanes 0 .. 127 double lo, lanes 128 .. 255 hi: up to 2^7
+// entries a step, kl <= 8.  Ends behind a barrier.
+__device__ __forceinline__ void bg_build_eq_halves(uint4 *lo, uint4 *hi, const uint4 *point, const uint32_t dim) {
+    const uint32_t tid = threadIdx.x, kl = (dim + 1) / 2, kh = dim - kl;
+    static_assert(kTsBlock == 256, "two halves of 128 lanes");
+    if (tid == 0) fr_store(lo, fr_one());
+    if (tid == 128) fr_store(hi, fr_one());
+    __syncthreads();
+    for (uint32_t i = 0; i < kl; ++i) {
+        const uint32_t w = tid >> 7, t = tid & 127u;
+        if (t < (1u << i) && (w == 0 || i < kh)) {
+            uint4 *tab = w == 0 ? lo : hi;
+            const Fr a = fr_load(tab + 2 * t), m = fr_mul(a, fr_load(point + 2 * (w == 0 ? i : kl + i)));
+            fr_store(tab + 2 * (t + (1u << i)), m);
+            fr_store(tab + 2 * t, fr_sub(a, m));
+        }
+        __syncthreads();
+    }
+}
+
 // A GKR phase's table from the instance's non-zeros (k_batch_gkr, k_batch_gkr_phase).  kPhase 1: cell x, term eq(g,z) * v * f3[y];
 // kPhase 2: cell y, term eq(g,z) * eq(u,x) * v.  The cells (eight uint64 lanes of 32-bit limbs each, lane-major: cell[j << dim | c],
 // neighbouring cells in neighbouring banks) are zeroed, filled with LDS atomic adds (exact in any order) and folded mod p; store(c, value)

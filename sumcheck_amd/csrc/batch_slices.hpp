@@ -105,4 +105,36 @@ SC_BS_FN int bs_plan(uint64_t n, uint32_t nv, uint32_t U, int K, int D, uint32_t
     return kBrSlices;
 }
 
+// ---- the plan of a GKR batch handle (sc_gkr_batch_prover_init) ----
+// Both phases are one product of two tables (U = 2, K = 1, D = 3, max_mult = 2).  Up to kBsGkrMaxDim the two initialisations run in one
+// block per instance (k_batch_gkr_phase); beyond it, with policy "batch_slices" = 1, k_batch_gkr_terms / k_batch_gkr_fold
+// (kernels_batch_gkr_round_slices.hip) give an instance to many blocks through wide cells in device memory, and the rounds are the sliced
+// ones above.  (kernels.h keeps the two constants as kGkrBatchMaxDim / kGkrBatchMaxNnzPerCell.)
+constexpr uint32_t kBsGkrMaxDim = 9;
+constexpr uint64_t kBsGkrMaxNnzPerCell = 64;
+constexpr uint64_t kBsGkrCellBytes = 64;          // eight uint64 lanes per cell
+constexpr uint64_t kBsGkrTermsPerBlock = 8 * (uint64_t)kBsBlock; // non-zeros a block of k_batch_gkr_terms takes: eight per lane behind its two eq half tables
+constexpr uint64_t kBsGkrMaxTermBlocks = 2048;    // ... blocks per instance at the most: beyond that a block grid-strides (64 x 2^16 / 2048 = 2048 per block, the same eight per lane)
+enum GkrBatchRoundsPlan { kGbrSerial = 0, kGbrOneBlock = 1, kGbrSlices = 2 };
+// blocks per instance of k_batch_gkr_terms, from the batch's largest list; an empty batch still gets one (it builds its eq tables and adds nothing)
+SC_BS_FN uint64_t gkr_bs_term_blocks(uint64_t nnz_max) {
+    const uint64_t b = (nnz_max + kBsGkrTermsPerBlock - 1) / kBsGkrTermsPerBlock;
+    return b < 1 ? 1 : (b > kBsGkrMaxTermBlocks ? kBsGkrMaxTermBlocks : b);
+}
+// the handle's device memory that grows with the shape: areas A and B and the cells both phases share
+SC_BS_FN uint64_t gkr_bs_handle_bytes(uint64_t n, uint32_t dim) { return 2 * bs_work_bytes(n, 2, dim) + ((n * kBsGkrCellBytes) << dim); }
+SC_BS_FN int gkr_bs_plan(uint64_t n, uint32_t dim, uint64_t nnz_max, int n_combos, int64_t pol_batch, int64_t pol_slices) {
+    if (pol_batch == 0 || n == 0 || dim == 0 || dim > kBsMaxNv) return kGbrSerial;
+    if (nnz_max > (kBsGkrMaxNnzPerCell << dim)) return kGbrSerial;
+    if (dim <= kBsGkrMaxDim) return kGbrOneBlock;
+    if (pol_slices != 1 || !bs_envelope(dim, 2, 1, 3, 2)) return kGbrSerial;
+    if (n > (1ULL << 32) || gkr_bs_handle_bytes(n, dim) > kBsMaxWorkBytes) return kGbrSerial;
+    // the grids: a sliced round's, the terms kernel's, the fold kernel's (one lane per cell)
+    if (bs_round_sliced(dim, 0, 2, 1, 3, 2) && (n << bs_slices_log2(dim, 2, 1, 3)) >= (1ULL << 31)) return kGbrSerial;
+    if (n * gkr_bs_term_blocks(nnz_max) >= (1ULL << 31) || ((n << dim) + kBsBlock - 1) / kBsBlock >= (1ULL << 31)) return kGbrSerial;
+    for (uint32_t j = 0; j < dim && bs_round_sliced(dim, j, 2, 1, 3, 2); ++j)
+        if (!bs_lane_sums_hold(bs_slice_log2(bs_loaded_log2(dim, j), 2, 1, 3), j, n_combos)) return kGbrSerial;
+    return kGbrSlices;
+}
+
 } // namespace scd

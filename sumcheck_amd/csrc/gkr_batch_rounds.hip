@@ -2,33 +2,43 @@
 // src/gkr_round_sumcheck/mod.rs:93-139) of one dim behind ONE handle, a round of all n instances per call, under the caller's transcript.
 // What batch_rounds.hip is to sc_ml_prove_batch, this is to sc_gkr_prove_batch: the caller hands in every challenge (one per instance, or
 // one shared by all), so a round is launched after its challenges are known and nothing on the GPU ever waits for the host.  A proof is
-// 2 x dim round calls -- phase one's dim messages, then phase two's -- and sc_gkr_batch_prover_finish.  Two plans, chosen when the handle
-// is built, same bits:
+// 2 x dim round calls -- phase one's dim messages, then phase two's -- and sc_gkr_batch_prover_finish.  Three plans, chosen when the handle
+// is built (batch_slices.hpp: gkr_bs_plan), same bits:
 //   batch.gkr_rounds_one_block  two work areas of k_batch_round's layout (U = 2): A for phase one, B for phase two.  k_batch_gkr_phase<1>
 //                               (kernels_batch_gkr_rounds.hip) fills A's depth 0 once, at init -- it is never written again, so a reset
 //                               rewinds counters --; round call dim launches k_batch_gkr_phase<2> in front of its k_batch_round, which
 //                               binds what is left of f2 with u_{dim-1} and fills B from the challenges the handle has kept on the
 //                               device.  Per round call: one upload of the challenges, one launch (call dim: two, back to back), one copy
 //                               back, one synchronisation;
+//   batch.gkr_rounds_slices     policy "batch_slices" = 1, dim 10 .. 16, nnz <= 64 x 2^dim, at most 16 GiB: the same two work areas and
+//                               per-round sequence, but the areas are filled by k_batch_gkr_terms + k_batch_gkr_fold
+//                               (kernels_batch_gkr_round_slices.hip: many blocks per instance, wide cells in device memory, zeroed in
+//                               front of each phase) and the rounds whose tables as loaded do not fit one block run as
+//                               k_batch_round_slices + k_batch_round_fin (dim >= 11: rounds 0 .. dim - 10 of each phase);
 //   batch.gkr_rounds_serial     per instance the two dense tables by the route sc_gkr_prove takes (sc_internal_gkr_dense_table) and an
 //                               ordinary sc_prover per phase (device-side waits off, no resident kernel); a round is a loop of
-//                               sc_prove_round, the phase change and finish go through sc_prover_bind_final: dim > 9, nnz beyond
-//                               64 x 2^dim, policy "batch" = 0.
+//                               sc_prove_round, the phase change and finish go through sc_prover_bind_final: dim > 9 without the key,
+//                               dim > 16, nnz beyond 64 x 2^dim, policy "batch" = 0.
 // The handle copies every input once per distinct pointer (phase two needs f1 and f3 again): nothing of the caller's is read after init.
+#include "batch_slices.hpp"
 #include "prover_internal.hpp"
 
 struct sc_gkr_batch_prover {
     int device = 0;
     uint32_t n = 0, dim = 0, round = 0; // round: round calls answered so far, 0 .. 2 dim
     bool exhausted = false;
-    bool one_block = false;
+    int plan = scd::kGbrSerial; // scd::GkrBatchRoundsPlan; kGbrOneBlock and kGbrSlices share the work areas and everything that reads them
+    bool work_areas() const { return plan != scd::kGbrSerial; }
+    uint64_t nnz_max = 0;
     std::vector<std::vector<sch::Fr>> randomness; // per challenge received (u, then v): n elements, or ONE for a shared challenge
     std::vector<uint64_t> nnz;
     std::vector<sch::Fr> g;                        // n x dim
     std::vector<scd::GkrBatchInst> rec;            // the instances' arrays in the handle's copy (d_in), g in d_up
     hipStream_t stream = nullptr;
-    char *d_buf = nullptr; // device, ONE allocation: area A | area B (one block) | matrices | records | index flags | g | challenges | messages | f2(u) | export area | inputs | serial tables
+    char *d_buf = nullptr; // device, ONE allocation: area A | area B (work areas) | matrices | records | index flags | g | challenges | messages | f2(u) | export area | inputs | serial tables, or (slices) cells | partials
     char *d_in = nullptr;  // (inside d_buf) the inputs, every distinct array once
+    char *d_cells = nullptr, *d_part = nullptr; // (inside d_buf, slices) the wide cells both phases share, n x 64 B x 2^dim; the sliced rounds' partials
+    size_t cells_bytes = 0;
     char *h_pin = nullptr; // pinned: matrices | ... | export area
     size_t work_bytes = 0, w_off = 0, rec_off = 0, flag_off = 0, g_off = 0, u_off = 0, msg_off = 0, f2u_off = 0, exp_off = 0, pin_bytes = 0; // (offsets into h_pin; d_buf: + 2 work_bytes)
     SharedMeta s; // one product of two tables with a coefficient of one: both phases (start_phase{1,2}_sumcheck, mod.rs:45-54, 66-82)
@@ -138,6 +148,24 @@ int serial_phase_two(sc_gkr_batch_prover *bp, uint32_t i, const std::vector<sch:
     return serial_prover(bp, &bp->p2[i], serial_table(bp, i, 1), serial_table(bp, i, 2));
 }
 
+// the sliced plan's initialisation of a phase: the cells zeroed, k_batch_gkr_terms, k_batch_gkr_fold -- all on the handle's stream
+int slices_phase(sc_gkr_batch_prover *bp, int phase) {
+    char *d_up = bp->d_buf + 2 * bp->work_bytes;
+    HIP_TRY(hipMemsetAsync(bp->d_cells, 0, bp->cells_bytes, bp->stream));
+    scd::BatchGkrSlicesArgs P;
+    std::memset(&P, 0, sizeof(P));
+    P.inst = reinterpret_cast<const scd::GkrBatchInst *>(d_up + bp->rec_off);
+    P.work_a = reinterpret_cast<int32_t *>(bp->d_buf);
+    P.work_b = reinterpret_cast<int32_t *>(bp->d_buf + bp->work_bytes);
+    P.u = reinterpret_cast<const uint4 *>(d_up + bp->u_off);
+    P.f2u = reinterpret_cast<uint4 *>(d_up + bp->f2u_off);
+    P.cells = reinterpret_cast<uint64_t *>(bp->d_cells);
+    P.n = bp->n;
+    P.dim = bp->dim;
+    HIP_TRY(scd::launch_batch_gkr_slices_phase(phase, P, bp->nnz_max, bp->stream));
+    return SC_OK;
+}
+
 } // namespace
 
 extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2,
@@ -164,12 +192,16 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
     bp->nnz.assign(nnz, nnz + n);
     bp->g.resize((size_t)n * dim);
     for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g[(size_t)i * dim], g[i], (size_t)dim * 32);
-    bp->one_block = scd::policy(scd::kPolBatch) != 0 && scd::gkr_batch_shape_fits(dim, nnz_max);
+    bp->nnz_max = nnz_max;
     const size_t N = (size_t)1 << dim;
     auto build = [&]() -> int {
         PhaseDesc pd(dim, 0);
         build_shared(&pd.d, bp->s);
         bp->s.unit.push_back(unit_matrix(2, 3));
+        bp->plan = scd::gkr_bs_plan(n, dim, nnz_max, bp->s.n_combos, scd::policy(scd::kPolBatch), scd::policy(scd::kPolBatchSlices));
+        // (batch_slices.hpp spells the envelopes out for the host tests: the launchers are guarded by the kernels' own)
+        if (bp->plan != scd::kGbrSerial && scd::gkr_batch_shape_fits(dim, nnz_max) != (bp->plan == scd::kGbrOneBlock)) bp->plan = scd::kGbrSerial;
+        const bool areas = bp->work_areas(), slices = bp->plan == scd::kGbrSlices;
         // ---- the handle's copy of the inputs: every distinct (pointer, size) once ----
         std::map<std::pair<const void *, size_t>, size_t> where;
         std::vector<std::pair<const void *, size_t>> items;
@@ -190,7 +222,7 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             offs[4 * (size_t)i + 2] = add(f2[i], N * 32);
             offs[4 * (size_t)i + 3] = add(f3[i], N * 32);
         }
-        bp->work_bytes = bp->one_block ? up256((size_t)n * 2 * 2 * (scd::kBatchRoundSlotBytes << dim)) : 0;
+        bp->work_bytes = areas ? up256((size_t)n * 2 * 2 * (scd::kBatchRoundSlotBytes << dim)) : 0;
         bp->w_off = 0;
         bp->rec_off = bp->w_off + up256((size_t)bp->s.w_elems * 32);
         bp->flag_off = bp->rec_off + up256((size_t)n * sizeof(scd::GkrBatchInst));
@@ -204,12 +236,18 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             DeviceGate gate_(bp->device);
             HIP_TRY(hipSetDevice(bp->device));
             HIP_TRY(hipStreamCreateWithFlags(&bp->stream, hipStreamNonBlocking));
-            const size_t tabs_bytes = bp->one_block ? 0 : (size_t)n * 3 * N * 32, fin_bytes = bp->one_block ? 0 : up256((size_t)n * 64);
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), 2 * bp->work_bytes + bp->pin_bytes + in_bytes + tabs_bytes + fin_bytes)); // (one allocation: a handle's life is short)
+            const size_t tabs_bytes = areas ? 0 : (size_t)n * 3 * N * 32, fin_bytes = areas ? 0 : up256((size_t)n * 64);
+            bp->cells_bytes = slices ? (size_t)n * scd::kBsGkrCellBytes * N : 0;
+            const size_t part_bytes = slices ? up256((size_t)scd::bs_partials_bytes(n, dim, 2, 1, 3, bp->s.n_combos)) : 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), 2 * bp->work_bytes + bp->pin_bytes + in_bytes + tabs_bytes + fin_bytes + bp->cells_bytes + part_bytes)); // (one allocation: a handle's life is short)
             bp->d_in = bp->d_buf + 2 * bp->work_bytes + bp->pin_bytes;
-            if (!bp->one_block) {
+            if (!areas) {
                 bp->d_tabs = bp->d_in + in_bytes;
                 bp->d_fin = bp->d_tabs + tabs_bytes;
+            }
+            if (slices) {
+                bp->d_cells = bp->d_in + in_bytes;
+                bp->d_part = bp->d_cells + bp->cells_bytes;
             }
             HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bp->h_pin), bp->pin_bytes, hipHostMallocDefault));
             if (dev_in) HIP_TRY(hipDeviceSynchronize()); // the inputs' producers are waited for, as a copy on their stream would
@@ -238,7 +276,9 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             // device-resident lists: an index out of range is found here, in front of any kernel that follows the indices (host lists: checked above)
             if (dev_in)
                 if (int rc = gkr_check_idx_on_device(d_rec, n, dim, bp->h_pin, d_up, bp->flag_off, bp->stream)) return rc;
-            if (bp->one_block) {
+            if (slices) {
+                if (int rc = slices_phase(bp, 1)) return rc;
+            } else if (areas) {
                 scd::BatchGkrPhaseArgs A;
                 std::memset(&A, 0, sizeof(A));
                 A.inst = d_rec;
@@ -249,7 +289,7 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             }
             HIP_TRY(hipStreamSynchronize(bp->stream)); // nothing of the caller's is read after the call returns
         }
-        if (bp->one_block) return SC_OK;
+        if (areas) return SC_OK;
         bp->p1.assign(n, nullptr);
         bp->p2.assign(n, nullptr);
         bp->f2u.resize(n);
@@ -283,14 +323,17 @@ extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t 
     if (r_or_null)
         if (int rc = take_challenges(bp, r_or_null, r_shared, chal)) return rc;
     const uint32_t n = bp->n, dim = bp->dim, t = bp->round, phase = t / dim, r = t % dim;
-    if (bp->one_block) {
+    if (bp->work_areas()) {
         const SharedMeta &s = bp->s;
+        const bool slices = bp->plan == scd::kGbrSlices;
         DeviceGate gate_(bp->device);
         HIP_TRY(hipSetDevice(bp->device));
         char *d_up = bp->d_buf + 2 * bp->work_bytes;
         if (r_or_null)
             if (int rc = upload_challenge(bp, t - 1, chal)) return rc;
-        if (t == dim) { // the phase change: f2(u), f1(g, u, .), f2(u) f3 -> area B
+        if (t == dim && slices) { // the phase change: f2(u), f1(g, u, .), f2(u) f3 -> area B
+            if (int rc = slices_phase(bp, 2)) return rc;
+        } else if (t == dim) {
             scd::BatchGkrPhaseArgs P;
             std::memset(&P, 0, sizeof(P));
             P.inst = reinterpret_cast<const scd::GkrBatchInst *>(d_up + bp->rec_off);
@@ -317,8 +360,9 @@ extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t 
         A.n_combos = s.n_combos;
         A.K = 1;
         A.D = 3;
-        HIP_TRY(scd::launch_batch_round(A, s.combo, s.fin, bp->stream));
-        scd::plan_hit(scd::kPlanBatchGkrRoundsOneBlock);
+        if (slices && scd::bs_round_sliced(dim, r, 2, 1, 3, 2)) HIP_TRY(scd::launch_batch_round_slices(A, reinterpret_cast<uint4 *>(bp->d_part), s.combo, s.fin, bp->stream));
+        else HIP_TRY(scd::launch_batch_round(A, s.combo, s.fin, bp->stream));
+        scd::plan_hit(slices ? scd::kPlanBatchGkrRoundsSlices : scd::kPlanBatchGkrRoundsOneBlock);
         HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->msg_off, d_up + bp->msg_off, (size_t)n * 96, hipMemcpyDeviceToHost, bp->stream));
         HIP_TRY(hipStreamSynchronize(bp->stream));
         std::memcpy(out_evals, bp->h_pin + bp->msg_off, (size_t)n * 96);
@@ -346,7 +390,7 @@ extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_
     if (int rc = take_challenges(bp, r, r_shared, chal)) return rc;
     const uint32_t n = bp->n, dim = bp->dim;
     std::vector<sch::Fr> fin((size_t)n * 3); // f1(g,u,v), f2(u), f2(u) f3(v)
-    if (bp->one_block) {
+    if (bp->work_areas()) {
         DeviceGate gate_(bp->device);
         HIP_TRY(hipSetDevice(bp->device));
         char *d_up = bp->d_buf + 2 * bp->work_bytes;
@@ -406,7 +450,7 @@ extern "C" int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t insta
     if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "tables were consumed by sc_gkr_batch_prover_finish");
     // the current phase's two tables: phase one's until round call dim has built phase two's; bound = the phase's max(round - 1, 0)
     const uint32_t dim = bp->dim, phase = bp->round > dim ? 1u : 0u, pr = bp->round - phase * dim, bound = pr > 0 ? pr - 1 : 0;
-    if (!bp->one_block) return sc_prover_state(phase ? bp->p2[instance] : bp->p1[instance], nullptr, nullptr, tables_out, nullptr);
+    if (!bp->work_areas()) return sc_prover_state(phase ? bp->p2[instance] : bp->p1[instance], nullptr, nullptr, tables_out, nullptr);
     const size_t bytes = (size_t)2 * ((size_t)32 << (dim - bound));
     DeviceGate gate_(bp->device);
     HIP_TRY(hipSetDevice(bp->device));
@@ -421,10 +465,10 @@ extern "C" int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t insta
 
 extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
-    if (!bp->one_block)
+    if (!bp->work_areas())
         for (uint32_t i = 0; i < bp->n; ++i) // phase one's provers borrow the handle's own tables: rewound in place (phase two's are rewound over new tables at the phase change)
             if (int rc = sc_prover_reset(bp->p1[i], nullptr, SC_TABLES_ON_DEVICE)) return prefix(rc, i);
-    // (one block: area A's depth 0 was never overwritten)
+    // (work areas: area A's depth 0 was never overwritten)
     bp->round = 0;
     bp->exhausted = false;
     bp->randomness.clear();

@@ -381,6 +381,24 @@ struct BatchGkrPhaseArgs {
     uint32_t n, dim;
 };
 hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream);
+// The same two initialisations beyond one block's LDS (kernels_batch_gkr_round_slices.hip; the envelope and the grids: batch_slices.hpp,
+// gkr_bs_plan), dim 10 .. 16, as two plain launches each over wide cells in DEVICE memory (n x 8 uint64 lanes x 2^dim, zeroed by the caller
+// on the same stream in front of every phase):
+//   k_batch_gkr_terms<kPhase>  n x blocks_per_inst blocks; a block builds eq(g, .) (phase 2: and eq(u, .)) as two half tables in LDS, strides
+//                              over its share of the instance's non-zeros and adds every term's eight limbs into the cell's lanes with
+//                              relaxed agent-scope atomics: integer sums, exact in any order;
+//   k_batch_gkr_fold<kPhase>   one lane per cell: wide_fold_cell -> table 0, depth 0 of area A (phase 1) or B (phase 2); table 1 gets f2,
+//                              or f3 * f2(u) with f2(u) bound out of area A as k_batch_gkr_phase<2> binds it (kept in f2u[i]).
+struct BatchGkrSlicesArgs {
+    const GkrBatchInst *inst;   // device, n records
+    int32_t *work_a, *work_b;   // as in BatchGkrPhaseArgs
+    const uint4 *u;             // as in BatchGkrPhaseArgs
+    uint4 *f2u;                 // device: n elements (phase 2 writes)
+    uint64_t *cells;            // device: n x 8 x 2^dim lanes, zero on entry
+    uint32_t n, dim;
+    uint32_t blocks_per_inst;   // (filled in by the launcher from nnz_max: gkr_bs_term_blocks)
+};
+hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -400,7 +418,7 @@ enum PolicyKey {
     kPolStagedInit,       // "staged_init"        1: sc_prover_init over HOST tables copies them in chunks and computes round 1 under the copy (shapes of the merged big-round kernel, >= 2^18 entries)
     kPolBatch,            // "batch"              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
     kPolLagSingle,        // "lag_single"         tables that only single-table products name skip this many big rounds after the first (0: off .. 4): class sums stand in for them (lag_index.hpp)
-    kPolBatchSlices,      // "batch_slices"       sc_batch_prover_init: 1 shapes beyond one block's LDS (to 2^16 entries) run their first rounds sliced over several blocks per instance (batch_slices.hpp); 0 they take the serial plan
+    kPolBatchSlices,      // "batch_slices"       sc_batch_prover_init, sc_gkr_batch_prover_init (dim 10 .. 16): 1 shapes beyond one block's LDS (to 2^16 entries) run their first rounds sliced over several blocks per instance (batch_slices.hpp); 0 they take the serial plan
     kPolCount
 };
 int64_t policy(int key);
@@ -446,6 +464,7 @@ enum Plan {
     kPlanBatchRoundsSlices,   // sc_batch_prove_round: k_batch_round_slices + k_batch_round_fin, several blocks per instance, two launches for a round of the whole batch (the rounds whose tables do not fit one block; policy "batch_slices" = 1)
     kPlanGkrBucketedGrouped,  // GKR initialisation: buckets of an index-ordered list (k_bucket_bounds)
     kPlanGkrBucketedCounted,  // ... counting sort into buckets
+    kPlanBatchGkrRoundsSlices, // sc_gkr_batch_prove_round on a handle of dim 10 .. 16 built with policy "batch_slices" = 1: areas filled by k_batch_gkr_terms / k_batch_gkr_fold, the rounds k_batch_round_slices + k_batch_round_fin while the tables do not fit one block, then k_batch_round; counted once per round call
     kPlanGkrListForm,         // ... sort + merge + scatter
     kPlanGkrEqDirect,         // ... the list form's fold with eq evaluated per entry (k_sparse_scale_direct: 2^k > 8 n + 1024, no eq table)
     kPlanGkrCoeffFromBound,   // phase two's coefficient f2(u) from phase one's bound table

@@ -318,7 +318,10 @@ class GKRRoundSumcheck:
                           f3s: Sequence[DenseMultilinearExtension], gs) -> "GKRBatchProverState":
         """n x the two prover states of GKRRoundSumcheck.prove of one dim behind one handle (sc_gkr_batch_prover_init): the interactive
         rounds under the CALLER's transcript -- 2 dim calls of prove_round, then finish.  Inputs as for prove_batch (all on the host or
-        all on the GPU; the same object may stand for several instances); they are copied: nothing is read after this returns."""
+        all on the GPU; the same object may stand for several instances); they are copied: nothing is read after this returns.
+        Plans: dim <= 9 runs one block per instance; under _lib.policy(batch_slices=1), set when the handle is built, dim 10 .. 16
+        (nnz <= 64 x 2^dim, at most 16 GiB) gives every instance to many blocks (plan batch.gkr_rounds_slices: same bits); other
+        shapes take the serial plan."""
         n = len(f1s)
         assert len(f2s) == n and len(f3s) == n and len(gs) == n, "one f1, f2, f3 and g per instance"
         dim = f2s[0].num_vars if n else 0
