@@ -113,12 +113,6 @@ struct AreaLease {
         g_area.mu.unlock();
     }
 };
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-// the error a step on instance i has just left, behind "instance i: "
-int prefix_instance(int rc, uint32_t i) {
-    const std::string why = sc_last_error();
-    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-}
 // the area on the calling thread's device, with its stream (the caller holds the lease and the device gate)
 int area_open(BatchArea &a, int dev) {
     HIP_TRY(hipSetDevice(dev));
@@ -154,6 +148,45 @@ int area_reserve(BatchArea &a, size_t d_bytes, size_t up_bytes) {
 }
 
 } // namespace
+
+// ---- what the entry points here and the two batch handles share (prover_internal.hpp) ----
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+int prefix_instance(int rc, uint32_t i) {
+    const std::string why = sc_last_error();
+    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+}
+const sch::Fr &challenge_of(const std::vector<sch::Fr> &c, uint32_t i) { return c.size() == 1 ? c[0] : c[i]; }
+int take_challenges(uint32_t n, const uint64_t *r, uint32_t r_shared, std::vector<sch::Fr> &out) {
+    out.resize(r_shared ? 1 : n);
+    std::memcpy(out.data(), r, out.size() * 32);
+    for (size_t i = 0; i < out.size(); ++i)
+        if (sch::geq_p(out[i])) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: challenge is not canonical", (uint32_t)i);
+    return SC_OK;
+}
+int serial_bind_final(sc_prover *p, int device, const uint64_t *r, char *d_fin, uint32_t first, uint32_t count, void *h_out) {
+    if (int rc = sc_prover_bind_final(p, r, reinterpret_cast<uint64_t *>(d_fin))) return rc;
+    DeviceGate gate_(device);
+    hipError_t e = hipMemcpyAsync(h_out, d_fin + (size_t)first * 32, (size_t)count * 32, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e == hipSuccess) return SC_OK;
+    (void)hipGetLastError();
+    return sc_internal_fail(SC_ERR_HIP, "copying the final table values failed: %s", hipGetErrorString(e));
+}
+void batch_state_head(const std::vector<std::vector<sch::Fr>> &rand, uint32_t instance, uint32_t round_now, uint64_t *randomness, uint32_t *n_randomness, uint32_t *round) {
+    if (randomness)
+        for (size_t j = 0; j < rand.size(); ++j) std::memcpy(randomness + 4 * j, &challenge_of(rand[j], instance), 32);
+    if (n_randomness) *n_randomness = (uint32_t)rand.size();
+    if (round) *round = round_now;
+}
+int batch_export_out(const int32_t *work, uint32_t first, uint32_t count, uint32_t n_tables, uint32_t nv, uint32_t bound, const uint4 *d_chal_or_null, uint32_t chal_shared, char *d_exp,
+                     char *h_exp, void *out, hipStream_t stream) {
+    HIP_TRY(scd::launch_batch_rounds_export(work, first, count, n_tables, nv, bound, d_chal_or_null, chal_shared, reinterpret_cast<uint4 *>(d_exp), stream));
+    const size_t bytes = (size_t)count * n_tables * ((size_t)32 << (nv - bound - (d_chal_or_null ? 1u : 0u))); // (the launcher has refused a depth beyond nv)
+    HIP_TRY(hipMemcpyAsync(h_exp, d_exp, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(out, h_exp, bytes);
+    return SC_OK;
+}
 
 // (the structure every instance shares: SharedMeta, prover_internal.hpp -- also what batch_rounds.hip builds its launches from)
 void build_shared(const sc_poly_desc *d, SharedMeta &s) {
@@ -668,27 +701,6 @@ uint32_t gkr_batch_min_n(uint32_t dim) {
     return 1;
 }
 
-struct StageMap { // host arrays behind one another in the image, every distinct (pointer, size) once
-    struct Item {
-        const void *src;
-        size_t bytes, off;
-    };
-    std::vector<Item> items;
-    std::map<std::pair<const void *, size_t>, size_t> where;
-    size_t base = 0, bytes = 0;
-    size_t add(const void *src, size_t n_bytes) { // -> offset of the array's copy in the image
-        auto it = where.find({src, n_bytes});
-        if (it != where.end()) return it->second;
-        const size_t off = base + bytes;
-        items.push_back({src, n_bytes, off});
-        where.emplace(std::make_pair(src, n_bytes), off);
-        bytes += round_up(n_bytes, 32);
-        return off;
-    }
-    void copy_into(char *h_up) const {
-        for (const Item &it : items) std::memcpy(h_up + it.off, it.src, it.bytes);
-    }
-};
 int check_canonical(const uint64_t *elems, uint32_t n_elems, uint32_t i, const char *what) {
     for (uint32_t k = 0; k < n_elems; ++k) {
         sch::Fr e;

@@ -15,9 +15,7 @@
 
 namespace scd {
 
-// an element in LDS: nine limbs in a 48-byte, 16-byte aligned slot (three ds_read_b128 / ds_write_b128 instead of nine 32-bit accesses)
-constexpr int kBtEnt = 12;               // dwords per entry
-constexpr size_t kBtLdsMax = 144 * 1024; // a launch's dynamic LDS: of the CU's 160 KB (k_tail_slices: one block per CU; its static LDS is ~3 KB)
+// an element in LDS: nine limbs in a 48-byte, 16-byte aligned slot of kBtEnt dwords (batch_shape.hpp, with kBtLdsMax, a launch's dynamic LDS)
 __device__ __forceinline__ Fe bt_lds_load(const int32_t *t) {
     const int4 a = *reinterpret_cast<const int4 *>(t), b = *reinterpret_cast<const int4 *>(t + 4), c = *reinterpret_cast<const int4 *>(t + 8);
     Fe r;
@@ -31,7 +29,7 @@ __device__ __forceinline__ void bt_lds_store(int32_t *t, const Fe &v) {
     *reinterpret_cast<int4 *>(t + 4) = make_int4(v.l[4], v.l[5], v.l[6], v.l[7]);
     t[8] = v.l[8];
 }
-// a slot of a batch work area (global memory, kernels.h: batch_rounds_off): the LDS slot verbatim, three 16-byte words, the last one's upper lanes zero
+// a slot of a batch work area (global memory, batch_shape.hpp: batch_rounds_off): the LDS slot verbatim, three 16-byte words, the last one's upper lanes zero
 __device__ __forceinline__ Fe br_slot_load(const int32_t *t) { return bt_lds_load(t); }
 __device__ __forceinline__ void br_slot_store(int32_t *t, const Fe &v) {
     *reinterpret_cast<int4 *>(t) = make_int4(v.l[0], v.l[1], v.l[2], v.l[3]);
@@ -343,7 +341,6 @@ __device__ __forceinline__ void bg_accumulate(uint64_t *cell, const GkrBatchInst
     __syncthreads();
 }
 
-// finalize scratch | message: the head of a batched kernel's dynamic LDS
-inline size_t bt_fin_bytes(int K, int D) { return (((size_t)K * D * (D + 2) * 32 + 15) & ~(size_t)15) + (size_t)D * 32; }
+// (bt_fin_bytes, the head of a batched kernel's dynamic LDS -- finalize scratch | message: batch_shape.hpp)
 
 } // namespace scd

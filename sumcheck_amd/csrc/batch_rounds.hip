@@ -40,10 +40,6 @@ struct sc_batch_prover {
 
 namespace {
 
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-const sch::Fr &challenge_of(const std::vector<sch::Fr> &c, uint32_t i) { return c.size() == 1 ? c[0] : c[i]; }
-
 void batch_prover_destroy(sc_batch_prover *bp) {
     if (!bp) return;
     for (sc_prover *p : bp->provers)
@@ -141,20 +137,8 @@ int load_serial(sc_batch_prover *bp, const sc_poly_desc *descs) {
             rc = sc_prover_init(&eff, &bp->provers[i]);
             if (rc == SC_OK) rc = sc_prover_set_resident(bp->provers[i], 0);
         }
-        if (rc) {
-            const std::string why = sc_last_error();
-            return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-        }
+        if (rc) return prefix_instance(rc, i);
     }
-    return SC_OK;
-}
-
-// the challenges of a call: null / canonical checks (no HIP call), then as the handle records them
-int take_challenges(const sc_batch_prover *bp, const uint64_t *r, uint32_t r_shared, std::vector<sch::Fr> &out) {
-    out.resize(r_shared ? 1 : bp->n);
-    std::memcpy(out.data(), r, out.size() * 32);
-    for (size_t i = 0; i < out.size(); ++i)
-        if (sch::geq_p(out[i])) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: challenge is not canonical", (uint32_t)i);
     return SC_OK;
 }
 
@@ -185,8 +169,6 @@ extern "C" int sc_batch_prover_init(const sc_poly_desc *descs, uint32_t n, sc_ba
         build_shared(&d0, bp->s);
         const SharedMeta &s = bp->s;
         bp->plan = scd::bs_plan(n, s.nv, s.U, (int)s.K, (int)s.D, s.max_mult, s.n_combos, s.fits_args, scd::policy(scd::kPolBatch), scd::policy(scd::kPolBatchSlices));
-        // (batch_slices.hpp spells batch_shape_fits out for the host tests: the launchers are guarded by the kernels' own)
-        if (bp->plan != scd::kBrSerial && scd::batch_shape_fits(s.nv, s.U, (int)s.K, (int)s.D, s.max_mult) != (bp->plan == scd::kBrOneBlock)) bp->plan = scd::kBrSerial;
     }
     const size_t table_bytes = (size_t)32 << bp->nv;
     auto build = [&]() -> int {
@@ -207,16 +189,16 @@ extern "C" int sc_batch_prover_init(const sc_poly_desc *descs, uint32_t n, sc_ba
         SharedMeta &s = bp->s;
         for (uint32_t k = 0; k < s.K; ++k) s.unit.push_back(unit_matrix(s.M[k], s.D));
         const bool host_tables = !(d0.flags & SC_TABLES_ON_DEVICE);
-        bp->work_bytes = up256((size_t)n * bp->U * 2 * (scd::kBatchRoundSlotBytes << bp->nv));
+        bp->work_bytes = round_up((size_t)n * bp->U * 2 * (scd::kBatchRoundSlotBytes << bp->nv), 256);
         bp->exp_bytes = std::max((size_t)bp->U * table_bytes, (size_t)n * bp->U * 32); // one instance's tables (state), or every instance's final values
         bp->w_off = 0;
-        bp->ptr_off = bp->w_off + up256((size_t)n * s.w_elems * 32);
-        bp->chal_off = bp->ptr_off + up256((size_t)n * bp->U * sizeof(void *));
-        bp->msg_off = bp->chal_off + up256((size_t)n * 32);
-        bp->exp_off = bp->msg_off + up256((size_t)n * bp->D * 32);
-        bp->stage_off = bp->exp_off + up256(bp->exp_bytes);
+        bp->ptr_off = bp->w_off + round_up((size_t)n * s.w_elems * 32, 256);
+        bp->chal_off = bp->ptr_off + round_up((size_t)n * bp->U * sizeof(void *), 256);
+        bp->msg_off = bp->chal_off + round_up((size_t)n * 32, 256);
+        bp->exp_off = bp->msg_off + round_up((size_t)n * bp->D * 32, 256);
+        bp->stage_off = bp->exp_off + round_up(bp->exp_bytes, 256);
         bp->pin_bytes = bp->stage_off + (host_tables ? (size_t)n * bp->U * table_bytes : 0);
-        bp->part_off = bp->work_bytes + up256(bp->pin_bytes);
+        bp->part_off = bp->work_bytes + round_up(bp->pin_bytes, 256);
         const size_t part_bytes = bp->plan == scd::kBrSlices ? (size_t)scd::bs_partials_bytes(n, s.nv, s.U, (int)s.K, (int)s.D, s.n_combos) : 0;
         DeviceGate gate_(bp->device);
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), bp->part_off + part_bytes));
@@ -243,7 +225,7 @@ extern "C" int sc_batch_prove_round(sc_batch_prover *bp, const uint64_t *r_or_nu
     if (bp->round + 1 > bp->nv) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
     std::vector<sch::Fr> chal;
     if (r_or_null)
-        if (int rc = take_challenges(bp, r_or_null, r_shared, chal)) return rc;
+        if (int rc = take_challenges(bp->n, r_or_null, r_shared, chal)) return rc;
     const uint32_t n = bp->n, D = bp->D;
     if (bp->work_area()) {
         const SharedMeta &s = bp->s;
@@ -284,9 +266,8 @@ extern "C" int sc_batch_prove_round(sc_batch_prover *bp, const uint64_t *r_or_nu
         for (uint32_t i = 0; i < n; ++i) {
             int rc = sc_prove_round(bp->provers[i], r_or_null ? challenge_of(chal, i).l : nullptr, out_evals + (size_t)i * D * 4);
             if (rc) {
-                const std::string why = sc_last_error();
                 bp->exhausted = true; // (a HIP failure part of the way through the batch: the handle needs a reset)
-                return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+                return prefix_instance(rc, i);
             }
         }
     }
@@ -306,62 +287,38 @@ extern "C" int sc_batch_prover_push_randomness(sc_batch_prover *bp, const uint64
 extern "C" int sc_batch_prover_state(sc_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness, uint64_t *tables_out, uint32_t *round) {
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
     if (instance >= bp->n) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: the handle holds %u instances", instance, bp->n);
-    if (randomness)
-        for (size_t j = 0; j < bp->randomness.size(); ++j) std::memcpy(randomness + 4 * j, &challenge_of(bp->randomness[j], instance), 32);
-    if (n_randomness) *n_randomness = (uint32_t)bp->randomness.size();
-    if (round) *round = bp->round;
+    batch_state_head(bp->randomness, instance, bp->round, randomness, n_randomness, round);
     if (!tables_out) return SC_OK;
     if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "tables were consumed by sc_batch_prover_bind_final");
     if (!bp->work_area()) return sc_prover_state(bp->provers[instance], nullptr, nullptr, tables_out, nullptr);
     const uint32_t bound = bp->round > 0 ? bp->round - 1 : 0;
-    const size_t bytes = (size_t)bp->U * ((size_t)32 << (bp->nv - bound));
     DeviceGate gate_(bp->device);
     HIP_TRY(hipSetDevice(bp->device));
-    char *d_up = bp->d_buf + bp->work_bytes;
-    HIP_TRY(scd::launch_batch_rounds_export(reinterpret_cast<const int32_t *>(bp->d_buf), instance, 1, bp->U, bp->nv, bound, nullptr, 0, reinterpret_cast<uint4 *>(d_up + bp->exp_off), bp->stream));
-    HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->exp_off, d_up + bp->exp_off, bytes, hipMemcpyDeviceToHost, bp->stream));
-    HIP_TRY(hipStreamSynchronize(bp->stream));
-    std::memcpy(tables_out, bp->h_pin + bp->exp_off, bytes);
-    return SC_OK;
+    return batch_export_out(reinterpret_cast<const int32_t *>(bp->d_buf), instance, 1, bp->U, bp->nv, bound, nullptr, 0, bp->d_buf + bp->work_bytes + bp->exp_off, bp->h_pin + bp->exp_off,
+                            tables_out, bp->stream);
 }
 
 extern "C" int sc_batch_prover_bind_final(sc_batch_prover *bp, const uint64_t *r, uint32_t r_shared, uint64_t *out_table_values) {
     if (!bp || !r || !out_table_values) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
     if (bp->exhausted || bp->round != bp->nv) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "bind_final needs a prover that has finished its last round");
     std::vector<sch::Fr> chal;
-    if (int rc = take_challenges(bp, r, r_shared, chal)) return rc;
+    if (int rc = take_challenges(bp->n, r, r_shared, chal)) return rc;
     const uint32_t n = bp->n, U = bp->U;
-    const size_t bytes = (size_t)n * U * 32;
     if (bp->work_area()) {
         DeviceGate gate_(bp->device);
         HIP_TRY(hipSetDevice(bp->device));
         char *d_up = bp->d_buf + bp->work_bytes;
         std::memcpy(bp->h_pin + bp->chal_off, chal.data(), chal.size() * 32);
         HIP_TRY(hipMemcpyAsync(d_up + bp->chal_off, bp->h_pin + bp->chal_off, chal.size() * 32, hipMemcpyHostToDevice, bp->stream));
-        HIP_TRY(scd::launch_batch_rounds_export(reinterpret_cast<const int32_t *>(bp->d_buf), 0, n, U, bp->nv, bp->nv - 1, reinterpret_cast<const uint4 *>(d_up + bp->chal_off),
-                                                chal.size() == 1 && n != 1 ? 1u : 0u, reinterpret_cast<uint4 *>(d_up + bp->exp_off), bp->stream));
-        HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->exp_off, d_up + bp->exp_off, bytes, hipMemcpyDeviceToHost, bp->stream));
-        HIP_TRY(hipStreamSynchronize(bp->stream));
-        std::memcpy(out_table_values, bp->h_pin + bp->exp_off, bytes);
+        if (int rc = batch_export_out(reinterpret_cast<const int32_t *>(bp->d_buf), 0, n, U, bp->nv, bp->nv - 1, reinterpret_cast<const uint4 *>(d_up + bp->chal_off),
+                                      chal.size() == 1 && n != 1 ? 1u : 0u, d_up + bp->exp_off, bp->h_pin + bp->exp_off, out_table_values, bp->stream))
+            return rc;
     } else {
-        for (uint32_t i = 0; i < n; ++i) {
-            sc_prover *p = bp->provers[i];
-            int rc = sc_prover_bind_final(p, challenge_of(chal, i).l, reinterpret_cast<uint64_t *>(bp->d_fin + (size_t)i * U * 32));
-            if (rc == SC_OK) {
-                DeviceGate gate_(bp->device);
-                hipError_t e = hipMemcpyAsync(out_table_values + (size_t)i * U * 4, bp->d_fin + (size_t)i * U * 32, (size_t)U * 32, hipMemcpyDeviceToHost, p->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    rc = sc_internal_fail(SC_ERR_HIP, "copying the final table values failed: %s", hipGetErrorString(e));
-                }
-            }
-            if (rc) {
-                const std::string why = sc_last_error();
+        for (uint32_t i = 0; i < n; ++i)
+            if (int rc = serial_bind_final(bp->provers[i], bp->device, challenge_of(chal, i).l, bp->d_fin + (size_t)i * U * 32, 0, U, out_table_values + (size_t)i * U * 4)) {
                 bp->exhausted = true;
-                return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
+                return prefix_instance(rc, i);
             }
-        }
     }
     bp->randomness.push_back(std::move(chal));
     bp->exhausted = true;
@@ -396,11 +353,7 @@ extern "C" int sc_batch_prover_reset(sc_batch_prover *bp, const sc_poly_desc *de
         }
     } else if (!bp->work_area()) {
         for (uint32_t i = 0; i < bp->n; ++i) { // the handles borrow the batch handle's own copy of the tables: rewound in place
-            int rc = sc_prover_reset(bp->provers[i], nullptr, SC_TABLES_ON_DEVICE);
-            if (rc) {
-                const std::string why = sc_last_error();
-                return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-            }
+            if (int rc = sc_prover_reset(bp->provers[i], nullptr, SC_TABLES_ON_DEVICE)) return prefix_instance(rc, i);
         }
     } // (a work area, the same tables: round 0's slots were never overwritten)
     bp->round = 0;

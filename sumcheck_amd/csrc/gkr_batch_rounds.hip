@@ -51,10 +51,6 @@ struct sc_gkr_batch_prover {
 
 namespace {
 
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-const sch::Fr &challenge_of(const std::vector<sch::Fr> &c, uint32_t i) { return c.size() == 1 ? c[0] : c[i]; }
-
 void destroy(sc_gkr_batch_prover *bp) {
     if (!bp) return;
     for (sc_prover *p : bp->p1)
@@ -71,20 +67,6 @@ void destroy(sc_gkr_batch_prover *bp) {
         (void)hipGetLastError();
     }
     delete bp;
-}
-
-int prefix(int rc, uint32_t i) {
-    const std::string why = sc_last_error();
-    return sc_internal_fail(rc, "instance %u: %s", i, why.c_str());
-}
-
-// the challenges of a call: canonical checks (no HIP call), then as the handle records them
-int take_challenges(const sc_gkr_batch_prover *bp, const uint64_t *r, uint32_t r_shared, std::vector<sch::Fr> &out) {
-    out.resize(r_shared ? 1 : bp->n);
-    std::memcpy(out.data(), r, out.size() * 32);
-    for (size_t i = 0; i < out.size(); ++i)
-        if (sch::geq_p(out[i])) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: challenge is not canonical", (uint32_t)i);
-    return SC_OK;
 }
 
 // challenge number j (0-based: u_0 .. u_{dim-1}, v_0 ..) of every instance -> the handle's device copy, [j][instance]; a shared one is expanded
@@ -131,14 +113,7 @@ int serial_prover(sc_gkr_batch_prover *bp, sc_prover **p, const void *t0, const 
 // the serial plan's phase change for instance i: f2(u) from phase one's prover, f1(g, u, .), f2(u) f3, phase two's prover
 int serial_phase_two(sc_gkr_batch_prover *bp, uint32_t i, const std::vector<sch::Fr> &u_last) {
     const uint32_t dim = bp->dim;
-    sc_prover *p = bp->p1[i];
-    char *fin = bp->d_fin + (size_t)i * 64;
-    if (int rc = sc_prover_bind_final(p, challenge_of(u_last, i).l, reinterpret_cast<uint64_t *>(fin))) return rc;
-    {
-        DeviceGate gate_(bp->device);
-        HIP_TRY(hipMemcpyAsync(&bp->f2u[i], fin + 32, 32, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-    }
+    if (int rc = serial_bind_final(bp->p1[i], bp->device, challenge_of(u_last, i).l, bp->d_fin + (size_t)i * 64, 1, 1, &bp->f2u[i])) return rc;
     std::vector<sch::Fr> u(dim);
     for (uint32_t j = 0; j + 1 < dim; ++j) u[j] = challenge_of(bp->randomness[j], i);
     u[dim - 1] = challenge_of(u_last, i);
@@ -199,46 +174,35 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
         build_shared(&pd.d, bp->s);
         bp->s.unit.push_back(unit_matrix(2, 3));
         bp->plan = scd::gkr_bs_plan(n, dim, nnz_max, bp->s.n_combos, scd::policy(scd::kPolBatch), scd::policy(scd::kPolBatchSlices));
-        // (batch_slices.hpp spells the envelopes out for the host tests: the launchers are guarded by the kernels' own)
-        if (bp->plan != scd::kGbrSerial && scd::gkr_batch_shape_fits(dim, nnz_max) != (bp->plan == scd::kGbrOneBlock)) bp->plan = scd::kGbrSerial;
         const bool areas = bp->work_areas(), slices = bp->plan == scd::kGbrSlices;
         // ---- the handle's copy of the inputs: every distinct (pointer, size) once ----
-        std::map<std::pair<const void *, size_t>, size_t> where;
-        std::vector<std::pair<const void *, size_t>> items;
-        size_t in_bytes = 0;
-        auto add = [&](const void *src, size_t bytes) -> size_t {
-            auto it = where.find({src, bytes});
-            if (it != where.end()) return it->second;
-            const size_t off = in_bytes;
-            where.emplace(std::make_pair(src, bytes), off);
-            items.emplace_back(src, bytes);
-            in_bytes += up256(bytes);
-            return off;
-        };
+        StageMap st; // (offsets into d_in)
+        st.align = 256;
         std::vector<size_t> offs((size_t)n * 4, 0);
         for (uint32_t i = 0; i < n; ++i) {
-            offs[4 * (size_t)i + 0] = nnz[i] ? add(f1_idx[i], (size_t)nnz[i] * 8) : 0;
-            offs[4 * (size_t)i + 1] = nnz[i] ? add(f1_vals[i], (size_t)nnz[i] * 32) : 0;
-            offs[4 * (size_t)i + 2] = add(f2[i], N * 32);
-            offs[4 * (size_t)i + 3] = add(f3[i], N * 32);
+            offs[4 * (size_t)i + 0] = nnz[i] ? st.add(f1_idx[i], (size_t)nnz[i] * 8) : 0;
+            offs[4 * (size_t)i + 1] = nnz[i] ? st.add(f1_vals[i], (size_t)nnz[i] * 32) : 0;
+            offs[4 * (size_t)i + 2] = st.add(f2[i], N * 32);
+            offs[4 * (size_t)i + 3] = st.add(f3[i], N * 32);
         }
-        bp->work_bytes = areas ? up256((size_t)n * 2 * 2 * (scd::kBatchRoundSlotBytes << dim)) : 0;
+        const size_t in_bytes = st.bytes;
+        bp->work_bytes = areas ? round_up((size_t)n * 2 * 2 * (scd::kBatchRoundSlotBytes << dim), 256) : 0;
         bp->w_off = 0;
-        bp->rec_off = bp->w_off + up256((size_t)bp->s.w_elems * 32);
-        bp->flag_off = bp->rec_off + up256((size_t)n * sizeof(scd::GkrBatchInst));
-        bp->g_off = bp->flag_off + up256((size_t)n * 4);
-        bp->u_off = bp->g_off + up256((size_t)n * dim * 32);
-        bp->msg_off = bp->u_off + up256((size_t)2 * dim * n * 32);
-        bp->f2u_off = bp->msg_off + up256((size_t)n * 3 * 32);
-        bp->exp_off = bp->f2u_off + up256((size_t)n * 32);
-        bp->pin_bytes = bp->exp_off + up256(std::max(2 * N * 32, (size_t)n * 2 * 32)); // one instance's tables (state), or every instance's final values
+        bp->rec_off = bp->w_off + round_up((size_t)bp->s.w_elems * 32, 256);
+        bp->flag_off = bp->rec_off + round_up((size_t)n * sizeof(scd::GkrBatchInst), 256);
+        bp->g_off = bp->flag_off + round_up((size_t)n * 4, 256);
+        bp->u_off = bp->g_off + round_up((size_t)n * dim * 32, 256);
+        bp->msg_off = bp->u_off + round_up((size_t)2 * dim * n * 32, 256);
+        bp->f2u_off = bp->msg_off + round_up((size_t)n * 3 * 32, 256);
+        bp->exp_off = bp->f2u_off + round_up((size_t)n * 32, 256);
+        bp->pin_bytes = bp->exp_off + round_up(std::max(2 * N * 32, (size_t)n * 2 * 32), 256); // one instance's tables (state), or every instance's final values
         {
             DeviceGate gate_(bp->device);
             HIP_TRY(hipSetDevice(bp->device));
             HIP_TRY(hipStreamCreateWithFlags(&bp->stream, hipStreamNonBlocking));
-            const size_t tabs_bytes = areas ? 0 : (size_t)n * 3 * N * 32, fin_bytes = areas ? 0 : up256((size_t)n * 64);
+            const size_t tabs_bytes = areas ? 0 : (size_t)n * 3 * N * 32, fin_bytes = areas ? 0 : round_up((size_t)n * 64, 256);
             bp->cells_bytes = slices ? (size_t)n * scd::kBsGkrCellBytes * N : 0;
-            const size_t part_bytes = slices ? up256((size_t)scd::bs_partials_bytes(n, dim, 2, 1, 3, bp->s.n_combos)) : 0;
+            const size_t part_bytes = slices ? round_up((size_t)scd::bs_partials_bytes(n, dim, 2, 1, 3, bp->s.n_combos), 256) : 0;
             HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), 2 * bp->work_bytes + bp->pin_bytes + in_bytes + tabs_bytes + fin_bytes + bp->cells_bytes + part_bytes)); // (one allocation: a handle's life is short)
             bp->d_in = bp->d_buf + 2 * bp->work_bytes + bp->pin_bytes;
             if (!areas) {
@@ -251,14 +215,10 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             }
             HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&bp->h_pin), bp->pin_bytes, hipHostMallocDefault));
             if (dev_in) HIP_TRY(hipDeviceSynchronize()); // the inputs' producers are waited for, as a copy on their stream would
-            size_t off = 0;
-            for (const auto &it : items) {
-                HIP_TRY(hipMemcpyAsync(bp->d_in + off, it.first, it.second, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, bp->stream));
-                off += up256(it.second);
-            }
+            for (const StageMap::Item &it : st.items) HIP_TRY(hipMemcpyAsync(bp->d_in + it.off, it.src, it.bytes, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, bp->stream));
             char *d_up = bp->d_buf + 2 * bp->work_bytes;
             instance_weights(bp->s, sch::kOne.l, reinterpret_cast<sch::Fr *>(bp->h_pin + bp->w_off));
-            std::memset(bp->h_pin + bp->flag_off, 0, up256((size_t)n * 4));
+            std::memset(bp->h_pin + bp->flag_off, 0, round_up((size_t)n * 4, 256));
             std::memcpy(bp->h_pin + bp->g_off, bp->g.data(), (size_t)n * dim * 32);
             bp->rec.resize(n);
             for (uint32_t i = 0; i < n; ++i) {
@@ -297,7 +257,7 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             const scd::GkrBatchInst &I = bp->rec[i];
             int rc = sc_internal_gkr_dense_table(1, I.idx, I.vals, nnz[i], dim, I.f3, bp->g[(size_t)i * dim].l, nullptr, serial_table(bp, i, 0)); // mod.rs:30-38
             if (rc == SC_OK) rc = serial_prover(bp, &bp->p1[i], serial_table(bp, i, 0), I.f2);
-            if (rc) return prefix(rc, i);
+            if (rc) return prefix_instance(rc, i);
         }
         return SC_OK;
     };
@@ -321,7 +281,7 @@ extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t 
     if (bp->round + 1 > 2 * bp->dim) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
     std::vector<sch::Fr> chal;
     if (r_or_null)
-        if (int rc = take_challenges(bp, r_or_null, r_shared, chal)) return rc;
+        if (int rc = take_challenges(bp->n, r_or_null, r_shared, chal)) return rc;
     const uint32_t n = bp->n, dim = bp->dim, t = bp->round, phase = t / dim, r = t % dim;
     if (bp->work_areas()) {
         const SharedMeta &s = bp->s;
@@ -374,7 +334,7 @@ extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t 
             if (rc == SC_OK) rc = sc_prove_round(phase ? bp->p2[i] : bp->p1[i], r ? challenge_of(chal, i).l : nullptr, out_evals + (size_t)i * 12);
             if (rc) {
                 bp->exhausted = true; // (a failure part of the way through the batch: the handle needs a reset)
-                return prefix(rc, i);
+                return prefix_instance(rc, i);
             }
         }
     }
@@ -387,7 +347,7 @@ extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_
     if (!bp || !r) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
     if (bp->exhausted || bp->round != 2 * bp->dim) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "finish needs a prover that has answered its last round");
     std::vector<sch::Fr> chal;
-    if (int rc = take_challenges(bp, r, r_shared, chal)) return rc;
+    if (int rc = take_challenges(bp->n, r, r_shared, chal)) return rc;
     const uint32_t n = bp->n, dim = bp->dim;
     std::vector<sch::Fr> fin((size_t)n * 3); // f1(g,u,v), f2(u), f2(u) f3(v)
     if (bp->work_areas()) {
@@ -408,22 +368,10 @@ extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_
         }
     } else {
         for (uint32_t i = 0; i < n; ++i) {
-            sc_prover *p = bp->p2[i];
-            char *d = bp->d_fin + (size_t)i * 64;
             sch::Fr two[2];
-            int rc = sc_prover_bind_final(p, challenge_of(chal, i).l, reinterpret_cast<uint64_t *>(d));
-            if (rc == SC_OK) {
-                DeviceGate gate_(bp->device);
-                hipError_t e = hipMemcpyAsync(two, d, 64, hipMemcpyDeviceToHost, p->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    rc = sc_internal_fail(SC_ERR_HIP, "copying the final table values failed: %s", hipGetErrorString(e));
-                }
-            }
-            if (rc) {
+            if (int rc = serial_bind_final(bp->p2[i], bp->device, challenge_of(chal, i).l, bp->d_fin + (size_t)i * 64, 0, 2, two)) {
                 bp->exhausted = true;
-                return prefix(rc, i);
+                return prefix_instance(rc, i);
             }
             fin[3 * (size_t)i + 0] = two[0];
             fin[3 * (size_t)i + 1] = bp->f2u[i];
@@ -442,32 +390,23 @@ extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_
 extern "C" int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness, uint64_t *tables_out, uint32_t *round) {
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
     if (instance >= bp->n) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: the handle holds %u instances", instance, bp->n);
-    if (randomness)
-        for (size_t j = 0; j < bp->randomness.size(); ++j) std::memcpy(randomness + 4 * j, &challenge_of(bp->randomness[j], instance), 32);
-    if (n_randomness) *n_randomness = (uint32_t)bp->randomness.size();
-    if (round) *round = bp->round;
+    batch_state_head(bp->randomness, instance, bp->round, randomness, n_randomness, round);
     if (!tables_out) return SC_OK;
     if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "tables were consumed by sc_gkr_batch_prover_finish");
     // the current phase's two tables: phase one's until round call dim has built phase two's; bound = the phase's max(round - 1, 0)
     const uint32_t dim = bp->dim, phase = bp->round > dim ? 1u : 0u, pr = bp->round - phase * dim, bound = pr > 0 ? pr - 1 : 0;
     if (!bp->work_areas()) return sc_prover_state(phase ? bp->p2[instance] : bp->p1[instance], nullptr, nullptr, tables_out, nullptr);
-    const size_t bytes = (size_t)2 * ((size_t)32 << (dim - bound));
     DeviceGate gate_(bp->device);
     HIP_TRY(hipSetDevice(bp->device));
-    char *d_up = bp->d_buf + 2 * bp->work_bytes;
-    HIP_TRY(scd::launch_batch_rounds_export(reinterpret_cast<const int32_t *>(bp->d_buf + (phase ? bp->work_bytes : 0)), instance, 1, 2, dim, bound, nullptr, 0,
-                                            reinterpret_cast<uint4 *>(d_up + bp->exp_off), bp->stream));
-    HIP_TRY(hipMemcpyAsync(bp->h_pin + bp->exp_off, d_up + bp->exp_off, bytes, hipMemcpyDeviceToHost, bp->stream));
-    HIP_TRY(hipStreamSynchronize(bp->stream));
-    std::memcpy(tables_out, bp->h_pin + bp->exp_off, bytes);
-    return SC_OK;
+    return batch_export_out(reinterpret_cast<const int32_t *>(bp->d_buf + (phase ? bp->work_bytes : 0)), instance, 1, 2, dim, bound, nullptr, 0, bp->d_buf + 2 * bp->work_bytes + bp->exp_off,
+                            bp->h_pin + bp->exp_off, tables_out, bp->stream);
 }
 
 extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
     if (!bp->work_areas())
         for (uint32_t i = 0; i < bp->n; ++i) // phase one's provers borrow the handle's own tables: rewound in place (phase two's are rewound over new tables at the phase change)
-            if (int rc = sc_prover_reset(bp->p1[i], nullptr, SC_TABLES_ON_DEVICE)) return prefix(rc, i);
+            if (int rc = sc_prover_reset(bp->p1[i], nullptr, SC_TABLES_ON_DEVICE)) return prefix_instance(rc, i);
     // (work areas: area A's depth 0 was never overwritten)
     bp->round = 0;
     bp->exhausted = false;

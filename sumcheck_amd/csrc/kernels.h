@@ -3,13 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "batch_shape.hpp"
 #include "lag_index.hpp"
 #include "lane_sum.hpp"
 
 namespace scd {
 
-constexpr int kMaxFusedM = 8;  // products up to this many multiplicands run register-resident and fused with the bind
-constexpr int kMaxSmallTables = 32;         // table-pointer block that fits a kernel argument
+// (kMaxFusedM, kMaxSmallTables, kMetaProds, kTsBlock and the batched kernels' shape rule: batch_shape.hpp)
 constexpr uint64_t kSmallRoundPairs = 1u << 14; // rounds at or below this many pairs are latency-bound: split finer (bind launch + one lane per
                                                 // (combination, pair)).  2^16 until round 4: at 2^16 and 2^15 pairs that pair of launches moves 2.2x
                                                 // the bytes of the fused tree kernel (every node's combination re-reads its product's tables) and
@@ -137,7 +137,6 @@ struct FoldArgs {
 // dst[y][i] = fold over `levels` variables of src[y][i << levels ...], i < n_out, y < n_tables (grid.y)
 hipError_t launch_fold_multi(const FoldArgs &args, int levels, int n_tables, uint64_t n_out, hipStream_t stream);
 
-constexpr int kMetaProds = 16;
 struct FinMeta {
     FinProd prod[kMetaProds];
 };
@@ -196,13 +195,8 @@ struct TailArgs {
 };
 // The same rounds with the tables resident in LDS (kernels_tail.hip: k_tail_slices): block g of B owns a contiguous range of every
 // table for the whole launch; one hand-over per round (its sums -> block 0) as self-validating words in `xw`.
-constexpr int kTsBlock = 256, kTsMaxBlocks = 256;
-// lanes per (product, node) combination of the LDS-resident round body (batch_round.hpp): a power of two, all of a combination's lanes in one wavefront
-__host__ __device__ constexpr int bt_lanes(int n_combos) {
-    int L = 64;
-    while (L * n_combos > kTsBlock) L >>= 1;
-    return L;
-}
+constexpr int kTsMaxBlocks = 256;
+// (bt_lanes, the lanes per (product, node) combination of the LDS-resident round body: batch_shape.hpp)
 // (kLazySumMaxP and lazy_sum_needs_reduce, the rule of every lazy sum: lane_sum.hpp)
 // A line through two lazy entries leaves the entries' range: entries in (-(w - 1) p, p) put node x > 0 (x - 1 slopes beyond hi) and node -x
 // (x slopes beyond lo) within (n w - 1) p, n = ceil(D / 2) for a list of degree D.  A product is the chain prod = fe_mul(line, prod), and a
@@ -263,16 +257,13 @@ struct BatchArgs {
     uint32_t max_spins;
     uint32_t fin_bytes;         // (filled in by the launcher: LDS layout -- finalize scratch | message | tables)
 };
-bool batch_shape_fits(uint32_t nv, uint32_t n_tables, int K, int D, uint32_t max_multiplicands); // the envelope: one block's LDS, products of <= kMaxFusedM
+// (the envelope, one block's LDS and products of <= kMaxFusedM: batch_shape_fits, batch_shape.hpp)
 int batch_blocks_per_cu(int device, uint32_t nv, uint32_t n_tables, int K, int D);             // occupancy of k_batch_proofs at that LDS size (0: unknown)
 hipError_t launch_batch_proofs(BatchArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream);
 // Batched GKR round proofs (kernels_batch_gkr.hip: k_batch_gkr): n independent instances of GKRRoundSumcheck::prove of one dim, ONE block per
 // instance: both initialisations into LDS (wide integer cells, LDS atomics), then 2 x dim rounds of k_batch_proofs' round body
-// (batch_round.hpp) over one product of two tables.  The envelope: dim <= kGkrBatchMaxDim (tables 2 x 48 B, eq(g, .) and eq(u, .) 2 x 32 B, the
-// accumulator 64 B per cell: 208 B x 2^dim + finalize scratch <= 144 KB; dim = 10 does not fit even with the eq tables as halves), and
-// nnz <= kGkrBatchMaxNnzPerCell x 2^dim per instance (one block of 256 lanes walks the list twice: beyond that sc_gkr_prove's grids win).
-constexpr int kGkrBatchMaxDim = 9;
-constexpr uint64_t kGkrBatchMaxNnzPerCell = 64;
+// (batch_round.hpp) over one product of two tables.  The envelope, dim <= kGkrBatchMaxDim and nnz <= kGkrBatchMaxNnzPerCell x 2^dim per
+// instance: gkr_batch_shape_fits, batch_shape.hpp.
 struct GkrBatchInst { // device memory, one per instance; every pointer is device memory that is only read
     const uint64_t *idx; // nnz indices (z, x, y): z in the low dim bits
     const uint4 *vals;   // nnz values
@@ -293,7 +284,6 @@ struct BatchGkrArgs {
     uint32_t max_spins;
     uint32_t fin_bytes;         // (filled in by the launcher)
 };
-bool gkr_batch_shape_fits(uint32_t dim, uint64_t nnz_max);
 int gkr_batch_blocks_per_cu(int device, uint32_t dim); // occupancy of k_batch_gkr at that LDS size (0: unknown)
 hipError_t launch_batch_gkr_idx_range(const GkrBatchInst *inst, uint32_t n, uint32_t dim, uint32_t *flags, hipStream_t stream); // flags[i] |= 1: an index of instance i has a bit at or above 3 dim
 hipError_t launch_batch_gkr(BatchGkrArgs args, const ComboMeta &meta, const FinMeta &fin, int grid, hipStream_t stream);
@@ -323,8 +313,7 @@ hipError_t launch_batch_gkr_eval(const GkrBatchInst *inst, uint32_t n, uint32_t 
 // 48-byte LDS slots (kBtEnt words, copied verbatim: every magnitude is k_batch_proofs'), table u of instance i at slot
 // (i * n_tables + u) * 2 * 2^nv, and inside that region the table bound b times at batch_rounds_off(nv, b): the round-0 tables are never
 // overwritten (a reset to the same tables rewinds a counter), and a round never writes what it reads.
-constexpr size_t kBatchRoundSlotBytes = 48; // (kBtEnt words: batch_round.hpp)
-constexpr uint64_t batch_rounds_off(uint32_t nv, uint32_t bound) { return bound ? (2ULL << nv) - ((1ULL << nv) >> (bound - 1)) : 0; }
+// (kBatchRoundSlotBytes, batch_rounds_off: batch_shape.hpp)
 struct BatchRoundArgs {
     int32_t *work;              // device: n x n_tables x 2 x 2^nv slots of kBtEnt words
     const uint4 *Wm;            // device: n x w_stride elements, as in BatchArgs

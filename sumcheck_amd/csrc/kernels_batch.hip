@@ -86,13 +86,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_proofs(const BatchArgs A, co
     }
 }
 
-static size_t bt_lds_bytes(uint32_t nv, uint32_t n_tables, int K, int D) { return bt_fin_bytes(K, D) + ((size_t)n_tables << nv) * (kBtEnt * 4); }
-
-bool batch_shape_fits(uint32_t nv, uint32_t n_tables, int K, int D, uint32_t max_multiplicands) {
-    if (nv == 0 || nv > 16 || n_tables == 0 || n_tables > (uint32_t)kMaxSmallTables || K < 1 || K > kMetaProds || max_multiplicands > (uint32_t)kMaxFusedM) return false;
-    if ((uint32_t)D * 8u > (uint32_t)kTsBlock) return false; // (one lane per word of the message)
-    return bt_lds_bytes(nv, n_tables, K, D) <= kBtLdsMax;
-}
+// (the envelope and the launch's dynamic LDS: batch_shape_fits, bt_lds_bytes -- batch_shape.hpp)
 static hipError_t batch_attr() { // (more dynamic LDS than the default 64 KB limit of a launch)
     static bool done[64] = {};
     return ensure_dynamic_lds(reinterpret_cast<const void *>(k_batch_proofs<kMaxFusedM>), (int)kBtLdsMax, done);

@@ -126,13 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_gkr_idx_range(const GkrBatchIn
     }
 }
 
-static size_t bg_lds_bytes(uint32_t dim) { return bt_fin_bytes(1, 3) + ((size_t)1 << dim) * (2 * kBtEnt * 4 + 2 * 32 + 64); }
-
-bool gkr_batch_shape_fits(uint32_t dim, uint64_t nnz_max) {
-    if (dim == 0 || dim > (uint32_t)kGkrBatchMaxDim) return false;
-    if (nnz_max > ((uint64_t)kGkrBatchMaxNnzPerCell << dim)) return false; // (one block walks the whole list twice)
-    return bg_lds_bytes(dim) <= kBtLdsMax;
-}
+// (the envelope and the launch's dynamic LDS: gkr_batch_shape_fits, bg_lds_bytes -- batch_shape.hpp)
 static hipError_t batch_gkr_attr() { // (more dynamic LDS than the default 64 KB limit of a launch)
     static bool done[64] = {};
     return ensure_dynamic_lds(reinterpret_cast<const void *>(k_batch_gkr), (int)kBtLdsMax, done);

@@ -28,7 +28,6 @@
 
 namespace scd {
 
-static_assert(kBsGkrMaxDim == (uint32_t)kGkrBatchMaxDim && kBsGkrMaxNnzPerCell == kGkrBatchMaxNnzPerCell, "batch_slices.hpp mirrors kernels.h");
 static_assert(kBsGkrTermsPerBlock % kTsBlock == 0 && kBsGkrCellBytes == 8 * sizeof(uint64_t), "a block's share is whole strides; eight lanes a cell");
 
 constexpr uint32_t kGsHalf = 1u << ((kBsMaxNv + 1) / 2); // entries of a half table at the most
@@ -97,9 +96,9 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_fold(const BatchGkrSlice
 }
 
 hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream) {
-    if ((phase != 1 && phase != 2) || args.n == 0 || args.dim <= kBsGkrMaxDim || args.dim > kBsMaxNv || !args.inst || !args.work_a || !args.cells) return hipErrorInvalidValue;
+    if ((phase != 1 && phase != 2) || args.n == 0 || args.dim <= (uint32_t)kGkrBatchMaxDim || args.dim > kBsMaxNv || !args.inst || !args.work_a || !args.cells) return hipErrorInvalidValue;
     if (phase == 2 && (!args.work_b || !args.u || !args.f2u)) return hipErrorInvalidValue;
-    if (nnz_max > (kBsGkrMaxNnzPerCell << args.dim)) return hipErrorInvalidValue; // (the lanes' bound)
+    if (nnz_max > (kGkrBatchMaxNnzPerCell << args.dim)) return hipErrorInvalidValue; // (the lanes' bound)
     const uint64_t B = gkr_bs_term_blocks(nnz_max), grid_terms = (uint64_t)args.n * B, grid_fold = (((uint64_t)args.n << args.dim) + kTsBlock - 1) / kTsBlock;
     if (grid_terms >= (1ULL << 31) || grid_fold >= (1ULL << 31)) return hipErrorInvalidValue;
     args.blocks_per_inst = (uint32_t)B;

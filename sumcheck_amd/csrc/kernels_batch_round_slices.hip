@@ -19,12 +19,6 @@
 
 namespace scd {
 
-static_assert(kBsMaxTables == (uint32_t)kMaxSmallTables && kBsMaxProds == kMetaProds && kBsMaxMult == (uint32_t)kMaxFusedM && kBsBlock == kTsBlock, "batch_slices.hpp mirrors kernels.h");
-static_assert(kBsSlotBytes == kBatchRoundSlotBytes && kBsSlotBytes == kBtEnt * sizeof(int32_t) && kBsLdsMax == kBtLdsMax && kBsSliceLds <= kBtLdsMax, "batch_slices.hpp mirrors batch_round.hpp");
-static_assert(bs_lanes(1) == bt_lanes(1) && bs_lanes(4) == bt_lanes(4) && bs_lanes(5) == bt_lanes(5) && bs_lanes(16) == bt_lanes(16) && bs_lanes(17) == bt_lanes(17) &&
-                  bs_lanes(kMetaCombos) == bt_lanes(kMetaCombos),
-              "batch_slices.hpp mirrors bt_lanes");
-
 template <int kSlots>
 __global__ __launch_bounds__(kTsBlock) void k_batch_round_slices(const BatchRoundSlicesArgs A, const ComboMeta meta, const FinMeta fin) {
     extern __shared__ uint4 dyn_lds[];
@@ -113,13 +107,10 @@ hipError_t launch_batch_round_slices(BatchRoundArgs args, uint4 *partials, const
     if (args.n == 0 || args.round >= args.nv || args.nv > kBsMaxNv || !bs_envelope(args.nv, args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM)) return hipErrorInvalidValue;
     if (args.n_combos < 1 || args.n_combos > kMetaCombos || !args.work || !args.Wm || !args.out || !partials || (args.round && !args.chal)) return hipErrorInvalidValue;
     const uint32_t loaded = bs_loaded_log2(args.nv, args.round);
-    // sliced rounds only, by both spellings of the rule (batch_slices.hpp's mirror and the launcher k_batch_round is guarded by)
-    if (!bs_round_sliced(args.nv, args.round, args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM) || batch_shape_fits(loaded, args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM))
-        return hipErrorInvalidValue;
+    if (!bs_round_sliced(args.nv, args.round, args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM)) return hipErrorInvalidValue; // (sliced rounds only: the others are launch_batch_round's)
     const uint32_t es = bs_slice_log2(loaded, args.n_tables, args.K, args.D), ss = loaded - es;
     const size_t lds = ((size_t)args.n_tables << es) * (kBtEnt * 4);
     if (es < 2 || ss < 1 || lds > kBsSliceLds || ((uint64_t)args.n << ss) >= (1ULL << 31) || !bs_lane_sums_hold(es, args.round, args.n_combos)) return hipErrorInvalidValue;
-    if (bs_fin_bytes(args.K, args.D) != bt_fin_bytes(args.K, args.D)) return hipErrorInvalidValue;
     static bool done[64] = {}; // (the finalize scratch of a long list may pass the default 64 KB limit of a launch)
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_batch_round_fin), (int)kBtLdsMax, done); e != hipSuccess) return e;
     if constexpr (kBsSliceLds > 64 * 1024) { // (an A/B build with larger slices: beyond the default limit of a launch)

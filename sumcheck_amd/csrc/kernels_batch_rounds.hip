@@ -117,11 +117,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_rounds_export(const int32_t 
     fr_store(out + 2 * i, fe_to_fr(v));
 }
 
-// the launch's dynamic LDS: finalize scratch | message | the tables as loaded (bound max(round - 1, 0) times)
-static size_t br_lds_bytes(uint32_t nv, uint32_t round, uint32_t n_tables, int K, int D) {
-    return bt_fin_bytes(K, D) + ((size_t)n_tables << (nv - (round ? round - 1 : 0))) * (kBtEnt * 4);
-}
-
+// (the launch's dynamic LDS, finalize scratch | message | the tables as loaded: br_lds_bytes, batch_shape.hpp)
 hipError_t launch_batch_round(BatchRoundArgs args, const ComboMeta &meta, const FinMeta &fin, hipStream_t stream) {
     if (args.n == 0 || args.round >= args.nv || args.nv > 16 || !batch_shape_fits(args.nv - (args.round ? args.round - 1 : 0), args.n_tables, args.K, args.D, (uint32_t)kMaxFusedM)) return hipErrorInvalidValue;
     if (args.n_combos < 1 || args.n_combos > kMetaCombos || !args.work || !args.Wm || !args.out || (args.round && !args.chal)) return hipErrorInvalidValue;

@@ -292,6 +292,42 @@ struct GkrBatchIn {
 int gkr_check_instance(const GkrBatchIn &in, uint32_t i, const uint64_t *uv_or_null); // ... sc_gkr_prove's checks on instance i (no HIP call), errors behind "instance %u: "
 // ... and the check of device-resident index lists in front of any kernel that follows them (flags: n zeroed words at flag_off of the image)
 int gkr_check_idx_on_device(const scd::GkrBatchInst *d_rec, uint32_t n, uint32_t dim, char *h_up, char *d_up, size_t flag_off, hipStream_t stream);
+// what the batched entry points and the two batch handles (batch_rounds.hip, gkr_batch_rounds.hip) share
+size_t round_up(size_t v, size_t a);
+int prefix_instance(int rc, uint32_t i); // the error a step on instance i has just left, behind "instance i: "
+const sch::Fr &challenge_of(const std::vector<sch::Fr> &c, uint32_t i); // instance i's challenge of a call: its own, or the ONE all share
+// the challenges of a call to a handle of n instances: canonical checks (no HIP call), then as the handle records them
+int take_challenges(uint32_t n, const uint64_t *r, uint32_t r_shared, std::vector<sch::Fr> &out);
+struct StageMap { // arrays behind one another in an image, every distinct (pointer, size) once
+    struct Item {
+        const void *src;
+        size_t bytes, off;
+    };
+    std::vector<Item> items;
+    std::map<std::pair<const void *, size_t>, size_t> where;
+    size_t base = 0, bytes = 0, align = 32;
+    size_t add(const void *src, size_t n_bytes) { // -> offset of the array's copy in the image
+        auto it = where.find({src, n_bytes});
+        if (it != where.end()) return it->second;
+        const size_t off = base + bytes;
+        items.push_back({src, n_bytes, off});
+        where.emplace(std::make_pair(src, n_bytes), off);
+        bytes += round_up(n_bytes, align);
+        return off;
+    }
+    void copy_into(char *h_up) const {
+        for (const Item &it : items) std::memcpy(h_up + it.off, it.src, it.bytes);
+    }
+};
+// sc_prover_bind_final on a prover of a handle's serial plan, its values into d_fin; then `count` of them from value `first` on to the
+// host, on the prover's stream under the gate of the handle's device (one copy, one synchronisation)
+int serial_bind_final(sc_prover *p, int device, const uint64_t *r, char *d_fin, uint32_t first, uint32_t count, void *h_out);
+// the randomness / n_randomness / round outputs of a handle's _state call (each may be null)
+void batch_state_head(const std::vector<std::vector<sch::Fr>> &rand, uint32_t instance, uint32_t round_now, uint64_t *randomness, uint32_t *n_randomness, uint32_t *round);
+// launch_batch_rounds_export (its arguments up to chal_shared) into d_exp, one copy into the pinned h_exp, one synchronisation, the bytes
+// to the caller's `out`; the caller holds the device gate
+int batch_export_out(const int32_t *work, uint32_t first, uint32_t count, uint32_t n_tables, uint32_t nv, uint32_t bound, const uint4 *d_chal_or_null, uint32_t chal_shared, char *d_exp,
+                     char *h_exp, void *out, hipStream_t stream);
 // ---- gkr.hip ----
 int sc_internal_gkr_dense_table(int phase, const uint64_t *d_idx, const void *d_vals, uint64_t nnz, uint32_t dim, const void *d_f3, const uint64_t *g, const uint64_t *u_or_null,
                                 void *d_out); // one dense table of a GKR proof by sc_gkr_prove's route, device-resident inputs

@@ -26,8 +26,20 @@ int main() {
     uint32_t dim = 0, j = 0;
     uint64_t n = 0, nnz = 0, handles = 0, sliced = 0, sliced_rounds = 0;
     int pb = 0, ps = 0;
-    static_assert(kBsGkrMaxDim == 9 && kBsGkrMaxNnzPerCell == 64 && kBsMaxNv == 16 && kBsMaxWorkBytes == (16ULL << 30), "the constants");
+    static_assert(kGkrBatchMaxDim == 9 && kGkrBatchMaxNnzPerCell == 64 && kBsMaxNv == 16 && kBsMaxWorkBytes == (16ULL << 30), "the constants");
     CHECK(fits(10) && !fits(11)); // one block holds two tables of 2^10 entries: at dim 10 no round is sliced
+    // gkr_batch_shape_fits (batch_shape.hpp): dim 1 .. 9 -- 224 B a cell and the finalize scratch within one block's LDS -- and nnz within the cap
+    CHECK(fin_bytes() + ((size_t)224 << 9) <= kLdsMax && fin_bytes() + ((size_t)224 << 10) > kLdsMax && fin_bytes() + ((size_t)160 << 10) > kLdsMax);
+    for (dim = 0; dim <= 22; ++dim) {
+        const uint64_t cap = 64ULL << dim;
+        CHECK(bg_lds_bytes(dim) == fin_bytes() + ((size_t)(2 * kSlot + 2 * 32 + 64) << dim));
+        const uint64_t around[] = {cap - 1, cap, cap + 1};
+        for (uint64_t nnz_ : around) {
+            nnz = nnz_;
+            CHECK(gkr_batch_shape_fits(dim, nnz) == (dim >= 1 && dim <= 9 && nnz <= cap));
+        }
+    }
+    nnz = 0;
     for (dim = 1; dim <= 22; ++dim) {
         const uint64_t cap = 64ULL << dim;
         const uint64_t per_inst = 2 * (2 * 2 * kSlot << dim) + (64ULL << dim); // areas A and B, the cells
@@ -48,6 +60,7 @@ int main() {
                         if (envelope && dim <= 9) want = kGbrOneBlock;
                         else if (envelope && ps == 1 && dim >= 10 && n * per_inst <= (16ULL << 30)) want = kGbrSlices; // (every grid of such a handle is far below 2^31: checked below)
                         CHECK(plan == want);
+                        CHECK((plan == kGbrOneBlock) == (pb != 0 && gkr_batch_shape_fits(dim, nnz))); // one block exactly when the shape fits and the policy allows (what sc_gkr_batch_prover_init relies on)
                         CHECK(gkr_bs_plan(n, dim, nnz, kCombos, pb, 0) == (envelope && dim <= 9 ? kGbrOneBlock : kGbrSerial)); // the default of the key: nothing changes
                         CHECK(gkr_bs_plan(n, dim, nnz, kCombos, 0, ps) == kGbrSerial);
                         if (plan != kGbrSlices) continue;
