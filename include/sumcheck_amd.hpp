@@ -705,6 +705,28 @@ class GKRBatchProverState {
                 DenseMultilinearExtension{nv, std::vector<Fr>(buf.begin() + (size_t(1) << nv), buf.end())}};
     }
     void reset() { check(sc_gkr_batch_prover_reset(h_)); }
+    // the handle onto the next layer's inputs (sc_gkr_layer_next_batch): nothing is allocated; afterwards round 0, as prover_init_batch over
+    // these inputs would leave it.  f1s empty: the wiring the handle holds is kept.  Pointers may repeat; an argument error leaves the handle where it was.
+    void next_layer(const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                    const std::vector<const SparseMultilinearExtension *> &f1s = {}) {
+        const bool keep = f1s.empty();
+        if (f2s.size() != n || f3s.size() != n || gs.size() != n || (!keep && f1s.size() != n)) throw Panic(SC_ERR_BAD_ARG, "one f2, f3 and g per instance, and one f1 or none at all");
+        std::vector<const uint64_t *> idx(n + 1), vals(n + 1), p2(n + 1), p3(n + 1), pg(n + 1);
+        std::vector<uint64_t> nnz(n + 1);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f2s[i] || !f3s[i] || (!keep && !f1s[i])) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim || (!keep && f1s[i]->num_vars != 3 * dim)) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            if (!keep) {
+                idx[i] = f1s[i]->indices.data();
+                vals[i] = f1s[i]->values.empty() ? nullptr : f1s[i]->values[0].l;
+                nnz[i] = f1s[i]->indices.size();
+            }
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+            pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+        }
+        check(sc_gkr_layer_next_batch(h_, keep ? nullptr : idx.data(), keep ? nullptr : vals.data(), keep ? nullptr : nnz.data(), p2.data(), p3.data(), pg.data(), 0));
+    }
     sc_gkr_batch_prover *raw() { return h_; }
     std::vector<Fr> challenges(const std::vector<VerifierMsg> &v_msgs) const {
         if (v_msgs.size() != n && v_msgs.size() != 1) throw Panic(SC_ERR_BAD_ARG, "one VerifierMsg per instance, or a single one for all");

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, and sc_gkr_layer_next_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -427,9 +427,39 @@ SC_API_GKRB int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64
  * phase one's until call dim has been answered.  Every pointer but bp may be NULL. */
 SC_API_GKRB int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness,
                                           uint64_t *tables_out, uint32_t *round);
-/* Rewind to round 0 over the inputs the handle holds, without reallocating and without rebuilding phase one's tables.  New inputs: a new handle. */
+/* Rewind to round 0 over the inputs the handle holds, without reallocating and without rebuilding phase one's tables.  New inputs:
+ * sc_gkr_layer_next_batch, below. */
 SC_API_GKRB int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp);
 SC_API_GKRB void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp);
+/* ---- the handle onto the NEXT LAYER's inputs, without a rebuild ---------------------------------------------------------------------------
+ * A GKR prover runs one round sumcheck per layer under one transcript, and every layer has new inputs: its g is the previous layer's
+ * point, its f2 and f3 are the next layer's values, often it has wiring of its own.  sc_gkr_layer_next_batch puts an existing handle onto
+ * them: it ALLOCATES NOTHING and leaves the handle at round 0 with phase one's tables built, exactly as a fresh sc_gkr_batch_prover_init
+ * over these inputs would -- same plan, same bits.  It may be called in any state [fresh, in the middle of either phase, after finish];
+ * afterwards round is 0, the kept randomness is empty and the handle is not exhausted.
+ * SC_API_GKRL is SC_API: a marker of its own, for the reason SC_API_EXT and SC_API_GKRB have one [tests/test_gkr_next_layer_host.py
+ * compares this prototype with the shim's declaration; the older scanners each assert a closed set]. */
+#define SC_API_GKRL SC_API /* [nothing but this comment may follow on the line] */
+/* Arguments mean what they mean for sc_gkr_batch_prover_init; n and dim are the handle's.  flags & SC_TABLES_ON_DEVICE must equal what the
+ * handle was built with [SC_ERR_BAD_ARG otherwise].  f1: all three of f1_idx, f1_vals and nnz NULL keeps the wiring the handle holds, all
+ * three given is new wiring, a mixture is SC_ERR_BAD_ARG.  f2, f3 and g are required; pointers may repeat within and across instances.
+ * PLAN: the one chosen at init.  New wiring that a handle with work areas would not have been built for [an nnz above 64 x 2^dim] is
+ * SC_ERR_BAD_ARG naming the instance; a handle on the serial plan takes every shape and stays serial.
+ * CAPACITY: the handle's copy of the inputs is laid out again by init's rule, every distinct [pointer, size] once, inside the bytes
+ * reserved at init; with kept wiring the wiring's arrays stay where they are and the distinct f2 / f3 take the places the former ones had.
+ * A layout that does not fit is SC_ERR_BAD_ARG with both byte counts and "build a new handle".  A call ALWAYS fits if its pointers repeat
+ * in the same pattern as init's and its f1 is kept or has nnz[i] <= init's nnz[i] for every i.  Init reserves no slack for growth.
+ * ERRORS: every check the host can make runs before any HIP call; the lowest failing instance decides, errors start with "instance %u: "
+ * [init's own per-instance checks, a non-canonical g].  An out-of-range index in a device-resident list is found on the device, over the
+ * caller's arrays, before anything of the handle's is overwritten [SC_ERR_BAD_ARG "instance %u: f1 has an index out of range"].  ANY of
+ * these errors leaves the handle exactly where it was: a proof in progress continues with the same bits.  [A HIP error later in the call
+ * leaves the handle exhausted and its inputs undefined until the next successful call of this function.]
+ * SYNCHRONOUS: device inputs are read after a device-wide synchronise, as at init; nothing of the caller's is read after the call returns.
+ * Device arrays come in through ONE kernel launch for all of them [k_batch_gkr_restage], host arrays by init's copies.  Counted as plan
+ * batch.gkr_next_layer, once per successful call on a handle with work areas. */
+SC_API_GKRL int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null,
+                                        const uint64_t *nnz_or_null, const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
+                                        uint32_t flags);
 /* f4 -- the same two initialisations with f1's non-zeros SPREAD OVER SEVERAL GPUs (worth it from dim ~ 24).
  * Every rank passes a disjoint subset of f1's (index, value) pairs -- any partition -- and all of f3 / g.  A rank's scatter is a
  * partial sum of a_hg, so the ranks' dense tables are added with ONE table-sized integer all-reduce of the widened limbs

@@ -6,6 +6,7 @@
 //! | [`prover_init`], [`prove_round`]            | `IPForMLSumcheck::{prover_init, prove_round}` `src/ml_sumcheck/protocol/prover.rs:49,74` |
 //! | [`prove`], [`prove_as_subprotocol`]         | `MLSumcheck::{prove, prove_as_subprotocol}` `src/ml_sumcheck/mod.rs:42,50` |
 //! | [`gkr_prover_init_batch`], [`gkr_prove_round_batch`], [`gkr_finish_batch`] | (new) the rounds of many small `GKRRoundSumcheck::prove` under the caller's transcript (`rng: &mut impl FeedableRNG`), one call per round |
+//! | [`gkr_next_layer_batch`] | (new) the same handle onto the next layer's `f2`, `f3`, `g` (and `f1`) without a rebuild: one handle for the layers of a GKR prover |
 //! | [`prover_init_batch`], [`prove_round_batch`] | (new) `states.par_iter_mut().zip(msgs).map(prove_round)`: one round of many small provers in one call, the caller's transcript |
 //! | [`prove_batch`]                            | (new) `polys.par_iter().map(MLSumcheck::prove)`: many small instances of one structure in one call |
 //! | [`evaluate`]                                | `ListOfProductsOfPolynomials::evaluate` `src/ml_sumcheck/data_structures.rs:99` |
@@ -707,10 +708,58 @@ impl<F: Limbs4> HipGkrBatchProverState<F> {
         check(unsafe { sc_gkr_batch_prover_state(self.handle, i as u32, rand.as_mut_ptr() as *mut u64, &mut n_rand, core::ptr::null_mut(), core::ptr::null_mut()) });
         rand[..n_rand as usize].iter().map(|l| F::from_limbs(*l)).collect()
     }
-    /// rewind to round 0 over the inputs the handle holds (phase one's tables are not rebuilt)
+    /// rewind to round 0 over the inputs the handle holds (phase one's tables are not rebuilt); new inputs: [`gkr_next_layer_batch`]
     pub fn reset(&mut self) {
         check(unsafe { sc_gkr_batch_prover_reset(self.handle) });
     }
+}
+
+// An existing handle onto the next layer's inputs (`sc_gkr_layer_next_batch`): a private declaration behind the safe wrapper below.
+extern "C" {
+    fn sc_gkr_layer_next_batch(bp: *mut sc_gkr_batch_prover, f1_idx_or_null: *const *const u64, f1_vals_or_null: *const *const u64, nnz_or_null: *const u64,
+                               f2: *const *const u64, f3: *const *const u64, g: *const *const u64, flags: u32) -> c_int;
+}
+
+/// One instance of [`gkr_next_layer_batch`]: the next layer's values and point, and its wiring if it has wiring of its own.
+pub struct GkrNextLayerInstance<'a, F: Limbs4> {
+    /// `None` for every instance: the wiring the handle holds is kept; `Some` for every instance: new wiring
+    pub f1: Option<&'a SparseMultilinearExtension<F>>,
+    pub f2: &'a DenseMultilinearExtension<F>,
+    pub f3: &'a DenseMultilinearExtension<F>,
+    pub g: &'a [F],
+}
+
+/// The handle onto the next layer's inputs (`sc_gkr_layer_next_batch`): nothing is allocated, and afterwards the handle is at round 0 as
+/// [`gkr_prover_init_batch`] over these inputs would leave it -- same plan, same bits.  Callable in any state.  The inputs are copied; the
+/// copy fits whenever the arrays repeat in the pattern init's did and f1 is kept or has no more non-zeros per instance than it had there.
+pub fn gkr_next_layer_batch<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, layer: &[GkrNextLayerInstance<F>]) {
+    let (n, dim) = (state.n, state.dim);
+    assert_eq!(layer.len(), n, "one entry per instance of the handle");
+    let keep = layer.iter().all(|i| i.f1.is_none());
+    assert!(keep || layer.iter().all(|i| i.f1.is_some()), "new wiring for every instance, or for none");
+    let mut arrays = Vec::with_capacity(n);
+    let mut gls: Vec<Vec<[u64; 4]>> = Vec::with_capacity(n);
+    for inst in layer.iter() {
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        if let Some(f1) = inst.f1 {
+            assert_eq!(f1.num_vars, 3 * dim);
+            arrays.push(sparse_arrays(f1));
+        }
+        gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+    }
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let f2: Vec<*const u64> = layer.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = layer.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = gls.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let null = core::ptr::null();
+    check(unsafe {
+        sc_gkr_layer_next_batch(state.handle, if keep { null } else { idx.as_ptr() }, if keep { null } else { vals.as_ptr() },
+                                if keep { core::ptr::null() } else { nnz.as_ptr() }, f2.as_ptr(), f3.as_ptr(), g.as_ptr(), 0)
+    });
 }
 
 /// What [`gkr_finish_batch`] returns per instance: the points and the subclaim's oracle values, at no extra pass over the tables.

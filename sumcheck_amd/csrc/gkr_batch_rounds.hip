@@ -20,6 +20,9 @@
 //                               sc_prove_round, the phase change and finish go through sc_prover_bind_final: dim > 9 without the key,
 //                               dim > 16, nnz beyond 64 x 2^dim, policy "batch" = 0.
 // The handle copies every input once per distinct pointer (phase two needs f1 and f3 again): nothing of the caller's is read after init.
+// sc_gkr_layer_next_batch (at the end) puts a handle onto the next layer's inputs inside what init allocated.
+#include <set>
+
 #include "batch_slices.hpp"
 #include "prover_internal.hpp"
 
@@ -35,13 +38,19 @@ struct sc_gkr_batch_prover {
     std::vector<sch::Fr> g;                        // n x dim
     std::vector<scd::GkrBatchInst> rec;            // the instances' arrays in the handle's copy (d_in), g in d_up
     hipStream_t stream = nullptr;
-    char *d_buf = nullptr; // device, ONE allocation: area A | area B (work areas) | matrices | records | index flags | g | challenges | messages | f2(u) | export area | inputs | serial tables, or (slices) cells | partials
+    char *d_buf = nullptr; // device, ONE allocation: area A | area B (work areas) | matrices | records | index flags | g | challenges | messages | f2(u) | export area | a layer's staging image | inputs | serial tables, or (slices) cells | partials
     char *d_in = nullptr;  // (inside d_buf) the inputs, every distinct array once
     char *d_cells = nullptr, *d_part = nullptr; // (inside d_buf, slices) the wide cells both phases share, n x 64 B x 2^dim; the sliced rounds' partials
     size_t cells_bytes = 0;
-    char *h_pin = nullptr; // pinned: matrices | ... | export area
+    char *h_pin = nullptr; // pinned: matrices | ... | export area | a layer's staging image
     size_t work_bytes = 0, w_off = 0, rec_off = 0, flag_off = 0, g_off = 0, u_off = 0, msg_off = 0, f2u_off = 0, exp_off = 0, pin_bytes = 0; // (offsets into h_pin; d_buf: + 2 work_bytes)
     SharedMeta s; // one product of two tables with a coefficient of one: both phases (start_phase{1,2}_sumcheck, mod.rs:45-54, 66-82)
+    // ---- sc_gkr_layer_next_batch ----
+    bool dev_in = false;                   // SC_TABLES_ON_DEVICE at init: every later layer's arrays are where init's were
+    int64_t pol_batch = 0, pol_slices = 0; // the policies the plan was chosen under
+    size_t in_cap = 0, in_used = 0;        // d_in: the bytes reserved at init (never more), the bytes of the layout in force
+    std::vector<size_t> dense_slots;       // (offsets into d_in) the places of the distinct f2 / f3 arrays that no wiring array shares: where a layer that keeps the wiring puts its own
+    size_t nl_flag_off = 0, nl_chk_off = 0, nl_rec_off = 0, nl_g_off = 0, nl_item_off = 0; // (offsets into h_pin) the staging image of a layer: index flags | records over the caller's arrays | records | g | restage items
     // ---- batch.gkr_rounds_serial ----
     std::vector<sc_prover *> p1, p2;
     char *d_tabs = nullptr; // (inside d_buf) per instance h_g | f1(g, u, .) | f2(u) f3, 2^dim elements each
@@ -141,6 +150,45 @@ int slices_phase(sc_gkr_batch_prover *bp, int phase) {
     return SC_OK;
 }
 
+// phase one's tables of a handle with work areas out of the records and arrays on the device, on the handle's stream (init, and every later layer)
+int areas_phase_one(sc_gkr_batch_prover *bp) {
+    if (bp->plan == scd::kGbrSlices) return slices_phase(bp, 1);
+    if (bp->plan != scd::kGbrOneBlock) return SC_OK;
+    scd::BatchGkrPhaseArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.inst = reinterpret_cast<const scd::GkrBatchInst *>(bp->d_buf + 2 * bp->work_bytes + bp->rec_off);
+    A.work_a = reinterpret_cast<int32_t *>(bp->d_buf);
+    A.n = bp->n;
+    A.dim = bp->dim;
+    HIP_TRY(scd::launch_batch_gkr_phase(1, A, bp->stream));
+    return SC_OK;
+}
+
+// the serial plan's phase one: per instance h_g by sc_gkr_prove's route and a prover over (h_g, f2), or the old prover rewound over them
+int serial_phase_one(sc_gkr_batch_prover *bp) {
+    for (uint32_t i = 0; i < bp->n; ++i) {
+        const scd::GkrBatchInst &I = bp->rec[i];
+        int rc = sc_internal_gkr_dense_table(1, I.idx, I.vals, bp->nnz[i], bp->dim, I.f3, bp->g[(size_t)i * bp->dim].l, nullptr, serial_table(bp, i, 0)); // mod.rs:30-38
+        if (rc == SC_OK) rc = serial_prover(bp, &bp->p1[i], serial_table(bp, i, 0), I.f2);
+        if (rc) return prefix_instance(rc, i);
+    }
+    return SC_OK;
+}
+
+// the places of a layout's distinct f2 / f3 arrays that no wiring array shares (offs: per instance idx, vals, f2, f3), in the layout's order
+std::vector<size_t> dense_slots_of(const std::vector<size_t> &offs, const std::vector<uint64_t> &nnz) {
+    std::set<size_t> wiring, dense;
+    for (size_t i = 0; i < nnz.size(); ++i)
+        if (nnz[i]) {
+            wiring.insert(offs[4 * i + 0]);
+            wiring.insert(offs[4 * i + 1]);
+        }
+    for (size_t i = 0; i < nnz.size(); ++i)
+        for (int k = 2; k < 4; ++k)
+            if (!wiring.count(offs[4 * i + k])) dense.insert(offs[4 * i + k]);
+    return std::vector<size_t>(dense.begin(), dense.end());
+}
+
 } // namespace
 
 extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2,
@@ -173,7 +221,9 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
         PhaseDesc pd(dim, 0);
         build_shared(&pd.d, bp->s);
         bp->s.unit.push_back(unit_matrix(2, 3));
-        bp->plan = scd::gkr_bs_plan(n, dim, nnz_max, bp->s.n_combos, scd::policy(scd::kPolBatch), scd::policy(scd::kPolBatchSlices));
+        bp->pol_batch = scd::policy(scd::kPolBatch);
+        bp->pol_slices = scd::policy(scd::kPolBatchSlices);
+        bp->plan = scd::gkr_bs_plan(n, dim, nnz_max, bp->s.n_combos, bp->pol_batch, bp->pol_slices);
         const bool areas = bp->work_areas(), slices = bp->plan == scd::kGbrSlices;
         // ---- the handle's copy of the inputs: every distinct (pointer, size) once ----
         StageMap st; // (offsets into d_in)
@@ -186,6 +236,9 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             offs[4 * (size_t)i + 3] = st.add(f3[i], N * 32);
         }
         const size_t in_bytes = st.bytes;
+        bp->in_cap = bp->in_used = in_bytes;
+        bp->dense_slots = dense_slots_of(offs, bp->nnz);
+        bp->dev_in = dev_in;
         bp->work_bytes = areas ? round_up((size_t)n * 2 * 2 * (scd::kBatchRoundSlotBytes << dim), 256) : 0;
         bp->w_off = 0;
         bp->rec_off = bp->w_off + round_up((size_t)bp->s.w_elems * 32, 256);
@@ -195,7 +248,12 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
         bp->msg_off = bp->u_off + round_up((size_t)2 * dim * n * 32, 256);
         bp->f2u_off = bp->msg_off + round_up((size_t)n * 3 * 32, 256);
         bp->exp_off = bp->f2u_off + round_up((size_t)n * 32, 256);
-        bp->pin_bytes = bp->exp_off + round_up(std::max(2 * N * 32, (size_t)n * 2 * 32), 256); // one instance's tables (state), or every instance's final values
+        bp->nl_flag_off = bp->exp_off + round_up(std::max(2 * N * 32, (size_t)n * 2 * 32), 256); // one instance's tables (state), or every instance's final values
+        bp->nl_chk_off = bp->nl_flag_off + round_up((size_t)n * 4, 256);
+        bp->nl_rec_off = bp->nl_chk_off + round_up((size_t)n * sizeof(scd::GkrBatchInst), 256);
+        bp->nl_g_off = bp->nl_rec_off + round_up((size_t)n * sizeof(scd::GkrBatchInst), 256);
+        bp->nl_item_off = bp->nl_g_off + round_up((size_t)n * dim * 32, 256);
+        bp->pin_bytes = bp->nl_item_off + round_up(((size_t)n * 4 + 2) * sizeof(scd::GkrRestageItem), 256); // (every array of every instance, the records, g)
         {
             DeviceGate gate_(bp->device);
             HIP_TRY(hipSetDevice(bp->device));
@@ -236,30 +294,14 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             // device-resident lists: an index out of range is found here, in front of any kernel that follows the indices (host lists: checked above)
             if (dev_in)
                 if (int rc = gkr_check_idx_on_device(d_rec, n, dim, bp->h_pin, d_up, bp->flag_off, bp->stream)) return rc;
-            if (slices) {
-                if (int rc = slices_phase(bp, 1)) return rc;
-            } else if (areas) {
-                scd::BatchGkrPhaseArgs A;
-                std::memset(&A, 0, sizeof(A));
-                A.inst = d_rec;
-                A.work_a = reinterpret_cast<int32_t *>(bp->d_buf);
-                A.n = n;
-                A.dim = dim;
-                HIP_TRY(scd::launch_batch_gkr_phase(1, A, bp->stream));
-            }
+            if (int rc = areas_phase_one(bp)) return rc;
             HIP_TRY(hipStreamSynchronize(bp->stream)); // nothing of the caller's is read after the call returns
         }
         if (areas) return SC_OK;
         bp->p1.assign(n, nullptr);
         bp->p2.assign(n, nullptr);
         bp->f2u.resize(n);
-        for (uint32_t i = 0; i < n; ++i) {
-            const scd::GkrBatchInst &I = bp->rec[i];
-            int rc = sc_internal_gkr_dense_table(1, I.idx, I.vals, nnz[i], dim, I.f3, bp->g[(size_t)i * dim].l, nullptr, serial_table(bp, i, 0)); // mod.rs:30-38
-            if (rc == SC_OK) rc = serial_prover(bp, &bp->p1[i], serial_table(bp, i, 0), I.f2);
-            if (rc) return prefix_instance(rc, i);
-        }
-        return SC_OK;
+        return serial_phase_one(bp);
     };
     if (int rc = build()) {
         const std::string why = sc_last_error(); // (the frees below may run library calls of their own)
@@ -411,5 +453,170 @@ extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
     bp->round = 0;
     bp->exhausted = false;
     bp->randomness.clear();
+    return SC_OK;
+}
+
+// ---- sc_gkr_layer_next_batch: the handle onto the next layer's inputs, inside what init allocated ------------------------------------
+// A GKR prover runs one round sumcheck per layer under one transcript, and every layer has new inputs: its g is the previous layer's point,
+// its f2 and f3 are the next layer's values, often it has wiring of its own.  The input area is laid out again by init's rule (a layer that
+// keeps the wiring leaves the wiring's arrays where they are and gives its distinct f2 / f3 the places the former ones had), phase one's
+// tables are rebuilt, and the handle is at round 0 as a fresh init over these inputs would leave it -- same plan, same bits.
+//   host arrays    one copy per distinct array into the handle's copy (init's staging), one upload of records and g;
+//   device arrays  ONE upload of a staging image -- index flags | records over the CALLER's arrays | records | g | restage items --, the
+//                  index check over the caller's arrays where the wiring is new (the last thing that can refuse: up to here nothing of the
+//                  handle's has been written), then ONE launch of k_batch_gkr_restage that brings in every array, the records and g;
+// then what init runs (k_batch_gkr_phase<1>, or the sliced plan's memset + terms + fold; serial plan: the per-instance loop, the provers
+// rewound over the new tables) and one synchronisation.  A HIP error past the index check leaves the handle exhausted with undefined inputs:
+// the next successful call of this function, or free.
+extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null, const uint64_t *nnz_or_null,
+                                       const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags) {
+    // ---- everything the host can check, before any HIP call and before the first change to the handle ----
+    if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (!f2 || !f3 || !g) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    const bool new_f1 = f1_idx_or_null && f1_vals_or_null && nnz_or_null;
+    if (!new_f1 && (f1_idx_or_null || f1_vals_or_null || nnz_or_null))
+        return sc_internal_fail(SC_ERR_BAD_ARG, "f1_idx, f1_vals and nnz come together (new wiring) or are all NULL (the handle's wiring is kept)");
+    const bool dev_in = flags & SC_TABLES_ON_DEVICE;
+    if (dev_in != bp->dev_in) return sc_internal_fail(SC_ERR_BAD_ARG, "flags: the handle was built over %s arrays, a later layer's are where init's were", bp->dev_in ? "device" : "host");
+    const uint32_t n = bp->n, dim = bp->dim;
+    const size_t N = (size_t)1 << dim, slot = round_up(N * 32, 256);
+    static const char *const kPlanOf[3] = {"batch.gkr_rounds_serial", "batch.gkr_rounds_one_block", "batch.gkr_rounds_slices"};
+    std::vector<const uint64_t *> none;
+    std::vector<uint64_t> nnz = bp->nnz;
+    if (!new_f1) none.assign(n, nullptr);
+    else nnz.assign(nnz_or_null, nnz_or_null + n);
+    const std::vector<uint64_t> zero(new_f1 ? 0 : n, 0); // (kept wiring: nothing of f1 to check)
+    const GkrBatchIn in = {n, dim, new_f1 ? f1_idx_or_null : none.data(), new_f1 ? f1_vals_or_null : none.data(), new_f1 ? nnz_or_null : zero.data(), f2, f3, g, dev_in};
+    uint64_t nnz_max = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (int rc = gkr_check_instance(in, i, nullptr)) return rc;
+        // the plan stays the one chosen at init (the serial plan takes every shape)
+        if (new_f1 && bp->work_areas()) {
+            const int would = scd::gkr_bs_plan(n, dim, nnz[i], bp->s.n_combos, bp->pol_batch, bp->pol_slices);
+            if (would != bp->plan)
+                return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: nnz %llu (the plan's limit: 64 x 2^dim = %llu) would take plan %s, the handle was built for %s: build a new handle", i,
+                                        (unsigned long long)nnz[i], (unsigned long long)(scd::kGkrBatchMaxNnzPerCell << dim), kPlanOf[would], kPlanOf[bp->plan]);
+        }
+        nnz_max = std::max(nnz_max, nnz[i]);
+    }
+    // ---- the input area again: every distinct (pointer, size) once, inside the bytes reserved at init ----
+    std::vector<size_t> offs((size_t)n * 4, 0), slots;
+    std::vector<StageMap::Item> copy; // what has to be brought in (offsets into d_in)
+    size_t used = 0;
+    if (new_f1) {
+        StageMap st;
+        st.align = 256;
+        for (uint32_t i = 0; i < n; ++i) {
+            offs[4 * (size_t)i + 0] = nnz[i] ? st.add(f1_idx_or_null[i], (size_t)nnz[i] * 8) : 0;
+            offs[4 * (size_t)i + 1] = nnz[i] ? st.add(f1_vals_or_null[i], (size_t)nnz[i] * 32) : 0;
+            offs[4 * (size_t)i + 2] = st.add(f2[i], N * 32);
+            offs[4 * (size_t)i + 3] = st.add(f3[i], N * 32);
+        }
+        copy = st.items;
+        used = st.bytes;
+        slots = dense_slots_of(offs, nnz);
+    } else {
+        slots = bp->dense_slots;
+        used = bp->in_used;
+        std::map<const void *, size_t> where;
+        size_t taken = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            offs[4 * (size_t)i + 0] = reinterpret_cast<const char *>(bp->rec[i].idx) - bp->d_in;
+            offs[4 * (size_t)i + 1] = reinterpret_cast<const char *>(bp->rec[i].vals) - bp->d_in;
+            for (int k = 2; k < 4; ++k) {
+                const void *src = (k == 2 ? f2 : f3)[i];
+                auto it = where.find(src);
+                if (it == where.end()) {
+                    if (taken == slots.size()) { // more distinct arrays than the layout in force has places for: behind it, while the reserve lasts
+                        slots.push_back(used);
+                        used += slot;
+                    }
+                    it = where.emplace(src, slots[taken++]).first;
+                    copy.push_back({src, N * 32, it->second});
+                }
+                offs[4 * (size_t)i + k] = it->second;
+            }
+        }
+    }
+    if (used > bp->in_cap)
+        return sc_internal_fail(SC_ERR_BAD_ARG, "the layer's distinct arrays take %zu bytes of the handle's copy, init reserved %zu: build a new handle", used, bp->in_cap);
+    char *const d_up = bp->d_buf + 2 * bp->work_bytes;
+    std::vector<scd::GkrBatchInst> rec(n), chk(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        scd::GkrBatchInst &r = rec[i], &c = chk[i];
+        r.nnz = c.nnz = nnz[i];
+        r.idx = reinterpret_cast<const uint64_t *>(bp->d_in + offs[4 * (size_t)i + 0]);
+        r.vals = reinterpret_cast<const uint4 *>(bp->d_in + offs[4 * (size_t)i + 1]);
+        r.f2 = reinterpret_cast<const uint4 *>(bp->d_in + offs[4 * (size_t)i + 2]);
+        r.f3 = reinterpret_cast<const uint4 *>(bp->d_in + offs[4 * (size_t)i + 3]);
+        r.g = c.g = reinterpret_cast<const uint4 *>(d_up + bp->g_off + (size_t)i * dim * 32);
+        c.idx = new_f1 ? f1_idx_or_null[i] : r.idx;
+        c.vals = new_f1 ? reinterpret_cast<const uint4 *>(f1_vals_or_null[i]) : r.vals;
+        c.f2 = reinterpret_cast<const uint4 *>(f2[i]);
+        c.f3 = reinterpret_cast<const uint4 *>(f3[i]);
+    }
+    const size_t rec_bytes = (size_t)n * sizeof(scd::GkrBatchInst), g_bytes = (size_t)n * dim * 32;
+    size_t n_items = 0;
+    uint64_t blocks = 0;
+    auto upload_and_check = [&]() -> int { // device arrays: the staging image, the index check
+        DeviceGate gate_(bp->device);
+        HIP_TRY(hipSetDevice(bp->device));
+        HIP_TRY(hipDeviceSynchronize()); // the inputs' producers are waited for, as at init
+        std::memset(bp->h_pin + bp->nl_flag_off, 0, bp->nl_chk_off - bp->nl_flag_off);
+        std::memcpy(bp->h_pin + bp->nl_chk_off, chk.data(), rec_bytes);
+        std::memcpy(bp->h_pin + bp->nl_rec_off, rec.data(), rec_bytes);
+        for (uint32_t i = 0; i < n; ++i) std::memcpy(bp->h_pin + bp->nl_g_off + (size_t)i * dim * 32, g[i], (size_t)dim * 32);
+        scd::GkrRestageItem *items = reinterpret_cast<scd::GkrRestageItem *>(bp->h_pin + bp->nl_item_off);
+        auto item = [&](const void *src, size_t dst_off, size_t bytes) {
+            items[n_items++] = {src, dst_off, bytes, blocks};
+            blocks += (bytes + scd::kGkrRestageChunk - 1) / scd::kGkrRestageChunk;
+        };
+        for (const StageMap::Item &it : copy) item(it.src, (size_t)(bp->d_in - bp->d_buf) + it.off, it.bytes);
+        item(d_up + bp->nl_rec_off, 2 * bp->work_bytes + bp->rec_off, rec_bytes);
+        item(d_up + bp->nl_g_off, 2 * bp->work_bytes + bp->g_off, g_bytes);
+        HIP_TRY(hipMemcpyAsync(d_up + bp->nl_flag_off, bp->h_pin + bp->nl_flag_off, bp->nl_item_off + n_items * sizeof(scd::GkrRestageItem) - bp->nl_flag_off, hipMemcpyHostToDevice, bp->stream));
+        // new device-resident wiring: an index out of range is found here, over the caller's arrays -- nothing of the handle's has been written
+        if (new_f1)
+            if (int rc = gkr_check_idx_on_device(reinterpret_cast<const scd::GkrBatchInst *>(d_up + bp->nl_chk_off), n, dim, bp->h_pin, d_up, bp->nl_flag_off, bp->stream)) return rc;
+        return SC_OK;
+    };
+    if (dev_in)
+        if (int rc = upload_and_check()) return rc;
+    // ---- from here on the handle is the new layer's ----
+    bp->round = 0;
+    bp->exhausted = false;
+    bp->randomness.clear();
+    bp->nnz = nnz;
+    bp->nnz_max = nnz_max;
+    bp->rec = rec;
+    for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g[(size_t)i * dim], g[i], (size_t)dim * 32);
+    bp->dense_slots = slots;
+    bp->in_used = used;
+    std::memcpy(bp->h_pin + bp->rec_off, rec.data(), rec_bytes);
+    std::memcpy(bp->h_pin + bp->g_off, bp->g.data(), g_bytes);
+    auto stage_on_stream = [&]() -> int {
+        if (dev_in) {
+            HIP_TRY(scd::launch_batch_gkr_restage(reinterpret_cast<const scd::GkrRestageItem *>(d_up + bp->nl_item_off), (uint32_t)n_items, blocks, bp->d_buf, bp->stream));
+        } else {
+            for (const StageMap::Item &it : copy) HIP_TRY(hipMemcpyAsync(bp->d_in + it.off, it.src, it.bytes, hipMemcpyHostToDevice, bp->stream));
+            HIP_TRY(hipMemcpyAsync(d_up + bp->rec_off, bp->h_pin + bp->rec_off, bp->u_off - bp->rec_off, hipMemcpyHostToDevice, bp->stream));
+        }
+        if (int rc = areas_phase_one(bp)) return rc;
+        HIP_TRY(hipStreamSynchronize(bp->stream)); // nothing of the caller's is read after the call returns
+        return SC_OK;
+    };
+    auto stage = [&]() -> int {
+        {
+            DeviceGate gate_(bp->device);
+            HIP_TRY(hipSetDevice(bp->device));
+            if (int rc = stage_on_stream()) return rc;
+        }
+        return bp->work_areas() ? SC_OK : serial_phase_one(bp);
+    };
+    if (int rc = stage()) {
+        bp->exhausted = true;
+        return rc;
+    }
+    if (bp->work_areas()) scd::plan_hit(scd::kPlanBatchGkrNextLayer);
     return SC_OK;
 }

@@ -370,6 +370,18 @@ struct BatchGkrPhaseArgs {
     uint32_t n, dim;
 };
 hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream);
+// sc_gkr_layer_next_batch: the arrays a handle takes from the caller's device memory, all in ONE launch (k_batch_gkr_restage) out of a
+// device table of items.  An item is spread over ceil(bytes / kGkrRestageChunk) blocks, the first of them first_block: the items' first
+// blocks ascend from 0 and `blocks` is their total.  Sizes are multiples of 8; 16 bytes per lane where an item's source and destination are
+// both 16-byte aligned, 8 otherwise.  The caller answers for the destinations: inside its allocation, disjoint, no source among them.
+constexpr uint64_t kGkrRestageChunk = 16384; // bytes a block moves: four 16-byte accesses per lane
+struct GkrRestageItem {
+    const void *src;      // device memory, 8-byte aligned
+    uint64_t dst_off;     // bytes from dst_base, a multiple of 8
+    uint64_t bytes;       // a multiple of 8, not 0
+    uint64_t first_block;
+};
+hipError_t launch_batch_gkr_restage(const GkrRestageItem *items, uint32_t n_items, uint64_t blocks, char *dst_base, hipStream_t stream);
 // The same two initialisations beyond one block's LDS (kernels_batch_gkr_round_slices.hip; the envelope and the grids: batch_slices.hpp,
 // gkr_bs_plan), dim 10 .. 16, as two plain launches each over wide cells in DEVICE memory (n x 8 uint64 lanes x 2^dim, zeroed by the caller
 // on the same stream in front of every phase):
@@ -452,6 +464,7 @@ enum Plan {
     kPlanShardedGatherTail,   // bind + all-gather + replicated tail
     kPlanBatchRoundsSlices,   // sc_batch_prove_round: k_batch_round_slices + k_batch_round_fin, several blocks per instance, two launches for a round of the whole batch (the rounds whose tables do not fit one block; policy "batch_slices" = 1)
     kPlanGkrBucketedGrouped,  // GKR initialisation: buckets of an index-ordered list (k_bucket_bounds)
+    kPlanBatchGkrNextLayer,   // sc_gkr_layer_next_batch on a handle with work areas (batch.gkr_rounds_one_block / _slices): new inputs into the handle's own copy (k_batch_gkr_restage for device arrays) and phase one's tables rebuilt, nothing allocated; counted once per successful call
     kPlanGkrBucketedCounted,  // ... counting sort into buckets
     kPlanBatchGkrRoundsSlices, // sc_gkr_batch_prove_round on a handle of dim 10 .. 16 built with policy "batch_slices" = 1: areas filled by k_batch_gkr_terms / k_batch_gkr_fold, the rounds k_batch_round_slices + k_batch_round_fin while the tables do not fit one block, then k_batch_round; counted once per round call
     kPlanGkrListForm,         // ... sort + merge + scatter

@@ -15,6 +15,7 @@
 // Every index is masked to dim bits per component before it addresses LDS or f3 (bg_accumulate); an index with a bit at or above 3 dim
 // is an argument error that k_batch_gkr_idx_range reports in front of the first launch that follows the indices.
 // LDS: eq(g, .) | eq(u, .) (32 B per cell) | the accumulator (64 B per cell, also bg_build_eq's scratch): 128 B x 2^dim; no tables.
+// Behind them k_batch_gkr_restage: the copy kernel that brings the next layer's device arrays into a handle (sc_gkr_layer_next_batch).
 #include "batch_round.hpp"
 
 namespace scd {
@@ -58,6 +59,46 @@ hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipS
     const size_t lds = (size_t)128 << args.dim; // (at most 64 KB: within a launch's default limit)
     if (phase == 1) hipLaunchKernelGGL(k_batch_gkr_phase<1>, dim3(args.n), dim3(kTsBlock), lds, stream, args);
     else hipLaunchKernelGGL(k_batch_gkr_phase<2>, dim3(args.n), dim3(kTsBlock), lds, stream, args);
+    return hipGetLastError();
+}
+
+// k_batch_gkr_restage (sc_gkr_layer_next_batch): every array a handle has to take from the caller's DEVICE memory, in one launch.  Block b
+// serves chunk b - first_block of the last item whose first_block is <= b (a uniform binary search over the table: the items' first blocks
+// ascend from 0), kGkrRestageChunk bytes at the most, so a large table is many blocks' work.  Every size is a multiple of 8 and a caller's
+// uint64_t * is only 8-byte aligned: an item whose source and destination are both 16-byte aligned moves 16 bytes per lane (a chunk starts
+// at a multiple of 16) and its last 8 bytes, where its size is an odd multiple of 8, by one lane; every other item moves 8 bytes per lane.
+// Plain loads and stores: no atomics, no waits, no LDS.  The host side lays the destinations out: they do not overlap each other or a source.
+__global__ __launch_bounds__(kTsBlock) void k_batch_gkr_restage(const GkrRestageItem *__restrict__ items, const uint32_t n_items, char *__restrict__ dst_base) {
+    const uint64_t b = blockIdx.x;
+    uint32_t lo = 0, hi = n_items; // items[lo].first_block <= b < items[hi].first_block (hi == n_items: the grid's end)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (items[mid].first_block <= b) lo = mid;
+        else hi = mid;
+    }
+    const GkrRestageItem it = items[lo];
+    const uint64_t begin = (b - it.first_block) * kGkrRestageChunk;
+    if (begin >= it.bytes) return;
+    const uint64_t len = it.bytes - begin < kGkrRestageChunk ? it.bytes - begin : kGkrRestageChunk;
+    const char *const src = static_cast<const char *>(it.src) + begin;
+    char *const dst = dst_base + it.dst_off + begin;
+    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
+        const uint4 *const s = reinterpret_cast<const uint4 *>(src);
+        uint4 *const d = reinterpret_cast<uint4 *>(dst);
+        const uint32_t n16 = (uint32_t)(len >> 4);
+        for (uint32_t k = threadIdx.x; k < n16; k += kTsBlock) d[k] = s[k];
+        if ((len & 8u) && threadIdx.x == 0) *reinterpret_cast<uint64_t *>(dst + ((size_t)n16 << 4)) = *reinterpret_cast<const uint64_t *>(src + ((size_t)n16 << 4));
+    } else {
+        const uint64_t *const s = reinterpret_cast<const uint64_t *>(src);
+        uint64_t *const d = reinterpret_cast<uint64_t *>(dst);
+        const uint32_t n8 = (uint32_t)(len >> 3);
+        for (uint32_t k = threadIdx.x; k < n8; k += kTsBlock) d[k] = s[k];
+    }
+}
+
+hipError_t launch_batch_gkr_restage(const GkrRestageItem *items, uint32_t n_items, uint64_t blocks, char *dst_base, hipStream_t stream) {
+    if (!items || !dst_base || n_items == 0 || blocks == 0 || blocks >= (1ULL << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_batch_gkr_restage, dim3((uint32_t)blocks), dim3(kTsBlock), 0, stream, items, n_items, dst_base);
     return hipGetLastError();
 }
 

@@ -407,6 +407,34 @@ class GKRBatchProverState:
     def reset(self) -> None:
         check(lib().sc_gkr_batch_prover_reset(self._h))
 
+    def next_layer(self, f2s, f3s, gs, f1s=None) -> None:
+        """The handle onto the next layer's inputs (sc_gkr_layer_next_batch): nothing is allocated, and afterwards the handle is at round 0
+        exactly as prover_init_batch over these inputs would leave it -- same plan, same bits.  f1s=None keeps the wiring the handle
+        holds.  Inputs are where prover_init_batch's were (all on the host, or all on the GPU) and are copied: nothing is read after this
+        returns.  Callable in any state; an argument error leaves the handle where it was.  The copy fits whenever the objects repeat in
+        the pattern prover_init_batch's did and f1 is kept or has no more non-zeros per instance than it had there."""
+        n, dim = self.n, self.dim
+        assert len(f2s) == n and len(f3s) == n and len(gs) == n and (f1s is None or len(f1s) == n), "one f2, f3 and g (and f1) per instance"
+        ons = [m.on_device for m in list(f1s or []) + list(f2s) + list(f3s)]
+        dev = all(ons)
+        assert dev or not any(ons), "mixing host and device inputs is not supported"
+        g_arr = []
+        for i in range(n):
+            assert f2s[i].num_vars == dim and f3s[i].num_vars == dim and (f1s is None or f1s[i].num_vars == 3 * dim), f"instance {i}: the handle's dim is {dim}"
+            g_arr.append(_np64(gs[i]).reshape(-1, 4))
+            assert g_arr[i].shape[0] == dim
+        if dev:
+            import torch
+            torch.cuda.current_stream(f2s[0].evaluations.device).synchronize()  # the library works on its own stream
+
+        def ptrs(vals):
+            return (C.c_void_p * n)(*[C.cast(v, C.c_void_p) for v in vals])
+
+        f1p = [f._ptrs() for f in f1s] if f1s is not None else None
+        check(lib().sc_gkr_layer_next_batch(self._h, ptrs([p[0] for p in f1p]) if f1p else None, ptrs([p[1] for p in f1p]) if f1p else None,
+                                            (C.c_uint64 * n)(*[f.nnz for f in f1s]) if f1p else None, ptrs([_dense_ptr(m) for m in f2s]),
+                                            ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), SC_TABLES_ON_DEVICE if dev else 0))
+
     def close(self) -> None:
         if self._h:
             lib().sc_gkr_batch_prover_free(self._h)
