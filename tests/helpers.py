@@ -213,3 +213,82 @@ def mont_challenges(r_std) -> np.ndarray:
     """standard-form challenges -> (len, 4) as the API takes them"""
     from tests import fe_model as fm
     return np.stack([raw_limbs(fm.to_mont(r)) for r in r_std])
+
+
+# ---- thread ranks on one GPU (tests/test_gpu_sharded_edges.py) ---------------------------------------------------------------------------------
+RANKS_BROKEN = []  # why no further rank may start in this process: a rank thread that never came back, or a rank that met a HIP error
+
+
+def run_ranks(G: int, work, timeout: float = 150.0, on_error=None):
+    """work(rank) on one thread per rank -> [its results].  Every thread is joined against ONE deadline; afterwards no thread may be alive
+    and no rank may have raised.  A rank that hangs or meets a HIP error ends every later run_ranks of the process before it starts a
+    thread: nothing more goes to a GPU that may be in a bad state.  on_error(): called by a failing rank, to let its peers out of an
+    exchange they would otherwise wait in."""
+    import threading
+    import time
+    import traceback
+    import pytest
+    if RANKS_BROKEN:
+        pytest.fail(f"not started: {RANKS_BROKEN[0]}")
+    out = [None] * G
+
+    def body(rank):
+        try:
+            out[rank] = ("ok", work(rank))
+        except BaseException as e:  # noqa: BLE001
+            out[rank] = ("error", f"rank {rank}: {e}\n{traceback.format_exc()}")
+            if on_error is not None:
+                on_error()
+
+    ts = [threading.Thread(target=body, args=(r,), daemon=True) for r in range(G)]
+    for t in ts:
+        t.start()
+    deadline = time.monotonic() + timeout
+    for t in ts:
+        t.join(timeout=max(0.0, deadline - time.monotonic()))
+    alive = [r for r, t in enumerate(ts) if t.is_alive()]
+    if alive:
+        RANKS_BROKEN.append(f"ranks {alive} of an earlier test were still running after {timeout:.0f} s")
+    errors = [o[1] for o in out if o is not None and o[0] == "error"]
+    if any("[sc_status 6]" in e for e in errors):  # SC_ERR_HIP
+        RANKS_BROKEN.append("a rank of an earlier test met a HIP error: " + errors[0].splitlines()[0])
+    assert not alive, f"ranks {alive} did not finish within {timeout:.0f} s"
+    assert not errors, "\n".join(errors)
+    assert all(o is not None for o in out)
+    return [o[1] for o in out]
+
+
+class RecordingExchange:
+    """sharded.ThreadExchange's in-process host transport with every call written down: allreduce_words[rank] and allgather_bytes[rank] list
+    the sizes of that rank's calls, in order.  (The proof's bits do not depend on where a sharded proof stops sharding; the calls do.)"""
+
+    def __init__(self, world: int):
+        from sumcheck_amd import sharded
+        self.world = world
+        self._ex = sharded.ThreadExchange(world)
+        self.clear()
+
+    def clear(self):
+        self.allreduce_words = [[] for _ in range(self.world)]
+        self.allgather_bytes = [[] for _ in range(self.world)]
+
+    def abort(self):
+        """a rank has failed: its peers leave the barrier at once instead of waiting out its timeout"""
+        self._ex._bar.abort()
+
+    def comm(self, rank: int):
+        from sumcheck_amd import sharded
+        base = self._ex
+
+        def allreduce(a):
+            self.allreduce_words[rank].append(int(a.shape[0]))
+            tot = np.zeros_like(a)
+            for x in base._exchange(rank, a):
+                tot += x
+            return tot
+
+        def allgather(b):
+            self.allgather_bytes[rank].append(int(b.shape[0]))
+            return np.concatenate(base._exchange(rank, b))
+
+        return sharded.HostComm(rank, self.world, allreduce, allgather)

@@ -53,7 +53,7 @@ def _thread_rank(rank, G, nv, shapes, tabs, coefs, make_comm, device, out, n_pro
 
 @pytest.mark.parametrize("G,nv,nt,shapes", [
     (2, 13, 4, [[0, 1, 2], [3, 3], [1]]),
-    (4, 19, 10, [[0, 1, 2, 3], [4, 5, 6], [7, 8], [9]]),   # config-3 shape; 2^17 entries per shard: no big rounds
+    (4, 19, 10, [[0, 1, 2, 3], [4, 5, 6], [7, 8], [9]]),   # config-3 shape; 2^17 entries per shard: two big rounds (2^16 and 2^15 pairs > kSmallRoundPairs = 2^14)
     (2, 20, 3, [[0, 1, 2]]),                               # config-4 shape; 2^19 per shard: two big rounds (merged kernel, F29) per shard
     (8, 6, 2, [[0, 1], [1]]),                              # tail as long as the local part
 ])
