@@ -636,6 +636,36 @@ struct GKRRoundSumcheckSubClaim {
         for (size_t i = 0; i < subclaims.size(); ++i) ok[i] = ev[i][3] == subclaims[i].expected_evaluation;
         return ok;
     }
+    // ... of n subclaims of rounds proved in TWO-POINT form (GKRRoundSumcheck::prover_init_batch with g2s and coeffs), from existing calls
+    // only: evaluate_subclaims_batch once over the gs and once over the g2s, then (alpha f1(g,u,v) + beta f1(g2,u,v)) f2(u) f3(v) by
+    // sc_fr_elementwise.  coeffs[i]: (alpha, beta)
+    static std::vector<bool> verify_subclaim_two_point_batch(const std::vector<GKRRoundSumcheckSubClaim> &subclaims, const std::vector<const SparseMultilinearExtension *> &f1s,
+                                                             const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s,
+                                                             const std::vector<std::vector<Fr>> &gs, const std::vector<std::vector<Fr>> &g2s, const std::vector<std::array<Fr, 2>> &coeffs) {
+        const size_t n = subclaims.size();
+        if (f1s.size() != n || g2s.size() != n || coeffs.size() != n) throw Panic(SC_ERR_BAD_ARG, "one f1, f2, f3, g, g2 and (alpha, beta) per subclaim");
+        std::vector<std::vector<Fr>> uv;
+        for (const GKRRoundSumcheckSubClaim &c : subclaims) {
+            uv.push_back(c.u);
+            uv.back().insert(uv.back().end(), c.v.begin(), c.v.end());
+        }
+        const auto e1 = evaluate_subclaims_batch(f1s, f2s, f3s, gs, uv), e2 = evaluate_subclaims_batch(f1s, f2s, f3s, g2s, uv);
+        std::vector<bool> ok(n);
+        for (size_t i = 0; i < n; ++i) {
+            Fr a, b, f1v, t, all;
+            check(sc_fr_elementwise(0, coeffs[i][0].l, e1[i][0].l, a.l, 1));
+            check(sc_fr_elementwise(0, coeffs[i][1].l, e2[i][0].l, b.l, 1));
+            check(sc_fr_elementwise(1, a.l, b.l, f1v.l, 1));
+            check(sc_fr_elementwise(0, f1v.l, e1[i][1].l, t.l, 1));
+            check(sc_fr_elementwise(0, t.l, e1[i][2].l, all.l, 1));
+            ok[i] = all == subclaims[i].expected_evaluation;
+        }
+        return ok;
+    }
+    bool verify_subclaim_two_point(const SparseMultilinearExtension &f1, const DenseMultilinearExtension &f2, const DenseMultilinearExtension &f3, const std::vector<Fr> &g,
+                                   const std::vector<Fr> &g2, const Fr &alpha, const Fr &beta) const {
+        return verify_subclaim_two_point_batch({*this}, {&f1}, {&f2}, {&f3}, {g}, {g2}, {std::array<Fr, 2>{alpha, beta}})[0];
+    }
 };
 
 // n x the two prover states of GKRRoundSumcheck::prove of ONE dim behind one sc_gkr_batch_prover handle (GKRRoundSumcheck::prover_init_batch):
@@ -726,6 +756,33 @@ class GKRBatchProverState {
             pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
         }
         check(sc_gkr_layer_next_batch(h_, keep ? nullptr : idx.data(), keep ? nullptr : vals.data(), keep ? nullptr : nnz.data(), p2.data(), p3.data(), pg.data(), 0));
+    }
+    // ... onto a layer in TWO-POINT form (sc_gkr_two_point_next_batch), whichever form the handle was built in: per instance a second point
+    // g2s[i] and coeffs[i] = (alpha, beta); alpha eq(g, .) + beta eq(g2, .) stands where eq(g, .) stands.  The overload above returns the
+    // handle to the one-point form.
+    void next_layer(const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                    const std::vector<std::vector<Fr>> &g2s, const std::vector<std::array<Fr, 2>> &coeffs, const std::vector<const SparseMultilinearExtension *> &f1s = {}) {
+        const bool keep = f1s.empty();
+        if (f2s.size() != n || f3s.size() != n || gs.size() != n || g2s.size() != n || coeffs.size() != n || (!keep && f1s.size() != n))
+            throw Panic(SC_ERR_BAD_ARG, "one f2, f3, g, g2 and (alpha, beta) per instance, and one f1 or none at all");
+        std::vector<const uint64_t *> idx(n + 1), vals(n + 1), p2(n + 1), p3(n + 1), pg(n + 1), pg2(n + 1);
+        std::vector<uint64_t> nnz(n + 1);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f2s[i] || !f3s[i] || (!keep && !f1s[i])) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim || g2s[i].size() != dim || (!keep && f1s[i]->num_vars != 3 * dim))
+                throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            if (!keep) {
+                idx[i] = f1s[i]->indices.data();
+                vals[i] = f1s[i]->values.empty() ? nullptr : f1s[i]->values[0].l;
+                nnz[i] = f1s[i]->indices.size();
+            }
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+            pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+            pg2[i] = g2s[i].empty() ? nullptr : g2s[i][0].l;
+        }
+        check(sc_gkr_two_point_next_batch(h_, keep ? nullptr : idx.data(), keep ? nullptr : vals.data(), keep ? nullptr : nnz.data(), p2.data(), p3.data(), pg.data(), pg2.data(),
+                                          n ? coeffs[0][0].l : nullptr, 0));
     }
     sc_gkr_batch_prover *raw() { return h_; }
     std::vector<Fr> challenges(const std::vector<VerifierMsg> &v_msgs) const {
@@ -852,6 +909,32 @@ struct GKRRoundSumcheck {
         }
         sc_gkr_batch_prover *h = nullptr;
         check(sc_gkr_batch_prover_init((uint32_t)n, (uint32_t)dim, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), 0, &h));
+        return GKRBatchProverState(h, n, dim);
+    }
+    // ... in TWO-POINT form (sc_gkr_two_point_init_batch): the handle proves alpha W(g) + beta W(g2) = sum (alpha f1(g,x,y) + beta f1(g2,x,y)) f2(x) f3(y),
+    // the claim a GKR layer below the output layer starts from.  g2s[i]: the second point; coeffs[i]: (alpha, beta).  finish's f1_guv is
+    // alpha f1(g,u,v) + beta f1(g2,u,v); everything else is as above.
+    static GKRBatchProverState prover_init_batch(const std::vector<const SparseMultilinearExtension *> &f1s, const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                 const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                                                 const std::vector<std::vector<Fr>> &g2s, const std::vector<std::array<Fr, 2>> &coeffs) {
+        const size_t n = f1s.size();
+        if (f2s.size() != n || f3s.size() != n || gs.size() != n || g2s.size() != n || coeffs.size() != n) throw Panic(SC_ERR_BAD_ARG, "one f1, f2, f3, g, g2 and (alpha, beta) per instance");
+        const size_t dim = n && f2s[0] ? f2s[0]->num_vars : 0;
+        std::vector<const uint64_t *> idx(n + 1), vals(n + 1), p2(n + 1), p3(n + 1), pg(n + 1), pg2(n + 1);
+        std::vector<uint64_t> nnz(n + 1);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f1s[i] || !f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f1s[i]->num_vars != 3 * dim || f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim || g2s[i].size() != dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            idx[i] = f1s[i]->indices.data();
+            vals[i] = f1s[i]->values.empty() ? nullptr : f1s[i]->values[0].l;
+            nnz[i] = f1s[i]->indices.size();
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+            pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+            pg2[i] = g2s[i].empty() ? nullptr : g2s[i][0].l;
+        }
+        sc_gkr_batch_prover *h = nullptr;
+        check(sc_gkr_two_point_init_batch((uint32_t)n, (uint32_t)dim, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), pg2.data(), n ? coeffs[0][0].l : nullptr, 0, &h));
         return GKRBatchProverState(h, n, dim);
     }
 };

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, and sc_gkr_layer_next_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, sc_gkr_layer_next_batch, and sc_gkr_two_point_init_batch with sc_gkr_two_point_next_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -433,7 +433,8 @@ SC_API_GKRB int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp);
 SC_API_GKRB void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp);
 /* ---- the handle onto the NEXT LAYER's inputs, without a rebuild ---------------------------------------------------------------------------
  * A GKR prover runs one round sumcheck per layer under one transcript, and every layer has new inputs: its g is the previous layer's
- * point, its f2 and f3 are the next layer's values, often it has wiring of its own.  sc_gkr_layer_next_batch puts an existing handle onto
+ * point [the output layer's; a layer below it starts from TWO points: sc_gkr_two_point_next_batch, further down], its f2 and f3 are the
+ * next layer's values, often it has wiring of its own.  sc_gkr_layer_next_batch puts an existing handle onto
  * them: it ALLOCATES NOTHING and leaves the handle at round 0 with phase one's tables built, exactly as a fresh sc_gkr_batch_prover_init
  * over these inputs would -- same plan, same bits.  It may be called in any state [fresh, in the middle of either phase, after finish];
  * afterwards round is 0, the kept randomness is empty and the handle is not exhausted.
@@ -460,6 +461,39 @@ SC_API_GKRB void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp);
 SC_API_GKRL int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null,
                                         const uint64_t *nnz_or_null, const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
                                         uint32_t flags);
+/* ---- the TWO-POINT form of the handle: a layer whose claim stands at two points -------------------------------------------------------------
+ * GKRRoundSumcheck::verify ends a round with a subclaim at TWO points, u and v [mod.rs:183-191; data_structures.rs:33-56]; the next layer's
+ * values W are claimed at W[u] and at W[v].  Only the output layer's g is one point.  Every layer below it starts from a linear
+ * combination of two claims [XZZPS19, the paper the reference module cites], proved by one round sumcheck:
+ *     alpha W[g] + beta W[g2]  =  sum over x, y of [ alpha f1[g,x,y] + beta f1[g2,x,y] ] f2[x] f3[y].
+ * Per instance i the caller gives, besides sc_gkr_batch_prover_init's arguments, a second point g2[i] [dim x 4 limbs, host] and two
+ * coefficients coef[i] = [alpha_i, beta_i] [coef: n x 2 x 4 limbs, instance-major, host, Montgomery, canonical].  Wherever the handle
+ * uses eq[g_i, z] it uses E_i[z] = alpha_i eq[g_i, z] + beta_i eq[g2_i, z] instead: phase one's h[x] = sum E[z] v f3[y], phase two's
+ * f1_gu[y] = sum E[z] eq[u,x] v.  Rounds, the phase change, f2[u], finish, state, reset, the shared challenge and every status are
+ * untouched; finish's first value is alpha f1[g,u,v] + beta f1[g2,u,v].  Every output is a canonical field element: the three plans give
+ * the same bits.  [alpha, beta] = [1, 0], beta = 0, alpha = beta = 0 and g2 = g are ordinary inputs; [1, 0] gives the one-point bits.
+ * EVERY handle can change form layer by layer: both inits reserve room for g2 and coef [n x [dim + 2] x 32 bytes in the upload area and
+ * in a layer's staging image; the input area's accounting, in_cap and the capacity error's byte counts do not move];
+ * sc_gkr_layer_next_batch on a handle in two-point form returns it to the one-point form, sc_gkr_two_point_next_batch works on a handle
+ * built by either init, sc_gkr_batch_prover_reset keeps the form.
+ * PLANS: one block per instance [dim <= 9] builds eq[g2, .] in the LDS region eq[u, .] will occupy and folds it into eq[g, .] in one pass
+ * -- no LDS beyond 128 B x 2^dim; the sliced plan keeps a second pair of half tables with alpha and beta folded into the low halves -- one
+ * fr_mul and one fr_add more per term, the lanes' bound unchanged; the serial plan combines the dense tables of g and of g2 by linearity.
+ * Counted as plan batch.gkr_two_point, once per successful call of either function below, on any plan.
+ * SC_API_GKR2 is SC_API; a marker of its own, for the reason the older families have theirs [tests/test_gkr_two_point_host.py compares
+ * these prototypes with the shim's declarations; every older scanner asserts a closed set]. */
+#define SC_API_GKR2 SC_API /* [nothing but this comment may follow on the line] */
+/* sc_gkr_batch_prover_init with g2 and coef; the same checks before any HIP call, and behind them per instance: a null g2[i] is
+ * SC_ERR_BAD_ARG "instance %u: null argument", then "instance %u: g2 is not canonical", then "instance %u: coefficient is not canonical".
+ * A null g2 or coef is SC_ERR_BAD_ARG "null argument".  The lowest failing instance decides. */
+SC_API_GKR2 int sc_gkr_two_point_init_batch(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
+                                            const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2,
+                                            const uint64_t *coef, uint32_t flags, sc_gkr_batch_prover **out);
+/* sc_gkr_layer_next_batch with g2 and coef, which are checked with g and staged where g is staged; every error of that call and the three
+ * above leave a proof in progress exactly where it was: nothing of the handle's is written before the last check has passed. */
+SC_API_GKR2 int sc_gkr_two_point_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null,
+                                            const uint64_t *nnz_or_null, const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
+                                            const uint64_t *const *g2, const uint64_t *coef, uint32_t flags);
 /* f4 -- the same two initialisations with f1's non-zeros SPREAD OVER SEVERAL GPUs (worth it from dim ~ 24).
  * Every rank passes a disjoint subset of f1's (index, value) pairs -- any partition -- and all of f3 / g.  A rank's scatter is a
  * partial sum of a_hg, so the ranks' dense tables are added with ONE table-sized integer all-reduce of the widened limbs

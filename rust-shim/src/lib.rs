@@ -7,6 +7,7 @@
 //! | [`prove`], [`prove_as_subprotocol`]         | `MLSumcheck::{prove, prove_as_subprotocol}` `src/ml_sumcheck/mod.rs:42,50` |
 //! | [`gkr_prover_init_batch`], [`gkr_prove_round_batch`], [`gkr_finish_batch`] | (new) the rounds of many small `GKRRoundSumcheck::prove` under the caller's transcript (`rng: &mut impl FeedableRNG`), one call per round |
 //! | [`gkr_next_layer_batch`] | (new) the same handle onto the next layer's `f2`, `f3`, `g` (and `f1`) without a rebuild: one handle for the layers of a GKR prover |
+//! | [`gkr_prover_init_batch_two_point`], [`gkr_next_layer_batch_two_point`] | (new) the same handle in two-point form: `alpha eq(g, .) + beta eq(g2, .)` where `eq(g, .)` stands, for the layers of a GKR prover below the output layer |
 //! | [`prover_init_batch`], [`prove_round_batch`] | (new) `states.par_iter_mut().zip(msgs).map(prove_round)`: one round of many small provers in one call, the caller's transcript |
 //! | [`prove_batch`]                            | (new) `polys.par_iter().map(MLSumcheck::prove)`: many small instances of one structure in one call |
 //! | [`evaluate`]                                | `ListOfProductsOfPolynomials::evaluate` `src/ml_sumcheck/data_structures.rs:99` |
@@ -759,6 +760,106 @@ pub fn gkr_next_layer_batch<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, la
     check(unsafe {
         sc_gkr_layer_next_batch(state.handle, if keep { null } else { idx.as_ptr() }, if keep { null } else { vals.as_ptr() },
                                 if keep { core::ptr::null() } else { nnz.as_ptr() }, f2.as_ptr(), f3.as_ptr(), g.as_ptr(), 0)
+    });
+}
+
+// The two-point form of the handle (`sc_gkr_two_point_init_batch`, `sc_gkr_two_point_next_batch`): private declarations, a block each.
+extern "C" {
+    fn sc_gkr_two_point_init_batch(n: u32, dim: u32, f1_idx: *const *const u64, f1_vals: *const *const u64, nnz: *const u64, f2: *const *const u64,
+                                   f3: *const *const u64, g: *const *const u64, g2: *const *const u64, coef: *const u64, flags: u32,
+                                   out: *mut *mut sc_gkr_batch_prover) -> c_int;
+}
+extern "C" {
+    fn sc_gkr_two_point_next_batch(bp: *mut sc_gkr_batch_prover, f1_idx_or_null: *const *const u64, f1_vals_or_null: *const *const u64, nnz_or_null: *const u64,
+                                   f2: *const *const u64, f3: *const *const u64, g: *const *const u64, g2: *const *const u64, coef: *const u64,
+                                   flags: u32) -> c_int;
+}
+
+/// The second point and the coefficients of one instance in two-point form: the handle proves
+/// `alpha W(g) + beta W(g2) = sum (alpha f1(g,x,y) + beta f1(g2,x,y)) f2(x) f3(y)`, the claim a GKR layer below the output layer starts from.
+pub struct GkrSecondPoint<'a, F: Limbs4> {
+    pub g2: &'a [F],
+    pub alpha: F,
+    pub beta: F,
+}
+
+fn second_point_arrays<F: Limbs4>(second: &[GkrSecondPoint<F>], n: usize, dim: usize) -> (Vec<Vec<[u64; 4]>>, Vec<[u64; 4]>) {
+    assert_eq!(second.len(), n, "one second point per instance");
+    let mut g2s = Vec::with_capacity(n);
+    let mut coef = Vec::with_capacity(2 * n);
+    for s in second.iter() {
+        assert_eq!(s.g2.len(), dim);
+        g2s.push(s.g2.iter().map(|x| x.to_limbs()).collect());
+        coef.push(s.alpha.to_limbs());
+        coef.push(s.beta.to_limbs());
+    }
+    (g2s, coef)
+}
+
+/// [`gkr_prover_init_batch`] in two-point form (`sc_gkr_two_point_init_batch`): `alpha eq(g, .) + beta eq(g2, .)` stands wherever the
+/// handle uses `eq(g, .)`; rounds, finish, state and reset are unchanged, and the first value of [`gkr_finish_batch`] is
+/// `alpha f1(g,u,v) + beta f1(g2,u,v)`.
+pub fn gkr_prover_init_batch_two_point<F: Limbs4>(instances: &[GkrRoundsInstance<F>], second: &[GkrSecondPoint<F>]) -> HipGkrBatchProverState<F> {
+    let n = instances.len();
+    let dim = if n > 0 { instances[0].f2.num_vars } else { 0 };
+    let mut arrays = Vec::with_capacity(n);
+    let mut gls: Vec<Vec<[u64; 4]>> = Vec::with_capacity(n);
+    for inst in instances.iter() {
+        assert_eq!(inst.f1.num_vars, 3 * dim);
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        arrays.push(sparse_arrays(inst.f1));
+        gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+    }
+    let (g2s, coef) = second_point_arrays(second, n, dim);
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let f2: Vec<*const u64> = instances.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = instances.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = gls.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let g2: Vec<*const u64> = g2s.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let mut handle: *mut sc_gkr_batch_prover = core::ptr::null_mut();
+    check(unsafe {
+        sc_gkr_two_point_init_batch(n as u32, dim as u32, idx.as_ptr(), vals.as_ptr(), nnz.as_ptr(), f2.as_ptr(), f3.as_ptr(), g.as_ptr(), g2.as_ptr(),
+                                    coef.as_ptr() as *const u64, 0, &mut handle)
+    });
+    HipGkrBatchProverState { handle, n, dim, _f: core::marker::PhantomData }
+}
+
+/// [`gkr_next_layer_batch`] onto a layer in two-point form (`sc_gkr_two_point_next_batch`), on a handle built in either form;
+/// [`gkr_next_layer_batch`] afterwards returns the handle to the one-point form.
+pub fn gkr_next_layer_batch_two_point<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, layer: &[GkrNextLayerInstance<F>], second: &[GkrSecondPoint<F>]) {
+    let (n, dim) = (state.n, state.dim);
+    assert_eq!(layer.len(), n, "one entry per instance of the handle");
+    let keep = layer.iter().all(|i| i.f1.is_none());
+    assert!(keep || layer.iter().all(|i| i.f1.is_some()), "new wiring for every instance, or for none");
+    let mut arrays = Vec::with_capacity(n);
+    let mut gls: Vec<Vec<[u64; 4]>> = Vec::with_capacity(n);
+    for inst in layer.iter() {
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        if let Some(f1) = inst.f1 {
+            assert_eq!(f1.num_vars, 3 * dim);
+            arrays.push(sparse_arrays(f1));
+        }
+        gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+    }
+    let (g2s, coef) = second_point_arrays(second, n, dim);
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let f2: Vec<*const u64> = layer.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = layer.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = gls.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let g2: Vec<*const u64> = g2s.iter().map(|a| a.as_ptr() as *const u64).collect();
+    let null = core::ptr::null();
+    check(unsafe {
+        sc_gkr_two_point_next_batch(state.handle, if keep { null } else { idx.as_ptr() }, if keep { null } else { vals.as_ptr() },
+                                    if keep { core::ptr::null() } else { nnz.as_ptr() }, f2.as_ptr(), f3.as_ptr(), g.as_ptr(), g2.as_ptr(),
+                                    coef.as_ptr() as *const u64, 0)
     });
 }
 

@@ -21,6 +21,10 @@
 //                               dim > 16, nnz beyond 64 x 2^dim, policy "batch" = 0.
 // The handle copies every input once per distinct pointer (phase two needs f1 and f3 again): nothing of the caller's is read after init.
 // sc_gkr_layer_next_batch (at the end) puts a handle onto the next layer's inputs inside what init allocated.
+// The two-point form (sc_gkr_two_point_init_batch, sc_gkr_two_point_next_batch): a layer below the output layer is claimed at two points, and
+// alpha eq(g, .) + beta eq(g2, .) stands wherever eq(g, .) stands above -- k_batch_gkr_phase<., 2> folds eq(g2, .) into eq(g, .) in LDS,
+// k_batch_gkr_terms<., 2> keeps a second pair of half tables, the serial plan combines the dense tables of g and g2 (k_gkr_two_point_combine).
+// Every handle reserves room for g2 and the coefficients and takes either form layer by layer; a reset keeps the form.
 #include <set>
 
 #include "batch_slices.hpp"
@@ -38,7 +42,7 @@ struct sc_gkr_batch_prover {
     std::vector<sch::Fr> g;                        // n x dim
     std::vector<scd::GkrBatchInst> rec;            // the instances' arrays in the handle's copy (d_in), g in d_up
     hipStream_t stream = nullptr;
-    char *d_buf = nullptr; // device, ONE allocation: area A | area B (work areas) | matrices | records | index flags | g | challenges | messages | f2(u) | export area | a layer's staging image | inputs | serial tables, or (slices) cells | partials
+    char *d_buf = nullptr; // device, ONE allocation: area A | area B (work areas) | matrices | records | index flags | g | g2 | coefficients | challenges | messages | f2(u) | export area | a layer's staging image | inputs | serial tables, or (slices) cells | partials
     char *d_in = nullptr;  // (inside d_buf) the inputs, every distinct array once
     char *d_cells = nullptr, *d_part = nullptr; // (inside d_buf, slices) the wide cells both phases share, n x 64 B x 2^dim; the sliced rounds' partials
     size_t cells_bytes = 0;
@@ -56,6 +60,13 @@ struct sc_gkr_batch_prover {
     char *d_tabs = nullptr; // (inside d_buf) per instance h_g | f1(g, u, .) | f2(u) f3, 2^dim elements each
     char *d_fin = nullptr;  // (inside d_buf) bind_final's n x 2 elements
     std::vector<sch::Fr> f2u; // n: f2(u), from the phase change
+    // ---- the two-point form (sc_gkr_two_point_init_batch / _next_batch): alpha eq(g, .) + beta eq(g2, .) where eq(g, .) stands ----
+    bool two_point = false;          // the form of the layer in force: every init and every next call sets it, a reset keeps it
+    std::vector<sch::Fr> g2, coef;   // n x dim; n x 2 (alpha, beta) -- read only in two-point form
+    size_t g2_off = 0, coef_off = 0; // (offsets into h_pin, behind g) the upload area's g2 and coefficients: reserved by both inits
+    size_t nl_g2_off = 0, nl_coef_off = 0; // ... and their places in a layer's staging image, behind its g
+    char *d_tab2 = nullptr;          // (inside d_buf, serial plan) ONE scratch table of 2^dim elements: the dense table of g2 before it is combined
+    int points() const { return two_point ? 2 : 1; }
 };
 
 namespace {
@@ -119,6 +130,17 @@ int serial_prover(sc_gkr_batch_prover *bp, sc_prover **p, const void *t0, const 
     return rc;
 }
 
+// the serial plan's two-point tables, by linearity: table <- alpha table + beta d_tab2 (the dense tables of g and of g2), one launch on the
+// handle's stream and a synchronisation -- the tables' producer has synchronised, their consumer is a prover with a stream of its own
+int serial_combine(sc_gkr_batch_prover *bp, uint32_t i, char *table) {
+    DeviceGate gate_(bp->device);
+    HIP_TRY(hipSetDevice(bp->device));
+    const uint4 *coef = reinterpret_cast<const uint4 *>(bp->d_buf + 2 * bp->work_bytes + bp->coef_off) + 4 * (size_t)i;
+    HIP_TRY(scd::launch_gkr_two_point_combine(reinterpret_cast<const uint4 *>(table), reinterpret_cast<const uint4 *>(bp->d_tab2), coef, reinterpret_cast<uint4 *>(table), 1ULL << bp->dim, bp->stream));
+    HIP_TRY(hipStreamSynchronize(bp->stream));
+    return SC_OK;
+}
+
 // the serial plan's phase change for instance i: f2(u) from phase one's prover, f1(g, u, .), f2(u) f3, phase two's prover
 int serial_phase_two(sc_gkr_batch_prover *bp, uint32_t i, const std::vector<sch::Fr> &u_last) {
     const uint32_t dim = bp->dim;
@@ -128,6 +150,10 @@ int serial_phase_two(sc_gkr_batch_prover *bp, uint32_t i, const std::vector<sch:
     u[dim - 1] = challenge_of(u_last, i);
     const scd::GkrBatchInst &I = bp->rec[i];
     if (int rc = sc_internal_gkr_dense_table(2, I.idx, I.vals, bp->nnz[i], dim, I.f3, bp->g[(size_t)i * dim].l, u[0].l, serial_table(bp, i, 1))) return rc;
+    if (bp->two_point) {
+        if (int rc = sc_internal_gkr_dense_table(2, I.idx, I.vals, bp->nnz[i], dim, I.f3, bp->g2[(size_t)i * dim].l, u[0].l, bp->d_tab2)) return rc;
+        if (int rc = serial_combine(bp, i, serial_table(bp, i, 1))) return rc;
+    }
     if (int rc = sc_dense_scale(reinterpret_cast<const uint64_t *>(I.f3), 1ULL << dim, bp->f2u[i].l, reinterpret_cast<uint64_t *>(serial_table(bp, i, 2)), SC_TABLES_ON_DEVICE)) return rc; // mod.rs:71-75
     return serial_prover(bp, &bp->p2[i], serial_table(bp, i, 1), serial_table(bp, i, 2));
 }
@@ -146,7 +172,9 @@ int slices_phase(sc_gkr_batch_prover *bp, int phase) {
     P.cells = reinterpret_cast<uint64_t *>(bp->d_cells);
     P.n = bp->n;
     P.dim = bp->dim;
-    HIP_TRY(scd::launch_batch_gkr_slices_phase(phase, P, bp->nnz_max, bp->stream));
+    P.g2 = reinterpret_cast<const uint4 *>(d_up + bp->g2_off);
+    P.coef = reinterpret_cast<const uint4 *>(d_up + bp->coef_off);
+    HIP_TRY(scd::launch_batch_gkr_slices_phase(phase, P, bp->nnz_max, bp->stream, bp->points()));
     return SC_OK;
 }
 
@@ -160,7 +188,9 @@ int areas_phase_one(sc_gkr_batch_prover *bp) {
     A.work_a = reinterpret_cast<int32_t *>(bp->d_buf);
     A.n = bp->n;
     A.dim = bp->dim;
-    HIP_TRY(scd::launch_batch_gkr_phase(1, A, bp->stream));
+    A.g2 = reinterpret_cast<const uint4 *>(bp->d_buf + 2 * bp->work_bytes + bp->g2_off);
+    A.coef = reinterpret_cast<const uint4 *>(bp->d_buf + 2 * bp->work_bytes + bp->coef_off);
+    HIP_TRY(scd::launch_batch_gkr_phase(1, A, bp->stream, bp->points()));
     return SC_OK;
 }
 
@@ -169,6 +199,10 @@ int serial_phase_one(sc_gkr_batch_prover *bp) {
     for (uint32_t i = 0; i < bp->n; ++i) {
         const scd::GkrBatchInst &I = bp->rec[i];
         int rc = sc_internal_gkr_dense_table(1, I.idx, I.vals, bp->nnz[i], bp->dim, I.f3, bp->g[(size_t)i * bp->dim].l, nullptr, serial_table(bp, i, 0)); // mod.rs:30-38
+        if (rc == SC_OK && bp->two_point) {
+            rc = sc_internal_gkr_dense_table(1, I.idx, I.vals, bp->nnz[i], bp->dim, I.f3, bp->g2[(size_t)i * bp->dim].l, nullptr, bp->d_tab2);
+            if (rc == SC_OK) rc = serial_combine(bp, i, serial_table(bp, i, 0));
+        }
         if (rc == SC_OK) rc = serial_prover(bp, &bp->p1[i], serial_table(bp, i, 0), I.f2);
         if (rc) return prefix_instance(rc, i);
     }
@@ -189,10 +223,52 @@ std::vector<size_t> dense_slots_of(const std::vector<size_t> &offs, const std::v
     return std::vector<size_t>(dense.begin(), dense.end());
 }
 
+// the two-point form's own checks on instance i, behind gkr_check_instance's (no HIP call)
+int check_second_point(const uint64_t *const *g2, const uint64_t *coef, uint32_t dim, uint32_t i) {
+    if (!g2[i]) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: null argument", i);
+    for (uint32_t k = 0; k < dim; ++k) {
+        sch::Fr e;
+        std::memcpy(&e, g2[i] + 4 * (size_t)k, 32);
+        if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: g2 is not canonical", i);
+    }
+    for (uint32_t k = 0; k < 2; ++k) {
+        sch::Fr e;
+        std::memcpy(&e, coef + 4 * ((size_t)i * 2 + k), 32);
+        if (sch::geq_p(e)) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: coefficient is not canonical", i);
+    }
+    return SC_OK;
+}
+
+// sc_gkr_batch_prover_init (g2 and coef null: the one-point form) and sc_gkr_two_point_init_batch
+int init_handle(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2, const uint64_t *const *f3,
+                const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags, sc_gkr_batch_prover **out);
+// sc_gkr_layer_next_batch (g2 and coef null: the layer is in one-point form) and sc_gkr_two_point_next_batch
+int next_layer(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null, const uint64_t *nnz_or_null, const uint64_t *const *f2,
+               const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags);
+
 } // namespace
 
 extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2,
                                         const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags, sc_gkr_batch_prover **out) {
+    return init_handle(n, dim, f1_idx, f1_vals, nnz, f2, f3, g, nullptr, nullptr, flags, out);
+}
+
+// The two-point form of the init: per instance a second point g2[i] and coefficients coef[i] = (alpha, beta); alpha eq(g, .) + beta eq(g2, .)
+// stands wherever the handle uses eq(g, .) -- the claim alpha W(g) + beta W(g2) a GKR layer below the output layer starts from.
+extern "C" int sc_gkr_two_point_init_batch(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2,
+                                           const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags, sc_gkr_batch_prover **out) {
+    if (!g2 || !coef) {
+        if (out) *out = nullptr;
+        return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    }
+    const int rc = init_handle(n, dim, f1_idx, f1_vals, nnz, f2, f3, g, g2, coef, flags, out);
+    if (rc == SC_OK) scd::plan_hit(scd::kPlanBatchGkrTwoPoint);
+    return rc;
+}
+
+namespace {
+int init_handle(uint32_t n, uint32_t dim, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *f2, const uint64_t *const *f3,
+                const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags, sc_gkr_batch_prover **out) {
     // ---- everything the host can check, before any HIP call (sc_gkr_prove_batch's checks: the lowest failing instance decides) ----
     if (!f1_idx || !f1_vals || !nnz || !f2 || !f3 || !g || !out) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
     *out = nullptr;
@@ -204,6 +280,8 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
     uint64_t nnz_max = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (int rc = gkr_check_instance(in, i, nullptr)) return rc;
+        if (g2)
+            if (int rc = check_second_point(g2, coef, dim, i)) return rc;
         nnz_max = std::max(nnz_max, nnz[i]);
     }
     if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
@@ -215,6 +293,13 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
     bp->nnz.assign(nnz, nnz + n);
     bp->g.resize((size_t)n * dim);
     for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g[(size_t)i * dim], g[i], (size_t)dim * 32);
+    bp->two_point = g2 != nullptr;
+    bp->g2.resize((size_t)n * dim); // (zero in one-point form: room for a later two-point layer)
+    bp->coef.resize((size_t)n * 2);
+    if (g2) {
+        for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g2[(size_t)i * dim], g2[i], (size_t)dim * 32);
+        std::memcpy(bp->coef.data(), coef, (size_t)n * 64);
+    }
     bp->nnz_max = nnz_max;
     const size_t N = (size_t)1 << dim;
     auto build = [&]() -> int {
@@ -244,7 +329,9 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
         bp->rec_off = bp->w_off + round_up((size_t)bp->s.w_elems * 32, 256);
         bp->flag_off = bp->rec_off + round_up((size_t)n * sizeof(scd::GkrBatchInst), 256);
         bp->g_off = bp->flag_off + round_up((size_t)n * 4, 256);
-        bp->u_off = bp->g_off + round_up((size_t)n * dim * 32, 256);
+        bp->g2_off = bp->g_off + round_up((size_t)n * dim * 32, 256);
+        bp->coef_off = bp->g2_off + round_up((size_t)n * dim * 32, 256);
+        bp->u_off = bp->coef_off + round_up((size_t)n * 64, 256);
         bp->msg_off = bp->u_off + round_up((size_t)2 * dim * n * 32, 256);
         bp->f2u_off = bp->msg_off + round_up((size_t)n * 3 * 32, 256);
         bp->exp_off = bp->f2u_off + round_up((size_t)n * 32, 256);
@@ -252,19 +339,22 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
         bp->nl_chk_off = bp->nl_flag_off + round_up((size_t)n * 4, 256);
         bp->nl_rec_off = bp->nl_chk_off + round_up((size_t)n * sizeof(scd::GkrBatchInst), 256);
         bp->nl_g_off = bp->nl_rec_off + round_up((size_t)n * sizeof(scd::GkrBatchInst), 256);
-        bp->nl_item_off = bp->nl_g_off + round_up((size_t)n * dim * 32, 256);
-        bp->pin_bytes = bp->nl_item_off + round_up(((size_t)n * 4 + 2) * sizeof(scd::GkrRestageItem), 256); // (every array of every instance, the records, g)
+        bp->nl_g2_off = bp->nl_g_off + round_up((size_t)n * dim * 32, 256);
+        bp->nl_coef_off = bp->nl_g2_off + round_up((size_t)n * dim * 32, 256);
+        bp->nl_item_off = bp->nl_coef_off + round_up((size_t)n * 64, 256);
+        bp->pin_bytes = bp->nl_item_off + round_up(((size_t)n * 4 + 4) * sizeof(scd::GkrRestageItem), 256); // (every array of every instance, the records, g, g2, the coefficients)
         {
             DeviceGate gate_(bp->device);
             HIP_TRY(hipSetDevice(bp->device));
             HIP_TRY(hipStreamCreateWithFlags(&bp->stream, hipStreamNonBlocking));
-            const size_t tabs_bytes = areas ? 0 : (size_t)n * 3 * N * 32, fin_bytes = areas ? 0 : round_up((size_t)n * 64, 256);
+            const size_t tabs_bytes = areas ? 0 : ((size_t)n * 3 + 1) * N * 32, fin_bytes = areas ? 0 : round_up((size_t)n * 64, 256);
             bp->cells_bytes = slices ? (size_t)n * scd::kBsGkrCellBytes * N : 0;
             const size_t part_bytes = slices ? round_up((size_t)scd::bs_partials_bytes(n, dim, 2, 1, 3, bp->s.n_combos), 256) : 0;
             HIP_TRY(hipMalloc(reinterpret_cast<void **>(&bp->d_buf), 2 * bp->work_bytes + bp->pin_bytes + in_bytes + tabs_bytes + fin_bytes + bp->cells_bytes + part_bytes)); // (one allocation: a handle's life is short)
             bp->d_in = bp->d_buf + 2 * bp->work_bytes + bp->pin_bytes;
             if (!areas) {
                 bp->d_tabs = bp->d_in + in_bytes;
+                bp->d_tab2 = bp->d_tabs + (size_t)n * 3 * N * 32;
                 bp->d_fin = bp->d_tabs + tabs_bytes;
             }
             if (slices) {
@@ -278,6 +368,8 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
             instance_weights(bp->s, sch::kOne.l, reinterpret_cast<sch::Fr *>(bp->h_pin + bp->w_off));
             std::memset(bp->h_pin + bp->flag_off, 0, round_up((size_t)n * 4, 256));
             std::memcpy(bp->h_pin + bp->g_off, bp->g.data(), (size_t)n * dim * 32);
+            std::memcpy(bp->h_pin + bp->g2_off, bp->g2.data(), (size_t)n * dim * 32);
+            std::memcpy(bp->h_pin + bp->coef_off, bp->coef.data(), (size_t)n * 64);
             bp->rec.resize(n);
             for (uint32_t i = 0; i < n; ++i) {
                 scd::GkrBatchInst &r = bp->rec[i];
@@ -311,6 +403,7 @@ extern "C" int sc_gkr_batch_prover_init(uint32_t n, uint32_t dim, const uint64_t
     *out = bp;
     return SC_OK;
 }
+} // namespace
 
 extern "C" void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp) { destroy(bp); }
 
@@ -345,7 +438,9 @@ extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t 
             P.f2u = reinterpret_cast<uint4 *>(d_up + bp->f2u_off);
             P.n = n;
             P.dim = dim;
-            HIP_TRY(scd::launch_batch_gkr_phase(2, P, bp->stream));
+            P.g2 = reinterpret_cast<const uint4 *>(d_up + bp->g2_off);
+            P.coef = reinterpret_cast<const uint4 *>(d_up + bp->coef_off);
+            HIP_TRY(scd::launch_batch_gkr_phase(2, P, bp->stream, bp->points()));
         }
         scd::BatchRoundArgs A;
         std::memset(&A, 0, sizeof(A));
@@ -457,7 +552,8 @@ extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
 }
 
 // ---- sc_gkr_layer_next_batch: the handle onto the next layer's inputs, inside what init allocated ------------------------------------
-// A GKR prover runs one round sumcheck per layer under one transcript, and every layer has new inputs: its g is the previous layer's point,
+// A GKR prover runs one round sumcheck per layer under one transcript, and every layer has new inputs: its g is the previous layer's point
+// (the output layer's; below it the claim stands at two points: next_layer's g2 and coef),
 // its f2 and f3 are the next layer's values, often it has wiring of its own.  The input area is laid out again by init's rule (a layer that
 // keeps the wiring leaves the wiring's arrays where they are and gives its distinct f2 / f3 the places the former ones had), phase one's
 // tables are rebuilt, and the handle is at round 0 as a fresh init over these inputs would leave it -- same plan, same bits.
@@ -470,6 +566,22 @@ extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
 // the next successful call of this function, or free.
 extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null, const uint64_t *nnz_or_null,
                                        const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, uint32_t flags) {
+    return next_layer(bp, f1_idx_or_null, f1_vals_or_null, nnz_or_null, f2, f3, g, nullptr, nullptr, flags); // (a handle in two-point form returns to the one-point form)
+}
+
+// The two-point form of the call, on a handle built by either init: g2 and coef are staged where g is staged, and checked with it.
+extern "C" int sc_gkr_two_point_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null, const uint64_t *nnz_or_null,
+                                           const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags) {
+    if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (!g2 || !coef) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    const int rc = next_layer(bp, f1_idx_or_null, f1_vals_or_null, nnz_or_null, f2, f3, g, g2, coef, flags);
+    if (rc == SC_OK) scd::plan_hit(scd::kPlanBatchGkrTwoPoint);
+    return rc;
+}
+
+namespace {
+int next_layer(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null, const uint64_t *nnz_or_null, const uint64_t *const *f2,
+               const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags) {
     // ---- everything the host can check, before any HIP call and before the first change to the handle ----
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
     if (!f2 || !f3 || !g) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
@@ -490,6 +602,8 @@ extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *
     uint64_t nnz_max = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (int rc = gkr_check_instance(in, i, nullptr)) return rc;
+        if (g2)
+            if (int rc = check_second_point(g2, coef, dim, i)) return rc;
         // the plan stays the one chosen at init (the serial plan takes every shape)
         if (new_f1 && bp->work_areas()) {
             const int would = scd::gkr_bs_plan(n, dim, nnz[i], bp->s.n_combos, bp->pol_batch, bp->pol_slices);
@@ -566,6 +680,10 @@ extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *
         std::memcpy(bp->h_pin + bp->nl_chk_off, chk.data(), rec_bytes);
         std::memcpy(bp->h_pin + bp->nl_rec_off, rec.data(), rec_bytes);
         for (uint32_t i = 0; i < n; ++i) std::memcpy(bp->h_pin + bp->nl_g_off + (size_t)i * dim * 32, g[i], (size_t)dim * 32);
+        if (g2) {
+            for (uint32_t i = 0; i < n; ++i) std::memcpy(bp->h_pin + bp->nl_g2_off + (size_t)i * dim * 32, g2[i], (size_t)dim * 32);
+            std::memcpy(bp->h_pin + bp->nl_coef_off, coef, (size_t)n * 64);
+        }
         scd::GkrRestageItem *items = reinterpret_cast<scd::GkrRestageItem *>(bp->h_pin + bp->nl_item_off);
         auto item = [&](const void *src, size_t dst_off, size_t bytes) {
             items[n_items++] = {src, dst_off, bytes, blocks};
@@ -574,6 +692,10 @@ extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *
         for (const StageMap::Item &it : copy) item(it.src, (size_t)(bp->d_in - bp->d_buf) + it.off, it.bytes);
         item(d_up + bp->nl_rec_off, 2 * bp->work_bytes + bp->rec_off, rec_bytes);
         item(d_up + bp->nl_g_off, 2 * bp->work_bytes + bp->g_off, g_bytes);
+        if (g2) {
+            item(d_up + bp->nl_g2_off, 2 * bp->work_bytes + bp->g2_off, g_bytes);
+            item(d_up + bp->nl_coef_off, 2 * bp->work_bytes + bp->coef_off, (size_t)n * 64);
+        }
         HIP_TRY(hipMemcpyAsync(d_up + bp->nl_flag_off, bp->h_pin + bp->nl_flag_off, bp->nl_item_off + n_items * sizeof(scd::GkrRestageItem) - bp->nl_flag_off, hipMemcpyHostToDevice, bp->stream));
         // new device-resident wiring: an index out of range is found here, over the caller's arrays -- nothing of the handle's has been written
         if (new_f1)
@@ -590,6 +712,13 @@ extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *
     bp->nnz_max = nnz_max;
     bp->rec = rec;
     for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g[(size_t)i * dim], g[i], (size_t)dim * 32);
+    bp->two_point = g2 != nullptr;
+    if (g2) {
+        for (uint32_t i = 0; i < n; ++i) std::memcpy(&bp->g2[(size_t)i * dim], g2[i], (size_t)dim * 32);
+        std::memcpy(bp->coef.data(), coef, (size_t)n * 64);
+        std::memcpy(bp->h_pin + bp->g2_off, bp->g2.data(), g_bytes);
+        std::memcpy(bp->h_pin + bp->coef_off, bp->coef.data(), (size_t)n * 64);
+    }
     bp->dense_slots = slots;
     bp->in_used = used;
     std::memcpy(bp->h_pin + bp->rec_off, rec.data(), rec_bytes);
@@ -620,3 +749,4 @@ extern "C" int sc_gkr_layer_next_batch(sc_gkr_batch_prover *bp, const uint64_t *
     if (bp->work_areas()) scd::plan_hit(scd::kPlanBatchGkrNextLayer);
     return SC_OK;
 }
+} // namespace

@@ -368,8 +368,14 @@ struct BatchGkrPhaseArgs {
     const uint4 *u;             // device: the challenges the handle has received, [challenge j][instance] elements (phase 2 reads j < dim)
     uint4 *f2u;                 // device: n elements (phase 2 writes)
     uint32_t n, dim;
+    const uint4 *g2, *coef;     // two-point form only (points = 2): device, n x dim elements g2 and n x 2 elements (alpha, beta), instance-major
 };
-hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream);
+// points 1: eq(g, .) as above.  points 2 (sc_gkr_two_point_*): E = alpha eq(g, .) + beta eq(g2, .) stands where eq(g, .) stands -- eq(g2, .)
+// is built in eq(u, .)'s region (free in phase 1, rebuilt afterwards in phase 2) and folded into eq(g, .) in one pass: no LDS beyond 128 B x 2^dim.
+hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream, int points = 1);
+// out[e] = alpha a[e] + beta b[e], e < count, canonical elements; coef: device, (alpha, beta).  The serial plan's two-point tables: by
+// linearity the dense table of E is this combination of the dense tables of g and of g2 (any dim).  out may be a or b.
+hipError_t launch_gkr_two_point_combine(const uint4 *a, const uint4 *b, const uint4 *coef, uint4 *out, uint64_t count, hipStream_t stream);
 // sc_gkr_layer_next_batch: the arrays a handle takes from the caller's device memory, all in ONE launch (k_batch_gkr_restage) out of a
 // device table of items.  An item is spread over ceil(bytes / kGkrRestageChunk) blocks, the first of them first_block: the items' first
 // blocks ascend from 0 and `blocks` is their total.  Sizes are multiples of 8; 16 bytes per lane where an item's source and destination are
@@ -398,8 +404,11 @@ struct BatchGkrSlicesArgs {
     uint64_t *cells;            // device: n x 8 x 2^dim lanes, zero on entry
     uint32_t n, dim;
     uint32_t blocks_per_inst;   // (filled in by the launcher from nnz_max: gkr_bs_term_blocks)
+    const uint4 *g2, *coef;     // two-point form only (points = 2): as in BatchGkrPhaseArgs
 };
-hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream);
+// points 2: a second pair of half tables for g2, alpha folded into g's low half and beta into g2's; a term's weight is
+// lo[z_lo] hi[z_hi] + lo2[z_lo] hi2[z_hi], canonical -- the number of terms per cell and with it the lanes' bound are those of points 1.
+hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream, int points = 1);
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -461,6 +470,7 @@ enum Plan {
     kPlanShardedRcclPublish,  // ... all-reduce + publish kernel
     kPlanShardedHost,         // ... the caller's host transport
     kPlanShardedP2P,          // ... k_p2p_allreduce
+    kPlanBatchGkrTwoPoint,    // sc_gkr_two_point_init_batch / sc_gkr_two_point_next_batch: a GKR batch handle in two-point form (alpha eq(g, .) + beta eq(g2, .) where eq(g, .) stands), on any plan; counted once per successful call
     kPlanShardedGatherTail,   // bind + all-gather + replicated tail
     kPlanBatchRoundsSlices,   // sc_batch_prove_round: k_batch_round_slices + k_batch_round_fin, several blocks per instance, two launches for a round of the whole batch (the rounds whose tables do not fit one block; policy "batch_slices" = 1)
     kPlanGkrBucketedGrouped,  // GKR initialisation: buckets of an index-ordered list (k_bucket_bounds)

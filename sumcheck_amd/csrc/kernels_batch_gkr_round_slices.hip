@@ -40,10 +40,15 @@ __device__ __forceinline__ size_t gs_lane_index(const uint32_t inst, const uint3
 #endif
 }
 
-template <int kPhase>
+// kPoints 2 (sc_gkr_two_point_*): alpha eq(g, .) + beta eq(g2, .) stands where eq(g, .) stands.  It is not a product of halves, so g2 gets a
+// pair of half tables of its own; alpha is folded into g's low half and beta into g2's (at most 2^8 products each, once per block), and a
+// term's weight is lo[z_lo] hi[z_hi] + lo2[z_lo] hi2[z_hi]: one fr_mul and one fr_add more, canonical.  Terms per cell, and with them the
+// lanes' bound, are unchanged.  Static LDS of <2, 2>: three pairs of half tables, 48 KB.
+template <int kPhase, int kPoints>
 __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_terms(const BatchGkrSlicesArgs A) {
     __shared__ uint4 g_sh[2 * kBsMaxNv], u_sh[kPhase == 2 ? 2 * kBsMaxNv : 2];           // the points g and u
     __shared__ uint4 eq_g[2 * 2 * kGsHalf], eq_u[kPhase == 2 ? 2 * 2 * kGsHalf : 2];     // lo | hi half tables, 32-byte elements
+    __shared__ uint4 eq_g2[kPoints == 2 ? 2 * 2 * kGsHalf : 2];                          // two-point form: g2's half tables
     const uint32_t tid = threadIdx.x, inst = blockIdx.x / A.blocks_per_inst, blk = blockIdx.x % A.blocks_per_inst; // (the grid is exactly n x blocks_per_inst)
     const uint32_t dim = A.dim, mask = (1u << dim) - 1u, kl = (dim + 1) / 2, lmask = (1u << kl) - 1u;
     const GkrBatchInst I = A.inst[inst];
@@ -54,11 +59,21 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_terms(const BatchGkrSlic
     __syncthreads();
     bg_build_eq_halves(eq_g, eq_g + 2 * kGsHalf, g_sh, dim);
     if (kPhase == 2) bg_build_eq_halves(eq_u, eq_u + 2 * kGsHalf, u_sh, dim);
+    if (kPoints == 2) {
+        bg_build_eq_halves(eq_g2, eq_g2 + 2 * kGsHalf, A.g2 + 2 * (size_t)inst * dim, dim);
+        const Fr alpha = fr_load(A.coef + 4 * (size_t)inst), beta = fr_load(A.coef + 4 * (size_t)inst + 2);
+        for (uint32_t t = tid; t <= lmask; t += kTsBlock) {
+            fr_store(eq_g + 2 * t, fr_mul(alpha, fr_load(eq_g + 2 * t)));
+            fr_store(eq_g2 + 2 * t, fr_mul(beta, fr_load(eq_g2 + 2 * t)));
+        }
+        __syncthreads();
+    }
     const uint64_t stride = (uint64_t)A.blocks_per_inst * kTsBlock;
     for (uint64_t i = (uint64_t)blk * kTsBlock + tid; i < I.nnz; i += stride) {
         const uint64_t id = I.idx[i];
         const uint32_t z = (uint32_t)id & mask, x = (uint32_t)(id >> dim) & mask, y = (uint32_t)(id >> (2 * dim)) & mask;
-        const Fr eg = fr_mul(fr_load(eq_g + 2 * (z & lmask)), fr_load(eq_g + 2 * kGsHalf + 2 * (z >> kl)));
+        Fr eg = fr_mul(fr_load(eq_g + 2 * (z & lmask)), fr_load(eq_g + 2 * kGsHalf + 2 * (z >> kl)));
+        if (kPoints == 2) eg = fr_add(eg, fr_mul(fr_load(eq_g2 + 2 * (z & lmask)), fr_load(eq_g2 + 2 * kGsHalf + 2 * (z >> kl))));
         const Fr a = fr_mul(eg, fr_load(I.vals + 2 * i));
         Fr t;
         if (kPhase == 1) t = fr_mul(a, fr_load(I.f3 + 2 * (size_t)y));
@@ -95,15 +110,21 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_fold(const BatchGkrSlice
     }
 }
 
-hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream) {
+hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream, int points) {
+    if ((points != 1 && points != 2) || (points == 2 && (!args.g2 || !args.coef))) return hipErrorInvalidValue;
     if ((phase != 1 && phase != 2) || args.n == 0 || args.dim <= (uint32_t)kGkrBatchMaxDim || args.dim > kBsMaxNv || !args.inst || !args.work_a || !args.cells) return hipErrorInvalidValue;
     if (phase == 2 && (!args.work_b || !args.u || !args.f2u)) return hipErrorInvalidValue;
     if (nnz_max > (kGkrBatchMaxNnzPerCell << args.dim)) return hipErrorInvalidValue; // (the lanes' bound)
     const uint64_t B = gkr_bs_term_blocks(nnz_max), grid_terms = (uint64_t)args.n * B, grid_fold = (((uint64_t)args.n << args.dim) + kTsBlock - 1) / kTsBlock;
     if (grid_terms >= (1ULL << 31) || grid_fold >= (1ULL << 31)) return hipErrorInvalidValue;
     args.blocks_per_inst = (uint32_t)B;
-    if (phase == 1) hipLaunchKernelGGL(k_batch_gkr_terms<1>, dim3((uint32_t)grid_terms), dim3(kTsBlock), 0, stream, args);
-    else hipLaunchKernelGGL(k_batch_gkr_terms<2>, dim3((uint32_t)grid_terms), dim3(kTsBlock), 0, stream, args);
+    if (points == 1) {
+        if (phase == 1) hipLaunchKernelGGL((k_batch_gkr_terms<1, 1>), dim3((uint32_t)grid_terms), dim3(kTsBlock), 0, stream, args);
+        else hipLaunchKernelGGL((k_batch_gkr_terms<2, 1>), dim3((uint32_t)grid_terms), dim3(kTsBlock), 0, stream, args);
+    } else {
+        if (phase == 1) hipLaunchKernelGGL((k_batch_gkr_terms<1, 2>), dim3((uint32_t)grid_terms), dim3(kTsBlock), 0, stream, args);
+        else hipLaunchKernelGGL((k_batch_gkr_terms<2, 2>), dim3((uint32_t)grid_terms), dim3(kTsBlock), 0, stream, args);
+    }
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     if (phase == 1) hipLaunchKernelGGL(k_batch_gkr_fold<1>, dim3((uint32_t)grid_fold), dim3(kTsBlock), 0, stream, args);
     else hipLaunchKernelGGL(k_batch_gkr_fold<2>, dim3((uint32_t)grid_fold), dim3(kTsBlock), 0, stream, args);

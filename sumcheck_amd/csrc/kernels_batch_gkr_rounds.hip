@@ -15,12 +15,24 @@
 // Every index is masked to dim bits per component before it addresses LDS or f3 (bg_accumulate); an index with a bit at or above 3 dim
 // is an argument error that k_batch_gkr_idx_range reports in front of the first launch that follows the indices.
 // LDS: eq(g, .) | eq(u, .) (32 B per cell) | the accumulator (64 B per cell, also bg_build_eq's scratch): 128 B x 2^dim; no tables.
+// k_batch_gkr_phase<kPhase, 2> is the two-point form (sc_gkr_two_point_*): alpha eq(g, .) + beta eq(g2, .) stands where eq(g, .) stands,
+// inside the same LDS; k_gkr_two_point_combine is the serial plan's share of it.
 // Behind them k_batch_gkr_restage: the copy kernel that brings the next layer's device arrays into a handle (sc_gkr_layer_next_batch).
 #include "batch_round.hpp"
 
 namespace scd {
 
-template <int kPhase>
+// kPoints 2 (sc_gkr_two_point_*): eq_g <- alpha eq(g, .) + beta eq(g2, .), canonical (fr_mul, fr_add), with eq(g2, .) built in eq(u, .)'s
+// region -- unused in phase 1, rebuilt behind this in phase 2 -- and the cells as bg_build_eq's scratch.  g2 and the coefficients are read
+// from the handle's device copies (uniform loads).  Ends behind a barrier.
+__device__ __forceinline__ void bg_fold_second_point(uint4 *eq_g, uint4 *eq_g2, uint4 *tmp, const uint4 *g2, const uint4 *coef, const uint32_t dim) {
+    bg_build_eq(eq_g2, tmp, g2, dim);
+    const Fr alpha = fr_load(coef), beta = fr_load(coef + 2);
+    for (uint32_t b = threadIdx.x; b < (1u << dim); b += kTsBlock) fr_store(eq_g + 2 * b, fr_add(fr_mul(alpha, fr_load(eq_g + 2 * b)), fr_mul(beta, fr_load(eq_g2 + 2 * b))));
+    __syncthreads();
+}
+
+template <int kPhase, int kPoints>
 __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_phase(const BatchGkrPhaseArgs A) {
     extern __shared__ uint4 dyn_lds[];
     __shared__ uint4 g_sh[2 * kGkrBatchMaxDim], u_sh[2 * kGkrBatchMaxDim]; // the points g and u
@@ -37,6 +49,7 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_phase(const BatchGkrPhas
     }
     __syncthreads();
     bg_build_eq(eq_g, reinterpret_cast<uint4 *>(cell), g_sh, dim);
+    if (kPoints == 2) bg_fold_second_point(eq_g, eq_u, reinterpret_cast<uint4 *>(cell), A.g2 + 2 * (size_t)inst * dim, A.coef + 4 * (size_t)inst, dim);
     if (kPhase == 1) {
         bg_accumulate<1>(cell, I, dim, eq_g, eq_g, [&](const uint32_t c, const Fe &v) { br_slot_store(dst + (size_t)c * kBtEnt, v); });
         for (uint32_t e = tid; e < cap; e += kTsBlock) br_slot_store(dst + ((size_t)2 * cap + e) * kBtEnt, fe_from_fr(fr_load(I.f2 + 2 * (size_t)e)));
@@ -53,12 +66,34 @@ __global__ __launch_bounds__(kTsBlock) void k_batch_gkr_phase(const BatchGkrPhas
     }
 }
 
-hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream) {
+hipError_t launch_batch_gkr_phase(int phase, const BatchGkrPhaseArgs &args, hipStream_t stream, int points) {
     if ((phase != 1 && phase != 2) || args.n == 0 || !gkr_batch_shape_fits(args.dim, 0) || !args.inst || !args.work_a) return hipErrorInvalidValue;
     if (phase == 2 && (!args.work_b || !args.u || !args.f2u)) return hipErrorInvalidValue;
+    if ((points != 1 && points != 2) || (points == 2 && (!args.g2 || !args.coef))) return hipErrorInvalidValue;
     const size_t lds = (size_t)128 << args.dim; // (at most 64 KB: within a launch's default limit)
-    if (phase == 1) hipLaunchKernelGGL(k_batch_gkr_phase<1>, dim3(args.n), dim3(kTsBlock), lds, stream, args);
-    else hipLaunchKernelGGL(k_batch_gkr_phase<2>, dim3(args.n), dim3(kTsBlock), lds, stream, args);
+    if (points == 1) {
+        if (phase == 1) hipLaunchKernelGGL((k_batch_gkr_phase<1, 1>), dim3(args.n), dim3(kTsBlock), lds, stream, args);
+        else hipLaunchKernelGGL((k_batch_gkr_phase<2, 1>), dim3(args.n), dim3(kTsBlock), lds, stream, args);
+    } else {
+        if (phase == 1) hipLaunchKernelGGL((k_batch_gkr_phase<1, 2>), dim3(args.n), dim3(kTsBlock), lds, stream, args);
+        else hipLaunchKernelGGL((k_batch_gkr_phase<2, 2>), dim3(args.n), dim3(kTsBlock), lds, stream, args);
+    }
+    return hipGetLastError();
+}
+
+// The serial plan's two-point tables (sc_gkr_two_point_*): out[e] = alpha a[e] + beta b[e] on canonical elements, one lane per element
+// with a grid stride; out may be a or b (an element is read before it is written, by the same lane).
+__global__ __launch_bounds__(kTsBlock) void k_gkr_two_point_combine(const uint4 *a, const uint4 *b, const uint4 *__restrict__ coef, uint4 *out, const uint64_t count) {
+    const Fr alpha = fr_load(coef), beta = fr_load(coef + 2);
+    const uint64_t stride = (uint64_t)gridDim.x * kTsBlock;
+    for (uint64_t e = (uint64_t)blockIdx.x * kTsBlock + threadIdx.x; e < count; e += stride)
+        fr_store(out + 2 * e, fr_add(fr_mul(alpha, fr_load(a + 2 * e)), fr_mul(beta, fr_load(b + 2 * e))));
+}
+
+hipError_t launch_gkr_two_point_combine(const uint4 *a, const uint4 *b, const uint4 *coef, uint4 *out, uint64_t count, hipStream_t stream) {
+    if (!a || !b || !coef || !out || count == 0) return hipErrorInvalidValue;
+    const uint64_t blocks = (count + kTsBlock - 1) / kTsBlock;
+    hipLaunchKernelGGL(k_gkr_two_point_combine, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(kTsBlock), 0, stream, a, b, coef, out, count);
     return hipGetLastError();
 }
 

@@ -194,6 +194,44 @@ class GKRRoundSumcheckSubClaim:  # data_structures.rs:22-31
         ev = GKRRoundSumcheck.evaluate_subclaims_batch(f1s, f2s, f3s, gs, uv)
         return [bool(np.array_equal(ev[i, 3], _np64(c.expected_evaluation).reshape(4))) for i, c in enumerate(subclaims)]
 
+    def verify_subclaim_two_point(self, f1: SparseMultilinearExtension, f2: DenseMultilinearExtension, f3: DenseMultilinearExtension, g, g2, alpha, beta) -> bool:
+        """verify_subclaim for a round proved in two-point form: (alpha f1(g,u,v) + beta f1(g2,u,v)) f2(u) f3(v) against expected_evaluation"""
+        return GKRRoundSumcheckSubClaim.verify_subclaim_two_point_batch([self], [f1], [f2], [f3], [g], [g2], [np.stack([_np64(alpha).reshape(4), _np64(beta).reshape(4)])])[0]
+
+    @staticmethod
+    def verify_subclaim_two_point_batch(subclaims: Sequence["GKRRoundSumcheckSubClaim"], f1s, f2s, f3s, gs, g2s, coeffs) -> List[bool]:
+        """n subclaims of rounds proved in two-point form, from existing calls only: GKRRoundSumcheck.evaluate_subclaims_batch once over the
+        gs and once over the g2s, then (alpha f1(g,u,v) + beta f1(g2,u,v)) f2(u) f3(v) in host field arithmetic.  coeffs: per instance
+        (alpha, beta), (2, 4) limbs"""
+        n = len(subclaims)
+        assert len(f1s) == n and len(f2s) == n and len(f3s) == n and len(gs) == n and len(g2s) == n and len(coeffs) == n, "one f1, f2, f3, g, g2 and (alpha, beta) per subclaim"
+        if n == 0:
+            return []
+        uv = np.stack([np.concatenate([_np64(c.u).reshape(-1, 4), _np64(c.v).reshape(-1, 4)]) for c in subclaims])
+        e1 = GKRRoundSumcheck.evaluate_subclaims_batch(f1s, f2s, f3s, gs, uv)
+        e2 = GKRRoundSumcheck.evaluate_subclaims_batch(f1s, f2s, f3s, g2s, uv)
+        out = []
+        for i, c in enumerate(subclaims):
+            ab = _np64(coeffs[i]).reshape(2, 4)
+            f1v = (field.to_int(ab[0]) * field.to_int(e1[i, 0]) + field.to_int(ab[1]) * field.to_int(e2[i, 0])) % field.P
+            out.append(f1v * field.to_int(e1[i, 1]) % field.P * field.to_int(e1[i, 2]) % field.P == field.to_int(c.expected_evaluation))
+        return out
+
+
+def _second_point(g2s, coeffs, n: int, dim: int):
+    """the two-point form's extra arguments -> None (one-point form), or (n arrays (dim, 4), one array (n, 2, 4))"""
+    if (g2s is None) != (coeffs is None):
+        raise ValueError("g2s and coeffs come together (the two-point form) or not at all")
+    if g2s is None:
+        return None
+    if len(g2s) != n or len(coeffs) != n:
+        raise ValueError("one g2 and one (alpha, beta) per instance")
+    g2_arr = [np.ascontiguousarray(_np64(a).reshape(-1, 4)) for a in g2s]
+    if any(a.shape[0] != dim for a in g2_arr):
+        raise ValueError(f"a g2 has dim elements ({dim})")
+    coef = np.ascontiguousarray(np.stack([_np64(c).reshape(2, 4) for c in coeffs])) if n else np.zeros((0, 2, 4), np.uint64)
+    return g2_arr, coef
+
 
 def _verify_phase(rng: Blake2b512Rng, msgs: Sequence[ProverMsg], dim: int, asserted_sum):
     """verifier_init{max_multiplicands: 2} + verify_round x dim + check_and_generate_subclaim (mod.rs:157-166)"""
@@ -315,15 +353,19 @@ class GKRRoundSumcheck:
 
     @staticmethod
     def prover_init_batch(f1s: Sequence[SparseMultilinearExtension], f2s: Sequence[DenseMultilinearExtension],
-                          f3s: Sequence[DenseMultilinearExtension], gs) -> "GKRBatchProverState":
+                          f3s: Sequence[DenseMultilinearExtension], gs, g2s=None, coeffs=None) -> "GKRBatchProverState":
         """n x the two prover states of GKRRoundSumcheck.prove of one dim behind one handle (sc_gkr_batch_prover_init): the interactive
         rounds under the CALLER's transcript -- 2 dim calls of prove_round, then finish.  Inputs as for prove_batch (all on the host or
         all on the GPU; the same object may stand for several instances); they are copied: nothing is read after this returns.
         Plans: dim <= 9 runs one block per instance; under _lib.policy(batch_slices=1), set when the handle is built, dim 10 .. 16
         (nnz <= 64 x 2^dim, at most 16 GiB) gives every instance to many blocks (plan batch.gkr_rounds_slices: same bits); other
-        shapes take the serial plan."""
+        shapes take the serial plan.
+        g2s and coeffs (both or neither) build the handle in TWO-POINT form (sc_gkr_two_point_init_batch): per instance a second point
+        g2 and (alpha, beta); alpha eq(g, .) + beta eq(g2, .) stands where eq(g, .) stands, so the handle proves
+        alpha W(g) + beta W(g2) = sum (alpha f1(g,x,y) + beta f1(g2,x,y)) f2(x) f3(y) -- a GKR layer below the output layer."""
         n = len(f1s)
         assert len(f2s) == n and len(f3s) == n and len(gs) == n, "one f1, f2, f3 and g per instance"
+        second = _second_point(g2s, coeffs, n, f2s[0].num_vars if n else 0)
         dim = f2s[0].num_vars if n else 0
         ons = [m.on_device for m in list(f1s) + list(f2s) + list(f3s)]
         dev = bool(ons) and all(ons)
@@ -343,8 +385,14 @@ class GKRRoundSumcheck:
         f1p = [f._ptrs() for f in f1s]
         nnz = (C.c_uint64 * max(n, 1))(*[f.nnz for f in f1s])
         h = C.c_void_p()
-        check(lib().sc_gkr_batch_prover_init(n, dim, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
-                                             ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), SC_TABLES_ON_DEVICE if dev else 0, C.byref(h)))
+        if second is None:
+            check(lib().sc_gkr_batch_prover_init(n, dim, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
+                                                 ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), SC_TABLES_ON_DEVICE if dev else 0, C.byref(h)))
+        else:
+            g2_arr, coef = second
+            check(lib().sc_gkr_two_point_init_batch(n, dim, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
+                                                    ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), ptrs([_ptr(a) for a in g2_arr]), _ptr(coef),
+                                                    SC_TABLES_ON_DEVICE if dev else 0, C.byref(h)))
         return GKRBatchProverState(h, n, dim)
 
     @staticmethod
@@ -407,13 +455,16 @@ class GKRBatchProverState:
     def reset(self) -> None:
         check(lib().sc_gkr_batch_prover_reset(self._h))
 
-    def next_layer(self, f2s, f3s, gs, f1s=None) -> None:
+    def next_layer(self, f2s, f3s, gs, f1s=None, g2s=None, coeffs=None) -> None:
         """The handle onto the next layer's inputs (sc_gkr_layer_next_batch): nothing is allocated, and afterwards the handle is at round 0
         exactly as prover_init_batch over these inputs would leave it -- same plan, same bits.  f1s=None keeps the wiring the handle
         holds.  Inputs are where prover_init_batch's were (all on the host, or all on the GPU) and are copied: nothing is read after this
         returns.  Callable in any state; an argument error leaves the handle where it was.  The copy fits whenever the objects repeat in
-        the pattern prover_init_batch's did and f1 is kept or has no more non-zeros per instance than it had there."""
+        the pattern prover_init_batch's did and f1 is kept or has no more non-zeros per instance than it had there.
+        g2s and coeffs (both or neither) put the handle onto a layer in TWO-POINT form (sc_gkr_two_point_next_batch), whichever form it
+        was built in; without them the layer is in one-point form."""
         n, dim = self.n, self.dim
+        second = _second_point(g2s, coeffs, n, dim)
         assert len(f2s) == n and len(f3s) == n and len(gs) == n and (f1s is None or len(f1s) == n), "one f2, f3 and g (and f1) per instance"
         ons = [m.on_device for m in list(f1s or []) + list(f2s) + list(f3s)]
         dev = all(ons)
@@ -431,9 +482,13 @@ class GKRBatchProverState:
             return (C.c_void_p * n)(*[C.cast(v, C.c_void_p) for v in vals])
 
         f1p = [f._ptrs() for f in f1s] if f1s is not None else None
-        check(lib().sc_gkr_layer_next_batch(self._h, ptrs([p[0] for p in f1p]) if f1p else None, ptrs([p[1] for p in f1p]) if f1p else None,
-                                            (C.c_uint64 * n)(*[f.nnz for f in f1s]) if f1p else None, ptrs([_dense_ptr(m) for m in f2s]),
-                                            ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]), SC_TABLES_ON_DEVICE if dev else 0))
+        head = (self._h, ptrs([p[0] for p in f1p]) if f1p else None, ptrs([p[1] for p in f1p]) if f1p else None, (C.c_uint64 * n)(*[f.nnz for f in f1s]) if f1p else None,
+                ptrs([_dense_ptr(m) for m in f2s]), ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]))
+        if second is None:
+            check(lib().sc_gkr_layer_next_batch(*head, SC_TABLES_ON_DEVICE if dev else 0))
+        else:
+            g2_arr, coef = second
+            check(lib().sc_gkr_two_point_next_batch(*head, ptrs([_ptr(a) for a in g2_arr]), _ptr(coef), SC_TABLES_ON_DEVICE if dev else 0))
 
     def close(self) -> None:
         if self._h:
