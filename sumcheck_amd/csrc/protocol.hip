@@ -2,9 +2,8 @@
 // (reference src/ml_sumcheck/mod.rs:50-70): sc_prove_round (launches, the resident kernel of the interactive protocol), the
 // Fiat-Shamir loop with pipelined late rounds and the persistent tail kernel, sc_ml_prove*, and the sharded proof of one rank.
 #include "prover_internal.hpp"
+#include "round_slots.hpp"
 
-// Launch one round's kernels on p->stream.  On return the round polynomial is in p->d_out (and in
-// d_wide if non-null); nothing has been synchronised.
 uint64_t small_pairs_limit() { // the big/small round boundary
 #ifdef SC_EXPERIMENTS // SC_SMALL_LOG2
     static const uint64_t v = [] {
@@ -185,33 +184,50 @@ int materialize_lagging(sc_prover *p, bool catch_up) {
             A.dst = t.buf[t.next];
             scd::plan_hit(catch_up ? scd::kPlanBigLagCatchUp : scd::kPlanBigLagMaterialize);
             HIP_TRY(scd::launch_fix_deep(A, p->use_f29, p->stream));
-            t.cur = t.buf[t.next];
-            t.cur_f29 = p->use_f29;
-            t.next ^= 1;
+            scd::flip_table(t, p->use_f29);
         }
     }
     lag_clear(p);
     return SC_OK;
 }
 
-// Rounds 1 and 2 of a handle whose tables stay in host memory (SC_TABLES_STREAM).  The round is the sum of its chunks: chunk c = entries
+// ---- what every big-round plan shares: the argument checks and the slot rule (round_slots.hpp) over device pointers ----
+using SrcBuf = scd::TableBuf<const uint4 *>;
+using LaunchStores = scd::LaunchStores<const uint4 *>;
+static_assert(4 * scd::kMaxRoundProds <= scd::kMaxLaunchStores && scd::kMaxFusedM <= scd::kMaxLaunchStores, "a launch's stores must fit their scope");
+static scd::TreeProd &tree_row(scd::RoundArgs &ra, uint32_t row, const Product &pr) { // a row of the merged launch, before its slots
+    ra.prod[row].M = pr.M;
+    ra.prod[row].partial_off = pr.partial_off;
+    return ra.prod[row];
+}
+// Validation, same precedence as the reference's panics (prover.rs:78-98), before the first change to the handle.  r: the challenge, if any.
+static int check_round_args(const sc_prover *p, const uint64_t *r_or_null, bool deferred, sch::Fr &r) {
+    if (p->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
+    if (p->deferred_pending) return sc_internal_fail(SC_ERR_BAD_ARG, "a pipelined round is waiting for its challenge");
+    if (r_or_null && p->round == 0) return sc_internal_fail(SC_ERR_FIRST_ROUND_HAS_MSG, "first round should be prover first.");
+    if (!r_or_null && p->round > 0 && !deferred) return sc_internal_fail(SC_ERR_MISSING_MSG, "verifier message is empty");
+    if (p->round + 1 > p->nv) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
+    if (r_or_null) {
+        std::memcpy(&r, r_or_null, 32);
+        if (sch::geq_p(r)) return sc_internal_fail(SC_ERR_BAD_ARG, "challenge is not a canonical field element");
+    }
+    const uint64_t np = 1ULL << (p->nv - (p->round + 1));
+    if (deferred && !(np <= small_pairs_limit() && p->U <= (uint32_t)scd::kMaxSmallTables && p->K > 0)) return sc_internal_fail(SC_ERR_BAD_ARG, "only late rounds are pipelined");
+    return SC_OK;
+}
+
+// Rounds 1 and 2 of a handle whose tables stay in host memory (SC_TABLES_STREAM). The round is the sum of its chunks: chunk c = entries
 // [c 2^L, (c+1) 2^L) of every table goes host -> staging slot c & 1 on the copy stream while the previous chunk computes; the merged
 // big-round kernel runs on the slot (round 1: sums only; round 2: bind + sums, the bound half-chunk written to its place in the
 // resident table), k_finalize turns the chunk's partials into a message and k_msg_accumulate adds it to the round's.  After round 2 the
 // bound tables (half the input) are resident and the ordinary path takes over.
 int launch_round_streamed(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool publish_to_host) {
     scd::plan_hit(scd::kPlanBigStreamed);
-    if (p->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
-    if (r_or_null && p->round == 0) return sc_internal_fail(SC_ERR_FIRST_ROUND_HAS_MSG, "first round should be prover first.");
-    if (!r_or_null && p->round > 0) return sc_internal_fail(SC_ERR_MISSING_MSG, "verifier message is empty");
     sch::Fr r = sch::zero();
-    if (r_or_null) {
-        std::memcpy(&r, r_or_null, 32);
-        if (sch::geq_p(r)) return sc_internal_fail(SC_ERR_BAD_ARG, "challenge is not a canonical field element");
-    }
-    HIP_TRY(hipSetDevice(p->device));
-    int rc_t = collect_timing(p);
+    int rc_t = check_round_args(p, r_or_null, false, r); // (rounds 1 and 2 of nv >= 11, never deferred: neither deferred_pending, nor round + 1 > nv, nor the late-round check can trip)
     if (rc_t) return rc_t;
+    HIP_TRY(hipSetDevice(p->device));
+    if ((rc_t = collect_timing(p))) return rc_t;
     const bool bind = r_or_null != nullptr;
     if (bind) p->randomness.push_back(r);
     p->round += 1;
@@ -234,57 +250,28 @@ int launch_round_streamed(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_w
         HIP_TRY(hipEventRecord(p->ev_copied[q], p->copy_stream));
         HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_copied[q], 0));
         auto ring_tab = [&](uint32_t u) { return reinterpret_cast<const uint4 *>(static_cast<char *>(p->ring[q]) + (((size_t)u << p->chunk_log2) * 32)); };
+        // this chunk's half of the bound table, in place (F29 blocks of 128 entries stay aligned: C / 2 >= 512); the tables move after the loop
+        auto chunk_dst = [&](uint32_t u) { return p->tabs[u].buf[0] + 2 * (c * (C / 2)); };
+        LaunchStores stores;
         if (merged) {
             scd::RoundArgs ra;
             std::memset(&ra, 0, sizeof(ra));
             ra.n_prod = (int)p->K;
             std::vector<uint8_t> bound(p->U, 0);
-            for (uint32_t k = 0; k < p->K; ++k) {
-                const Product &pr = p->prods[k];
-                scd::TreeProd &tp = ra.prod[k];
-                tp.M = pr.M;
-                tp.partial_off = pr.partial_off;
-                int f = 0;
-                for (size_t s = 0; s < pr.tables.size(); ++s) {
-                    const uint32_t u = pr.tables[s];
-                    Table &t = p->tabs[u];
-                    for (uint32_t rep = 0; rep < pr.exps[s]; ++rep, ++f) {
-                        scd::Slot &sl = tp.slot[f];
-                        sl.exp = 1;
-                        sl.src = ring_tab(u);
-                        sl.src_f29 = 0;
-                        if (!bind) {
-                            sl.mode = 0;
-                        } else if (!bound[u]) { // this chunk's half of the bound table, in place (F29 blocks of 128 entries stay aligned: C / 2 >= 512)
-                            sl.mode = 1;
-                            sl.dst = t.buf[0] + 2 * (c * (C / 2));
-                            sl.dst_f29 = p->use_f29 ? 1 : 0;
-                            bound[u] = 1;
-                        } else {
-                            sl.mode = 3;
-                            sl.dst_f29 = p->use_f29 ? 1 : 0;
-                        }
-                    }
-                }
-            }
+            for (uint32_t k = 0; k < p->K; ++k)
+                scd::fill_factor_slots(tree_row(ra, k, p->prods[k]).slot, p->prods[k].tables, p->prods[k].exps, bind, bound.data(), stores, p->use_f29 ? 1u : 0u,
+                                       [&](uint32_t u) { return SrcBuf{ring_tab(u), 0u}; }, chunk_dst);
             HIP_TRY(scd::launch_round_tree(ra, rc, pairs_per_chunk, p->d_partials, grid, p->stream, true));
-            if (bind) { // tables no product refers to still follow the state machine
-                for (uint32_t u = 0; u < p->U; ++u)
-                    if (!bound[u]) HIP_TRY(scd::launch_fix(ring_tab(u), p->tabs[u].buf[0] + 2 * (c * (C / 2)), to_dev(r), C / 2, p->stream));
-            }
+            for (uint32_t u = 0; u < p->U && bind; ++u) // tables no product refers to still follow the state machine
+                if (!bound[u]) HIP_TRY(scd::launch_fix(ring_tab(u), chunk_dst(u), to_dev(r), C / 2, p->stream));
         } else {
             // Any other shape (more than 12 products, more than four multiplicands): the chunk is bound table by table (k_fix, into its
             // place in the resident table, canonical reference layout) and every product then sums over what it needs -- the staged chunk
-            // in round 1, the freshly bound half-chunk in round 2 -- with the kernel launch_round would give it.
+            // in round 1, the freshly bound half-chunk in round 2 -- with the kernel launch_round would give it.  No slot binds.
             std::vector<const uint4 *> src(p->U);
             for (uint32_t u = 0; u < p->U; ++u) {
-                if (bind) {
-                    uint4 *dst = p->tabs[u].buf[0] + 2 * (c * (C / 2));
-                    HIP_TRY(scd::launch_fix(ring_tab(u), dst, to_dev(r), C / 2, p->stream));
-                    src[u] = dst;
-                } else {
-                    src[u] = ring_tab(u);
-                }
+                src[u] = bind ? chunk_dst(u) : ring_tab(u);
+                if (bind) HIP_TRY(scd::launch_fix(ring_tab(u), chunk_dst(u), to_dev(r), C / 2, p->stream));
             }
             bool ptrs_uploaded = false;
             for (uint32_t k = 0; k < p->K; ++k) {
@@ -293,22 +280,10 @@ int launch_round_streamed(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_w
                 ProdArgs a;
                 std::memset(&a, 0, sizeof(a));
                 if (pr.fused && p->kernel_variant == 3 && pr.M <= 4) { // product tree: one slot per FACTOR
-                    a.n_slots = (int)pr.M;
-                    int f = 0;
-                    for (size_t s2 = 0; s2 < pr.tables.size(); ++s2)
-                        for (uint32_t rep = 0; rep < pr.exps[s2]; ++rep, ++f) {
-                            a.slot[f].exp = 1;
-                            a.slot[f].mode = 0;
-                            a.slot[f].src = src[pr.tables[s2]];
-                        }
+                    a.n_slots = scd::fill_factor_slots(a.slot, pr.tables, pr.exps, false, nullptr, stores, 0u, [&](uint32_t u) { return SrcBuf{src[u], 0u}; }, chunk_dst);
                     HIP_TRY(scd::launch_prod_tree((int)pr.M, a, rc, pairs_per_chunk, partials, grid, p->stream));
                 } else if (pr.fused) { // node by node, carry-free arithmetic: one slot per distinct table
-                    a.n_slots = (int)pr.tables.size();
-                    for (size_t s2 = 0; s2 < pr.tables.size(); ++s2) {
-                        a.slot[s2].exp = pr.exps[s2];
-                        a.slot[s2].mode = 0;
-                        a.slot[s2].src = src[pr.tables[s2]];
-                    }
+                    a.n_slots = scd::fill_table_slots(a.slot, pr.tables, pr.exps, false, nullptr, [&](uint32_t u) { return src[u]; }, chunk_dst);
                     HIP_TRY(scd::launch_prod_round_fe((int)pr.M, a, r32, pairs_per_chunk, partials, grid, p->stream));
                 } else { // any number of multiplicands: table pointers through device memory, one set per staging slot
                     if (!ptrs_uploaded) {
@@ -346,8 +321,6 @@ int launch_round_streamed(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_w
     return SC_OK;
 }
 
-// deferred = true (library-internal): the challenge does not exist yet.  The round is enqueued behind a wait on p->sig and its
-// bind kernel reads the challenge from the mailbox; provide_challenge() supplies it later.  Late (small) rounds only.
 // SC_HOST_TRACE: report any single HIP call of a round's launch sequence that takes longer than a millisecond (stderr)
 struct SlowCallProbe {
     const char *what;
@@ -370,7 +343,6 @@ struct SlowCallProbe {
 // the sequence number round 1 will have, and keeps the node sums for round 2's claim identity -- exactly what an ordinary round 1 leaves.
 // The tables are resident and the caller's memory is no longer referenced when sc_prover_init returns, as the reference's ownership has
 // it; the first sc_prove_round finds its message waiting.  Shapes of the merged big-round kernel with at least 2^18 entries per table.
-bool fin_mb_enabled();
 bool staged_init_applies(const sc_prover *p) {
     return scd::policy(scd::kPolStagedInit) != 0 && p->merge_rounds && !p->any_generic && !p->streamed && !p->borrow && !p->fused_finalize && p->kernel_variant == 3 &&
            p->nv >= 18 && p->K > 0 && p->K <= (uint32_t)scd::kMetaProds;
@@ -384,10 +356,11 @@ int staged_copy_and_round1(sc_prover *p, const uint64_t *const *host_tables) {
         if (!p->ev_copied2[q]) HIP_TRY(hipEventCreateWithFlags(&p->ev_copied2[q], hipEventDisableTiming));
     }
     const uint64_t n = 1ULL << p->nv, n_pairs = n >> 1;
-    // the grid an ordinary round 1 of this shape takes (launch_round), cut into one section per chunk
+    // The grid of the merged launch, cut into one section per chunk: min(merged_row_blocks(n_pairs, K, 0, /*by_rows=*/false), grid_for_pairs)
+    // (lane_sum.hpp; tests/cpp/test_lane_sum.cpp holds the two equal).  Spelled out, because the suite's case generator reads the ladder
+    // here.  The sections of a staged round 1 have never been scaled by rows; whether they should be is a measurement for another change.
     int G = n_pairs >= (1ULL << 21) ? 1024 : n_pairs >= (1ULL << 20) ? 768 : n_pairs >= (1ULL << 18) ? 384 : n_pairs >= (1ULL << 17) ? 256 : 192;
-    if (p->K == 1) G = std::min(G, scd::kRoundTreeGrid);
-    G = std::min(G, scd::grid_for_pairs(n_pairs));
+    G = std::min(p->K == 1 ? std::min(G, scd::kRoundTreeGrid) : G, scd::grid_for_pairs(n_pairs));
     // Chunks of a half, a quarter, ... and the last two of equal size (1/32 of the tables from 2^21 entries, a quarter below): what is
     // left of round 1 when the last byte has arrived is the kernel over the LAST chunk alone.  The sections of the grid are not in
     // proportion: the early chunks' kernels hide under the copy whatever their grid, the late ones get an eighth of the blocks each so
@@ -432,19 +405,11 @@ int staged_copy_and_round1(sc_prover *p, const uint64_t *const *host_tables) {
         scd::RoundArgs ra;
         std::memset(&ra, 0, sizeof(ra));
         ra.n_prod = (int)p->K;
-        for (uint32_t k = 0; k < p->K; ++k) {
-            const Product &pr = p->prods[k];
-            scd::TreeProd &tp = ra.prod[k];
-            tp.M = pr.M;
-            tp.partial_off = pr.partial_off;
-            int f = 0;
-            for (size_t s2 = 0; s2 < pr.tables.size(); ++s2)
-                for (uint32_t rep = 0; rep < pr.exps[s2]; ++rep, ++f) {
-                    tp.slot[f].exp = 1;
-                    tp.slot[f].mode = 0;
-                    tp.slot[f].src = p->tabs[pr.tables[s2]].buf[0] + 2 * (size_t)first; // (an element is two uint4)
-                }
-        }
+        LaunchStores none; // (round 1 binds nothing)
+        for (uint32_t k = 0; k < p->K; ++k)
+            scd::fill_factor_slots(tree_row(ra, k, p->prods[k]).slot, p->prods[k].tables, p->prods[k].exps, false, nullptr, none, 0u,
+                                   [&](uint32_t u) { return SrcBuf{p->tabs[u].buf[0] + 2 * (size_t)first, 0u}; }, // (an element is two uint4)
+                                   [](uint32_t) { return (uint4 *)nullptr; });
         ra.part_stride = (uint32_t)G;
         ra.part_block0 = (uint32_t)block0;
         HIP_TRY(scd::launch_round_tree(ra, rc, chunk >> 1, p->d_partials, gc, p->stream, true, false));
@@ -460,6 +425,394 @@ int staged_copy_and_round1(sc_prover *p, const uint64_t *const *host_tables) {
     return SC_OK;
 }
 
+// ---- launch_round: one call's state, and its stages in the order they run ----
+struct RoundCtx {
+    sch::Fr r = sch::zero();
+    FrHost rdev, r32; // the challenge, and r * 2^5 for the 2^261-radix kernels
+    scd::BindConst rc; // tree kernels: rows (r * 2^(29 i + 58)) mod p as plain 29-bit limbs (only their big rounds pay for it)
+    uint64_t n_pairs = 0, *d_wide = nullptr;
+    const FrHost *r_mail = nullptr; // a pipelined round: where its bind kernel finds the challenge
+    int grid = 0, scaled = 0;
+    bool bind = false, deferred = false, publish_to_host = false, small = false, merged = false, tiled = false, timed = false;
+    bool lag_class = false; // a merged round before the catch-up round: the lagging products' rows bind their class tables
+    bool skip1 = false;     // the round kernel leaves node 1 out (ClaimArgs)
+    bool finalized = false; // the merged big-round launch also produced the message
+    std::vector<uint8_t> bound; // per table, 1: bound by this round; 2: bound up to and including this round's challenge by k_fix_deep
+};
+
+// The resident tables under the slot rule: a factor reads the table's current buffer; a bind stores into the spare one and the table moves there.
+static int resident_factor_slots(sc_prover *p, scd::Slot *slot, const Product &pr, RoundCtx &c, LaunchStores &stores) {
+    return scd::fill_factor_slots(slot, pr.tables, pr.exps, c.bind, c.bound.data(), stores, p->use_f29 ? 1u : 0u,
+                                  [&](uint32_t u) { return SrcBuf{p->tabs[u].cur, p->tabs[u].cur_f29 ? 1u : 0u}; },
+                                  [&](uint32_t u) { return scd::flip_table(p->tabs[u], p->use_f29); });
+}
+
+// a staged initialisation computed round 1 under the copy and published it under the next sequence number: true if this call takes it
+static bool take_staged_round1(sc_prover *p, const uint64_t *r_or_null, const RoundCtx &c) {
+    if (!p->r1_cached) return false;
+    p->r1_cached = false;
+    // (a caller that wants the lanes of a sharded round instead: the round is computed again, over the resident tables)
+    if (!(p->round == 0 && !r_or_null && !c.deferred && !c.d_wide && c.publish_to_host)) return false;
+    p->round = 1;
+    p->seq += 1;
+    p->sums_round = p->r1_keeps ? 1 : -1;
+    p->timed = p->timing_pending = p->prod_timed = false;
+    return true;
+}
+
+// the round begins: the handle moves on, the round's constants, the first timing event and -- deferred -- the wait for the challenge
+static int open_round(sc_prover *p, const uint64_t *r_or_null, RoundCtx &c) {
+    c.bind = r_or_null != nullptr || c.deferred;
+    if (r_or_null) p->randomness.push_back(c.r);
+    p->round += 1;
+    c.n_pairs = 1ULL << (p->nv - p->round);
+    c.rdev = to_dev(c.r);
+    sch::Fr r32v = c.r;
+    for (int d = 0; d < 5; ++d) r32v = sch::add(r32v, r32v);
+    c.r32 = to_dev(r32v);
+    c.small = c.n_pairs <= small_pairs_limit() && p->K > 0 && (p->U <= (uint32_t)scd::kMaxSmallTables || p->d_cur_tables != nullptr);
+    c.merged = !c.small && p->merge_rounds && !p->any_generic;
+    std::memset(&c.rc, 0, sizeof(c.rc));
+    if (c.bind && !c.small && p->kernel_variant == 3) make_bind_const(c.r, c.rc);
+    c.grid = scd::grid_for_pairs(c.n_pairs);
+#ifdef SC_EXPERIMENTS
+    c.tiled = !c.small && !p->any_generic && p->kernel_variant == 2;
+    if (c.tiled) c.grid = scd::grid_for_tiles(c.n_pairs);
+#endif
+    c.timed = p->timing && !c.deferred;
+    if (c.timed) HIP_TRY(hipEventRecord(p->ev0, p->stream));
+    if (c.deferred) {
+        p->sig_seq += 1;
+        SlowCallProbe pr("launch k_wait_challenge");
+        HIP_TRY(scd::launch_wait_challenge(p->sig_dev, p->sig_seq, p->h_mail_dev + (p->sig_seq & 1u), p->d_mail + (p->sig_seq & 1u), p->stream));
+        c.r_mail = p->d_mail + (p->sig_seq & 1u);
+        p->deferred_pending = true;
+    }
+    c.bound.assign(p->U, 0);
+    return SC_OK;
+}
+
+// Lagging tables (lag_index.hpp): a merged big round before the catch-up round lets them lag on (its rows bind the class tables), the
+// catch-up round binds them with everything they missed, this round's challenge included, and reads them in place; any other round
+// first makes the tables what they would be without lagging.
+static int lag_stage(sc_prover *p, RoundCtx &c) {
+    if (!p->lag.active) return SC_OK;
+    const bool lag_round = c.bind && !c.deferred && !c.d_wide && !c.small && p->merge_rounds && !p->any_generic && !p->fused_finalize;
+    if (lag_round && p->round < p->lag.j) {
+        c.lag_class = true;
+        p->lag.r.push_back(c.r);
+        return SC_OK;
+    }
+    if (!(lag_round && p->round == p->lag.j)) return materialize_lagging(p);
+    p->lag.r.push_back(c.r);
+    for (uint32_t u = 0; u < p->U; ++u)
+        if (p->tabs[u].lag) c.bound[u] = 2;
+    return materialize_lagging(p, true);
+}
+
+// One launch binds every table, 32 tables a launch, into canonical tables in the reference layout: the latency-bound rounds, and the big
+// rounds of products beyond kMaxFusedM, which read bound tables (SC_HOST_TRACE times both, each launch with the filling of its arguments).  No later stage binds.
+static int bind_all_tables(sc_prover *p, RoundCtx &c) {
+    if (!c.small) scd::plan_hit(scd::kPlanBigBindPass);
+    for (uint32_t u0 = 0; u0 < p->U; u0 += (uint32_t)scd::kMaxSmallTables) {
+        const uint32_t cnt = std::min<uint32_t>(p->U - u0, (uint32_t)scd::kMaxSmallTables);
+        SlowCallProbe pr("launch k_fix_multi");
+        TablePtrs tp;
+        std::memset(&tp, 0, sizeof(tp));
+        for (uint32_t j = 0; j < cnt; ++j) {
+            Table &t = p->tabs[u0 + j];
+            tp.src[j] = t.cur;
+            tp.src_f29[j] = t.cur_f29 ? 1 : 0;
+            tp.dst[j] = t.buf[t.next];
+        }
+        HIP_TRY(scd::launch_fix_multi(tp, (int)cnt, c.rdev, c.r_mail, 2 * c.n_pairs, p->stream));
+        for (uint32_t j = 0; j < cnt; ++j) scd::flip_table(p->tabs[u0 + j], false);
+    }
+    c.bind = false;
+    return SC_OK;
+}
+
+// latency-bound round: one launch binds every table (bind_all_tables), one launch sums every (product, point) combination
+static int small_round(sc_prover *p, RoundCtx &c) {
+    int rc_b = c.bind ? bind_all_tables(p, c) : SC_OK;
+    if (rc_b) return rc_b;
+    SlowCallProbe pr_sum("launch k_sum_combos");
+    scd::plan_hit(c.deferred ? scd::kPlanSmallPipelined : p->U > (uint32_t)scd::kMaxSmallTables ? scd::kPlanSmallPtrs : p->has_meta ? scd::kPlanSmallLaunched : scd::kPlanSmallCombosTable);
+    if (p->U <= (uint32_t)scd::kMaxSmallTables) {
+        TablePtrs tp;
+        std::memset(&tp, 0, sizeof(tp));
+        for (uint32_t u = 0; u < p->U; ++u) tp.src[u] = p->tabs[u].cur;
+        if (p->has_meta) HIP_TRY(scd::launch_sum_combos_meta(tp, p->meta, p->n_combos, c.n_pairs, p->d_partials, c.grid, p->stream));
+        else HIP_TRY(scd::launch_sum_combos(tp, p->d_combos, p->n_combos, p->d_slot_table, p->d_slot_exp, c.n_pairs, p->d_partials, c.grid, p->stream));
+    } else { // more tables than a launch's arguments hold: the pointers go through device memory (never a pipelined round: can_defer_next)
+        for (uint32_t u = 0; u < p->U; ++u) p->h_cur_tables[u] = p->tabs[u].cur;
+        HIP_TRY(hipMemcpyAsync(p->d_cur_tables, p->h_cur_tables, p->U * sizeof(void *), hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(scd::launch_sum_combos_ptrs(p->d_cur_tables, p->d_combos, p->n_combos, p->d_slot_table, p->d_slot_exp, c.n_pairs, p->d_partials, c.grid, p->stream));
+    }
+    c.scaled = 1; // products of up to kMaxFusedM multiplicands are summed in carry-free arithmetic (2^261 radix) there too
+    return SC_OK;
+}
+
+// Round 1 decides which tables lag: those that only products of one multiplicand name, where at least three big rounds exist and
+// this launch is the plain merged one (not a sharded round's, not a section of a staged initialisation).  The class work areas
+// are allocated with the first proof that needs them; a handle that cannot have them proves without lagging.  lag_prod: the products.
+static void decide_lagging(sc_prover *p, const RoundCtx &c, bool split, std::vector<uint8_t> &lag_prod) {
+#ifdef SC_SERIAL_EPILOGUE // (A/B build: the serial epilogue of round 1 leaves no class partials behind)
+    const int64_t lag_pol = 0;
+#else
+    const int64_t lag_pol = scd::policy(scd::kPolLagSingle);
+#endif
+    if (!(!c.bind && p->round == 1 && lag_pol > 0 && split && !c.d_wide && !p->streamed && !p->lag.active)) return;
+    uint32_t last_big = 0;
+    for (uint32_t q = 1; q <= p->nv; ++q)
+        if ((1ULL << (p->nv - q)) > small_pairs_limit()) last_big = q;
+    std::vector<uint8_t> eligible(p->U, 0);
+    for (const Product &pr : p->prods)
+        for (uint32_t u : pr.tables) eligible[u] = 1;
+    for (const Product &pr : p->prods)
+        if (pr.M != 1)
+            for (uint32_t u : pr.tables) eligible[u] = 0;
+    uint32_t n_lag = 0;
+    for (uint32_t k = 0; k < p->K; ++k)
+        if (p->prods[k].M == 1 && eligible[p->prods[k].tables[0]]) lag_prod[k] = 1, ++n_lag;
+    const size_t area = (size_t)scd::lag_area_elems(scd::kLagMaxM, scd::kMaxGrid);
+    if (n_lag > 0 && last_big >= 3 && p->lag_areas < n_lag) {
+        if (p->d_lag_area) (void)hipFree(p->d_lag_area);
+        p->d_lag_area = nullptr;
+        p->lag_areas = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&p->d_lag_area), area * n_lag * 32) == hipSuccess) p->lag_areas = n_lag;
+        else (void)hipGetLastError();
+    }
+    if (!(n_lag > 0 && last_big >= 3 && p->lag_areas >= n_lag)) {
+        std::fill(lag_prod.begin(), lag_prod.end(), 0);
+        return;
+    }
+    p->lag.active = true;
+    p->lag.j = std::min<uint32_t>((uint32_t)lag_pol + 2, last_big);
+    p->lag.m = p->lag.j - 1;
+    p->lag.grid = (uint32_t)c.grid;
+    p->lag.r.clear();
+    for (uint32_t k = 0; k < p->K; ++k)
+        if (lag_prod[k]) p->tabs[p->prods[k].tables[0]].lag = 1;
+}
+
+// One launch for the round, one product per block row (k_round_tree_split / k_round1_tree_split: `grid` blocks per product,
+// merged_row_blocks in lane_sum.hpp).  One scope of stores for the whole round: no product reads what another one writes in this launch.
+static int merged_round(sc_prover *p, RoundCtx &c) {
+    c.grid = std::min(c.grid, scd::kRoundTreeGrid);
+    bool split = !p->fused_finalize;
+    int split_base = 0;
+#ifdef SC_EXPERIMENTS // SC_SPLIT=0: every product in every block (k_round_tree); SC_SPLIT_GRID=n: blocks per product
+    static const bool split_off = std::getenv("SC_SPLIT") && std::atoi(std::getenv("SC_SPLIT")) == 0;
+    static const int split_cap = std::getenv("SC_SPLIT_GRID") ? std::atoi(std::getenv("SC_SPLIT_GRID")) : 0;
+    if (split_off) split = false;
+    if (split_cap > 0) split_base = split_cap;
+#endif
+#ifndef SC_NO_KGRID // (A/B build: the per-row counts whatever the number of rows)
+    constexpr bool by_rows = true;
+#else
+    constexpr bool by_rows = false;
+#endif
+    if (split) c.grid = std::min(scd::grid_for_pairs(c.n_pairs), scd::merged_row_blocks(c.n_pairs, p->K, split_base, by_rows));
+    // the previous round's complete node sums are on the device and this round's will be: node 1 comes from the claim identity
+    c.skip1 = c.bind && split && p->sums_round == (int64_t)p->round - 1 && skip1_enabled() &&
+              scd::finalize_keeps_sums((int)p->K, (int)p->D, c.grid, !p->h_finprods.empty(), fin_mb_enabled());
+    scd::RoundArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    ra.n_prod = (int)p->K;
+    ra.binding = c.bind ? 1 : 0;
+    std::vector<uint8_t> lag_prod(p->K, 0);
+    decide_lagging(p, c, split, lag_prod);
+    if (c.lag_class) {
+        scd::plan_hit(scd::kPlanBigLagClassRound);
+        for (uint32_t k = 0; k < p->K; ++k)
+            if (p->prods[k].M == 1 && p->tabs[p->prods[k].tables[0]].lag) lag_prod[k] = 1;
+    }
+    // (class rows first: block 0 of a row that is dispatched late would be the launch's last block)
+    std::vector<uint32_t> order;
+    for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t k = 0; k < p->K; ++k)
+            if ((c.lag_class && lag_prod[k]) == (pass == 0)) order.push_back(k);
+    uint32_t lag_slot = 0; // the k-th lagging product owns the k-th work area
+    std::vector<uint32_t> area_of(p->K, 0);
+    for (uint32_t k = 0; k < p->K; ++k)
+        if (lag_prod[k]) area_of[k] = lag_slot++;
+    LaunchStores stores;
+    for (uint32_t row = 0; row < p->K; ++row) {
+        const uint32_t k = order[row];
+        const Product &pr = p->prods[k];
+        scd::TreeProd &tp = tree_row(ra, row, pr);
+        if (lag_prod[k]) {
+            tp.lag_m = (uint8_t)p->lag.m;
+            tp.lag_grid = (uint16_t)p->lag.grid;
+            tp.slot[0].dst = reinterpret_cast<uint4 *>(p->d_lag_area + (size_t)area_of[k] * (size_t)scd::lag_area_elems(scd::kLagMaxM, scd::kMaxGrid));
+            if (c.lag_class) { // the row binds its class table; the table itself stays as it is
+                tp.lag_done = (uint8_t)(p->lag.r.size() - 1);
+                tp.slot[0].exp = 1;
+                c.bound[pr.tables[0]] = 1;
+                continue;
+            }
+        }
+        resident_factor_slots(p, tp.slot, pr, c, stores);
+    }
+    // the finalize step runs inside the launch (the blocks that finish last add up the partials and publish the message)
+    p->seq += 1;
+    ra.fin.enabled = p->fused_finalize ? 1 : 0;
+    ra.fin.D = (int)p->D;
+    for (uint32_t k = 0; k < p->K; ++k) ra.fin.w_off[k] = p->h_finprods[k].w_off;
+    ra.fin.Wm = reinterpret_cast<const uint4 *>(p->d_W);
+    ra.fin.partials2 = reinterpret_cast<uint4 *>(p->d_partials2);
+    ra.fin.counters = p->d_fin_counters;
+    ra.fin.out = reinterpret_cast<uint4 *>(p->d_out);
+    ra.fin.out_wide = c.d_wide;
+    ra.fin.h_out = c.publish_to_host ? reinterpret_cast<uint4 *>(p->h_out_dev) : nullptr;
+    ra.fin.h_flag = c.publish_to_host ? p->h_flag_dev : nullptr;
+    ra.fin.seq = p->seq;
+    if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[0], p->stream));
+    if (c.bind) scd::plan_hit(p->use_f29 ? scd::kPlanBigF29Store : scd::kPlanBigCanonicalStore);
+    HIP_TRY(scd::launch_round_tree(ra, c.rc, c.n_pairs, p->d_partials, c.grid, p->stream, split, c.skip1));
+    if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[1], p->stream));
+    c.scaled = 1;
+    if (p->fused_finalize) c.finalized = true;
+    else p->seq -= 1;
+    return SC_OK;
+}
+
+// ---- one launch per product: every product is a scope of stores of its own, and a table an earlier product bound is read as it is ----
+// product tree (k_prod_tree, kernels_wide.hip from five multiplicands): one argument slot per FACTOR
+static int product_tree(sc_prover *p, RoundCtx &c, const Product &pr, FrHost *partials) {
+    ProdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    LaunchStores stores;
+    a.n_slots = resident_factor_slots(p, a.slot, pr, c, stores);
+    scd::plan_hit(pr.M <= 4 ? scd::kPlanBigPerProductTree : scd::kPlanBigWide);
+    if (c.bind) scd::plan_hit(p->use_f29 ? scd::kPlanBigF29Store : scd::kPlanBigCanonicalStore);
+    HIP_TRY(scd::launch_prod_tree((int)pr.M, a, c.rc, c.n_pairs, partials, c.grid, p->stream));
+    c.scaled = 1;
+    return SC_OK;
+}
+// node by node: one slot per distinct table; the first product touching a table this round binds it (fill_table_slots)
+static int product_node_by_node(sc_prover *p, RoundCtx &c, const Product &pr, FrHost *partials) {
+    ProdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n_slots = scd::fill_table_slots(a.slot, pr.tables, pr.exps, c.bind, c.bound.data(), [&](uint32_t u) { return p->tabs[u].cur; },
+                                      [&](uint32_t u) { return scd::flip_table(p->tabs[u], p->tabs[u].cur_f29); });
+#ifdef SC_EXPERIMENTS
+    if (c.tiled || !p->use_fe) { // the cross-check kernels: LDS-tiled (scaled like the carry-free ones), saturated arithmetic
+        if (c.tiled) HIP_TRY(scd::launch_round_tile((int)pr.M, a, c.r32, c.n_pairs, partials, c.grid, p->stream));
+        else HIP_TRY(scd::launch_prod_round((int)pr.M, a, c.rdev, c.n_pairs, partials, c.grid, p->stream));
+        if (c.tiled) c.scaled = 1;
+        return SC_OK;
+    }
+#endif
+    scd::plan_hit(scd::kPlanBigNodeByNode);
+    HIP_TRY(scd::launch_prod_round_fe((int)pr.M, a, c.r32, c.n_pairs, partials, c.grid, p->stream));
+    c.scaled = 1;
+    return SC_OK;
+}
+// nine to twelve multiplicands: a tree of the trees (kernels_wide16.hip) over the tables the bind pass left; one slot per FACTOR, every
+// one in mode 0, and the sums come back in k_sum_generic's form (the kernel takes its 2^(-5(M-1)) off again)
+static int product_wide16(sc_prover *p, RoundCtx &c, const Product &pr, const std::vector<uint32_t> &factors, FrHost *partials) {
+    scd::WideArgs16 a;
+    std::memset(&a, 0, sizeof(a));
+    a.n_slots = (int)factors.size();
+    for (size_t f = 0; f < factors.size(); ++f) {
+        const Table &t = p->tabs[factors[f]];
+        a.slot[f].mode = 0;
+        a.slot[f].exp = 1;
+        a.slot[f].src = t.cur;
+        a.slot[f].src_f29 = t.cur_f29 ? 1 : 0;
+    }
+    sch::Fr comp = sch::kOne; // 2^(5(M-1)) in Montgomery form
+    for (uint32_t dbl = 0; dbl < 5 * (pr.M - 1); ++dbl) comp = sch::add(comp, comp);
+    scd::plan_hit(scd::kPlanBigWide16);
+    HIP_TRY(scd::launch_prod_tree_wide16((int)pr.M, a, to_dev(comp), c.n_pairs, partials, c.grid, p->stream));
+    return SC_OK;
+}
+// any number of multiplicands: the table pointers go through device memory, uploaded with the round's first such product
+static int product_generic(sc_prover *p, RoundCtx &c, const Product &pr, FrHost *partials, bool &ptrs_uploaded) {
+    if (!ptrs_uploaded) {
+        for (uint32_t u = 0; u < p->U; ++u) p->h_cur_tables[u] = p->tabs[u].cur;
+        HIP_TRY(hipMemcpyAsync(p->d_cur_tables, p->h_cur_tables, p->U * sizeof(void *), hipMemcpyHostToDevice, p->stream));
+        ptrs_uploaded = true;
+    }
+    scd::plan_hit(scd::kPlanBigGeneric);
+    HIP_TRY(scd::launch_sum_generic(p->d_cur_tables, p->d_slot_table + pr.slot_off, p->d_slot_exp + pr.slot_off, (int)pr.tables.size(), (int)pr.M, c.n_pairs, partials, c.grid, p->stream));
+    return SC_OK;
+}
+static int per_product_round(sc_prover *p, RoundCtx &c) {
+    bool ptrs_uploaded = false;
+    for (uint32_t k = 0; k < p->K; ++k) {
+        const Product &pr = p->prods[k];
+        FrHost *partials = p->d_partials + pr.partial_off;
+        if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[2 * k], p->stream));
+        int rc_k;
+        if (pr.fused && p->kernel_variant == 3 && (pr.M <= 4 || p->wide_tree)) rc_k = product_tree(p, c, pr, partials);
+        else if (pr.fused) rc_k = product_node_by_node(p, c, pr, partials);
+        else if (pr.M <= (uint32_t)scd::kMaxWideM && p->wide_tree && p->kernel_variant == 3) rc_k = product_wide16(p, c, pr, p->prod_indices[k], partials);
+        else rc_k = product_generic(p, c, pr, partials, ptrs_uploaded);
+        if (rc_k) return rc_k;
+        if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[2 * k + 1], p->stream));
+    }
+    return SC_OK;
+}
+
+// tables that no product refers to still follow the state machine: a stand-alone bind each (2 * n_pairs outputs)
+static int bind_unnamed_tables(sc_prover *p, RoundCtx &c) {
+    for (uint32_t u = 0; u < p->U; ++u) {
+        if (c.bound[u]) continue;
+        Table &t = p->tabs[u];
+        const uint4 *src = t.cur;
+        HIP_TRY(scd::launch_fix(src, scd::flip_table(t, t.cur_f29), c.rdev, 2 * c.n_pairs, p->stream));
+    }
+    return SC_OK;
+}
+
+// The claim weights of a round that leaves node 1 out, and k_finalize.  Its multi-block form leaves the round's node sums behind: kept per
+// round parity for the next round's claims (tree rounds only: their sums all carry the same scaling).
+static int finalize_round(sc_prover *p, RoundCtx &c) {
+    p->seq += 1;
+    const bool keeps = scd::finalize_keeps_sums((int)p->K, (int)p->D, c.grid, !p->h_finprods.empty(), fin_mb_enabled());
+    scd::ClaimArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    if (c.skip1) {
+        ca.skip1 = 1;
+        ca.prev = reinterpret_cast<const uint4 *>(p->d_sums[(p->round - 1) & 1]);
+        bool done[5] = {false, false, false, false, false};
+        for (uint32_t k = 0; k < p->K; ++k) {
+            const uint32_t M = p->prods[k].M;
+            if (done[M]) continue;
+            done[M] = true;
+            sch::Fr lam[5];
+            claim_weights(M, c.r, lam);
+            for (uint32_t s2 = 0; s2 <= M; ++s2) ca.lam[scd::claim_off((int)M) + (int)s2] = to_dev(lam[s2]);
+        }
+    }
+    SlowCallProbe pr_fin("launch k_finalize");
+    const bool tagged = p->wide_tagged && c.d_wide; // (tagged lanes: the communicator's generation, the same on every rank)
+    HIP_TRY(scd::launch_finalize(p->d_finprods, p->h_finprods.empty() ? nullptr : p->h_finprods.data(), p->d_W, (int)p->K, (int)p->D, c.grid, p->d_partials,
+                                 keeps ? p->d_sums[p->round & 1] : p->d_scratch, p->d_out, c.d_wide, c.publish_to_host ? p->h_out_dev : nullptr,
+                                 c.publish_to_host ? p->h_flag_dev : nullptr, tagged ? p->wide_gen : p->seq, c.scaled | (tagged ? 2 : 0),
+                                 fin_mb_enabled() ? p->d_fin_mb_counter : nullptr, p->stream, c.skip1 ? &ca : nullptr));
+    p->sums_round = keeps && c.merged ? (int64_t)p->round : -1;
+    return SC_OK;
+}
+
+// the closing timing event and what the next collect_timing will find
+static int close_round(sc_prover *p, const RoundCtx &c) {
+    if (c.timed) HIP_TRY(hipEventRecord(p->ev1, p->stream));
+    if (c.deferred) return SC_OK; // (a pipelined round leaves the previous round's pending event pairs to the next collect_timing)
+    p->timed = c.timed;
+    p->timing_pending = c.timed;
+    p->prod_timed = c.timed && !c.small;
+    p->prod_merged = c.merged;
+    p->timed_round = p->round;
+    return SC_OK;
+}
+
+// Launch one round's kernels on p->stream.  On return the round polynomial is in p->d_out (and in d_wide if non-null); nothing has been
+// synchronised.  deferred = true (library-internal): the challenge does not exist yet.  The round is enqueued behind a wait on p->sig and its
+// bind kernel reads the challenge from the mailbox; provide_challenge() supplies it later.  Late (small) rounds only.
 int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool publish_to_host, bool deferred) {
     if (p->res.active) { // (sc_prove_round_partial after interactive rounds)
         int rc_q = resident_quiesce(p);
@@ -470,480 +823,26 @@ int launch_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *d_wide, bool
         if (deferred) return sc_internal_fail(SC_ERR_BAD_ARG, "streamed tables: rounds 1 and 2 are not pipelined");
         return launch_round_streamed(p, r_or_null, d_wide, publish_to_host);
     }
-    // validation, same precedence as the reference's panics (prover.rs:78-98)
-    if (p->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
-    if (p->deferred_pending) return sc_internal_fail(SC_ERR_BAD_ARG, "a pipelined round is waiting for its challenge");
-    if (r_or_null && p->round == 0) return sc_internal_fail(SC_ERR_FIRST_ROUND_HAS_MSG, "first round should be prover first.");
-    if (!r_or_null && p->round > 0 && !deferred) return sc_internal_fail(SC_ERR_MISSING_MSG, "verifier message is empty");
-    if (p->round + 1 > p->nv) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
-    sch::Fr r = sch::zero();
-    if (r_or_null) {
-        std::memcpy(&r, r_or_null, 32);
-        if (sch::geq_p(r)) return sc_internal_fail(SC_ERR_BAD_ARG, "challenge is not a canonical field element");
-    }
-    if (deferred) { // (every check comes before the first change to the handle)
-        const uint64_t np = 1ULL << (p->nv - (p->round + 1));
-        if (!(np <= small_pairs_limit() && p->U <= (uint32_t)scd::kMaxSmallTables && p->K > 0)) return sc_internal_fail(SC_ERR_BAD_ARG, "only late rounds are pipelined");
-    }
+    RoundCtx c;
+    c.d_wide = d_wide;
+    c.publish_to_host = publish_to_host;
+    c.deferred = deferred;
+    int rc = check_round_args(p, r_or_null, deferred, c.r);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    if (!deferred) { // (a pipelined round records no events: collecting would wait for the round before it)
-        int rc_t = collect_timing(p);
-        if (rc_t) return rc_t;
-    }
-    if (p->r1_cached) { // a staged initialisation computed this round under the copy and published it under the next sequence number
-        p->r1_cached = false;
-        if (p->round == 0 && !r_or_null && !deferred && !d_wide && publish_to_host) {
-            p->round = 1;
-            p->seq += 1;
-            p->sums_round = p->r1_keeps ? 1 : -1;
-            p->timed = false;
-            p->timing_pending = false;
-            p->prod_timed = false;
-            return SC_OK;
-        }
-        // (a caller that wants the lanes of a sharded round instead: the round is computed again, over the resident tables)
-    }
-    bool bind = r_or_null != nullptr || deferred;
-    if (r_or_null) p->randomness.push_back(r);
-    p->round += 1;
-    const uint64_t n_pairs = 1ULL << (p->nv - p->round);
-    const FrHost rdev = to_dev(r);
-    sch::Fr r32v = r; // r * 2^5 for the 2^261-radix kernels
-    for (int d = 0; d < 5; ++d) r32v = sch::add(r32v, r32v);
-    const FrHost r32 = to_dev(r32v);
-    int scaled = 0;
-    const uint64_t small_pairs = small_pairs_limit();
-    const bool small_round = n_pairs <= small_pairs && p->K > 0 && (p->U <= (uint32_t)scd::kMaxSmallTables || p->d_cur_tables != nullptr);
-#ifdef SC_EXPERIMENTS
-    const bool tiled = !small_round && !p->any_generic && p->kernel_variant == 2;
-#else
-    const bool tiled = false;
-    (void)tiled;
-#endif
-    scd::BindConst rc; // (only the big rounds of the tree kernels pay for it)
-    std::memset(&rc, 0, sizeof(rc)); // tree kernels: rows (r * 2^(29 i + 58)) mod p as plain 29-bit limbs (fe_device.hpp, fe_mul_bind)
-    if (bind && !small_round && p->kernel_variant == 3) make_bind_const(r, rc);
-    int grid = scd::grid_for_pairs(n_pairs);
-#ifdef SC_EXPERIMENTS
-    if (tiled) grid = scd::grid_for_tiles(n_pairs);
-#endif
-    const bool timed = p->timing && !deferred;
-    if (timed) HIP_TRY(hipEventRecord(p->ev0, p->stream));
-    const FrHost *r_mail = nullptr;
-    if (deferred) {
-        p->sig_seq += 1;
-        {
-            SlowCallProbe pr("launch k_wait_challenge");
-            HIP_TRY(scd::launch_wait_challenge(p->sig_dev, p->sig_seq, p->h_mail_dev + (p->sig_seq & 1u), p->d_mail + (p->sig_seq & 1u), p->stream));
-        }
-        r_mail = p->d_mail + (p->sig_seq & 1u);
-        p->deferred_pending = true;
-    }
-
-    // Lagging tables (lag_index.hpp): a merged big round before the catch-up round lets them lag on (its rows bind the class tables), the
-    // catch-up round binds them with everything they missed, this round's challenge included, and reads them in place; any other round
-    // first makes the tables what they would be without lagging.
-    bool lag_class = false;
-    std::vector<uint8_t> bound(p->U, 0); // 1: bound by this round; 2: bound up to and including this round's challenge by k_fix_deep
-    if (p->lag.active) {
-        const bool lag_round = bind && !deferred && !d_wide && !small_round && p->merge_rounds && !p->any_generic && !p->fused_finalize;
-        if (lag_round && p->round < p->lag.j) {
-            lag_class = true;
-            p->lag.r.push_back(r);
-        } else if (lag_round && p->round == p->lag.j) {
-            p->lag.r.push_back(r);
-            for (uint32_t u = 0; u < p->U; ++u)
-                if (p->tabs[u].lag) bound[u] = 2;
-            int rc_l = materialize_lagging(p, true);
-            if (rc_l) return rc_l;
-        } else {
-            int rc_l = materialize_lagging(p);
-            if (rc_l) return rc_l;
-        }
-    }
-
-    auto bind_table = [&](uint32_t u) -> hipError_t { // stand-alone bind of table u (2*n_pairs outputs)
-        Table &t = p->tabs[u];
-        uint4 *dst = t.buf[t.next];
-        hipError_t e = scd::launch_fix(t.cur, dst, rdev, 2 * n_pairs, p->stream);
-        t.cur = dst;
-        t.next ^= 1;
-        return e;
-    };
-
-    const bool small = small_round;
-    if (small) {
-        // latency-bound round: one launch binds every table (32 tables a launch), one launch sums every (product, point) combination
-        TablePtrs tp;
-        if (bind) {
-            for (uint32_t u0 = 0; u0 < p->U; u0 += (uint32_t)scd::kMaxSmallTables) {
-                const uint32_t cnt = std::min<uint32_t>(p->U - u0, (uint32_t)scd::kMaxSmallTables);
-                std::memset(&tp, 0, sizeof(tp));
-                for (uint32_t j = 0; j < cnt; ++j) {
-                    Table &t = p->tabs[u0 + j];
-                    tp.src[j] = t.cur;
-                    tp.src_f29[j] = t.cur_f29 ? 1 : 0;
-                    tp.dst[j] = t.buf[t.next];
-                }
-                {
-                    SlowCallProbe pr("launch k_fix_multi");
-                    HIP_TRY(scd::launch_fix_multi(tp, (int)cnt, rdev, r_mail, 2 * n_pairs, p->stream));
-                }
-                for (uint32_t j = 0; j < cnt; ++j) {
-                    Table &t = p->tabs[u0 + j];
-                    t.cur = t.buf[t.next];
-                    t.cur_f29 = false; // the latency-bound path keeps tables canonical in the reference layout
-                    t.next ^= 1;
-                }
-            }
-        }
-        SlowCallProbe pr_sum("launch k_sum_combos");
-        scd::plan_hit(deferred ? scd::kPlanSmallPipelined : p->U > (uint32_t)scd::kMaxSmallTables ? scd::kPlanSmallPtrs : p->has_meta ? scd::kPlanSmallLaunched : scd::kPlanSmallCombosTable);
-        if (p->U <= (uint32_t)scd::kMaxSmallTables) {
-            std::memset(&tp, 0, sizeof(tp));
-            for (uint32_t u = 0; u < p->U; ++u) tp.src[u] = p->tabs[u].cur;
-            if (p->has_meta) HIP_TRY(scd::launch_sum_combos_meta(tp, p->meta, p->n_combos, n_pairs, p->d_partials, grid, p->stream));
-            else HIP_TRY(scd::launch_sum_combos(tp, p->d_combos, p->n_combos, p->d_slot_table, p->d_slot_exp, n_pairs, p->d_partials, grid, p->stream));
-        } else { // more tables than a launch's arguments hold: the pointers go through device memory (never a pipelined round: can_defer_next)
-            for (uint32_t u = 0; u < p->U; ++u) p->h_cur_tables[u] = p->tabs[u].cur;
-            HIP_TRY(hipMemcpyAsync(p->d_cur_tables, p->h_cur_tables, p->U * sizeof(void *), hipMemcpyHostToDevice, p->stream));
-            HIP_TRY(scd::launch_sum_combos_ptrs(p->d_cur_tables, p->d_combos, p->n_combos, p->d_slot_table, p->d_slot_exp, n_pairs, p->d_partials, grid, p->stream));
-        }
-        scaled = 1; // products of up to kMaxFusedM multiplicands are summed in carry-free arithmetic (2^261 radix) there too
-        bind = false;
-    }
-    if (bind && p->any_generic) { // products beyond kMaxFusedM read bound tables: bind everything up front, 32 tables a launch
-        scd::plan_hit(scd::kPlanBigBindPass);
-        for (uint32_t u0 = 0; u0 < p->U; u0 += (uint32_t)scd::kMaxSmallTables) {
-            const uint32_t cnt = std::min<uint32_t>(p->U - u0, (uint32_t)scd::kMaxSmallTables);
-            TablePtrs tp;
-            std::memset(&tp, 0, sizeof(tp));
-            for (uint32_t j = 0; j < cnt; ++j) {
-                Table &t = p->tabs[u0 + j];
-                tp.src[j] = t.cur;
-                tp.src_f29[j] = t.cur_f29 ? 1 : 0;
-                tp.dst[j] = t.buf[t.next];
-            }
-            HIP_TRY(scd::launch_fix_multi(tp, (int)cnt, rdev, nullptr, 2 * n_pairs, p->stream));
-            for (uint32_t j = 0; j < cnt; ++j) {
-                Table &t = p->tabs[u0 + j];
-                t.cur = t.buf[t.next];
-                t.cur_f29 = false;
-                t.next ^= 1;
-            }
-        }
-        bind = false;
-    }
-    bool ptrs_uploaded = false;
-    bool finalized = false; // the merged big-round launch also produced the message
-    bool skip1 = false;     // the round kernel leaves node 1 out (ClaimArgs)
-    const bool merged = !small && p->merge_rounds && !p->any_generic;
-    if (merged) {
-        grid = std::min(grid, scd::kRoundTreeGrid);
-        // One product per block row (k_round_tree_split / k_round1_tree_split): `grid` blocks per product, merged_row_blocks (lane_sum.hpp)
-        bool split = !p->fused_finalize;
-        int split_base = 0;
-#ifdef SC_EXPERIMENTS // SC_SPLIT=0: every product in every block (k_round_tree); SC_SPLIT_GRID=n: blocks per product
-        static const bool split_off = std::getenv("SC_SPLIT") && std::atoi(std::getenv("SC_SPLIT")) == 0;
-        static const int split_cap = std::getenv("SC_SPLIT_GRID") ? std::atoi(std::getenv("SC_SPLIT_GRID")) : 0;
-        if (split_off) split = false;
-        if (split_cap > 0) split_base = split_cap;
-#endif
-#ifndef SC_NO_KGRID // (A/B build: the per-row counts whatever the number of rows)
-        constexpr bool by_rows = true;
-#else
-        constexpr bool by_rows = false;
-#endif
-        if (split) grid = std::min(scd::grid_for_pairs(n_pairs), scd::merged_row_blocks(n_pairs, p->K, split_base, by_rows));
-        // the previous round's complete node sums are on the device and this round's will be: node 1 comes from the claim identity
-        skip1 = bind && split && p->sums_round == (int64_t)p->round - 1 && skip1_enabled() &&
-                scd::finalize_keeps_sums((int)p->K, (int)p->D, grid, !p->h_finprods.empty(), fin_mb_enabled());
-        // One launch for the round.  The first factor touching a table binds and stores it (mode 1); every later factor on
-        // that table -- in the same or in another product -- re-binds from the old buffer without storing (mode 3), so no
-        // product reads what another one writes in this launch.
-        scd::RoundArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
-        ra.n_prod = (int)p->K;
-        std::vector<const uint4 *> old_src(p->U);
-        std::vector<uint8_t> old_f29(p->U);
-        for (uint32_t u = 0; u < p->U; ++u) {
-            old_src[u] = p->tabs[u].cur;
-            old_f29[u] = p->tabs[u].cur_f29 ? 1 : 0;
-        }
-        ra.binding = bind ? 1 : 0;
-        // Round 1 decides which tables lag: those that only products of one multiplicand name, where at least three big rounds exist and
-        // this launch is the plain merged one (not a sharded round's, not a section of a staged initialisation).  The class work areas
-        // are allocated with the first proof that needs them; a handle that cannot have them proves without lagging.
-        std::vector<uint8_t> lag_prod(p->K, 0);
-#ifdef SC_SERIAL_EPILOGUE // (A/B build: the serial epilogue of round 1 leaves no class partials behind)
-        const int64_t lag_pol = 0;
-#else
-        const int64_t lag_pol = scd::policy(scd::kPolLagSingle);
-#endif
-        if (!bind && p->round == 1 && lag_pol > 0 && split && !d_wide && !p->streamed && !p->lag.active) {
-            uint32_t last_big = 0;
-            for (uint32_t q = 1; q <= p->nv; ++q)
-                if ((1ULL << (p->nv - q)) > small_pairs) last_big = q;
-            std::vector<uint8_t> eligible(p->U, 0);
-            for (const Product &pr : p->prods)
-                for (uint32_t u : pr.tables) eligible[u] = 1;
-            for (const Product &pr : p->prods)
-                if (pr.M != 1)
-                    for (uint32_t u : pr.tables) eligible[u] = 0;
-            uint32_t n_lag = 0;
-            for (uint32_t k = 0; k < p->K; ++k)
-                if (p->prods[k].M == 1 && eligible[p->prods[k].tables[0]]) lag_prod[k] = 1, ++n_lag;
-            const size_t area = (size_t)scd::lag_area_elems(scd::kLagMaxM, scd::kMaxGrid);
-            if (n_lag > 0 && last_big >= 3 && p->lag_areas < n_lag) {
-                if (p->d_lag_area) (void)hipFree(p->d_lag_area);
-                p->d_lag_area = nullptr;
-                p->lag_areas = 0;
-                if (hipMalloc(reinterpret_cast<void **>(&p->d_lag_area), area * n_lag * 32) == hipSuccess) p->lag_areas = n_lag;
-                else (void)hipGetLastError();
-            }
-            if (n_lag > 0 && last_big >= 3 && p->lag_areas >= n_lag) {
-                p->lag.active = true;
-                p->lag.j = std::min<uint32_t>((uint32_t)lag_pol + 2, last_big);
-                p->lag.m = p->lag.j - 1;
-                p->lag.grid = (uint32_t)grid;
-                p->lag.r.clear();
-                for (uint32_t k = 0; k < p->K; ++k)
-                    if (lag_prod[k]) p->tabs[p->prods[k].tables[0]].lag = 1;
-            } else {
-                std::fill(lag_prod.begin(), lag_prod.end(), 0);
-            }
-        } else if (lag_class) {
-            scd::plan_hit(scd::kPlanBigLagClassRound);
-            for (uint32_t k = 0; k < p->K; ++k)
-                if (p->prods[k].M == 1 && p->tabs[p->prods[k].tables[0]].lag) lag_prod[k] = 1;
-        }
-        // (class rows first: block 0 of a row that is dispatched late would be the launch's last block)
-        std::vector<uint32_t> order;
-        for (int pass = 0; pass < 2; ++pass)
-            for (uint32_t k = 0; k < p->K; ++k)
-                if ((lag_class && lag_prod[k]) == (pass == 0)) order.push_back(k);
-        uint32_t lag_slot = 0; // the k-th lagging product owns the k-th work area
-        std::vector<uint32_t> area_of(p->K, 0);
-        for (uint32_t k = 0; k < p->K; ++k)
-            if (lag_prod[k]) area_of[k] = lag_slot++;
-        for (uint32_t row = 0; row < p->K; ++row) {
-            const uint32_t k = order[row];
-            const Product &pr = p->prods[k];
-            scd::TreeProd &tp = ra.prod[row];
-            tp.M = pr.M;
-            tp.partial_off = pr.partial_off;
-            if (lag_prod[k]) {
-                tp.lag_m = (uint8_t)p->lag.m;
-                tp.lag_grid = (uint16_t)p->lag.grid;
-                tp.slot[0].dst = reinterpret_cast<uint4 *>(p->d_lag_area + (size_t)area_of[k] * (size_t)scd::lag_area_elems(scd::kLagMaxM, scd::kMaxGrid));
-                if (lag_class) { // the row binds its class table; the table itself stays as it is
-                    tp.lag_done = (uint8_t)(p->lag.r.size() - 1);
-                    tp.slot[0].exp = 1;
-                    bound[pr.tables[0]] = 1;
-                    continue;
-                }
-            }
-            int f = 0;
-            for (size_t s = 0; s < pr.tables.size(); ++s) {
-                const uint32_t u = pr.tables[s];
-                Table &t = p->tabs[u];
-                for (uint32_t rep = 0; rep < pr.exps[s]; ++rep, ++f) {
-                    scd::Slot &sl = tp.slot[f];
-                    sl.exp = 1;
-                    sl.src = old_src[u];
-                    sl.src_f29 = old_f29[u];
-                    if (!bind || bound[u] == 2) {
-                        sl.mode = 0;
-                    } else if (!bound[u]) {
-                        sl.mode = 1;
-                        sl.dst = t.buf[t.next];
-                        sl.dst_f29 = p->use_f29 ? 1 : 0;
-                        t.cur = t.buf[t.next];
-                        t.cur_f29 = p->use_f29;
-                        t.next ^= 1;
-                        bound[u] = 1;
-                    } else {
-                        sl.mode = 3;
-                        sl.dst_f29 = p->use_f29 ? 1 : 0; // (nothing is stored: keeps the value in the stored table's form)
-                    }
-                }
-            }
-        }
-        // the finalize step runs inside the launch (the blocks that finish last add up the partials and publish the message)
-        p->seq += 1;
-        ra.fin.enabled = p->fused_finalize ? 1 : 0;
-        ra.fin.D = (int)p->D;
-        for (uint32_t k = 0; k < p->K; ++k) ra.fin.w_off[k] = p->h_finprods[k].w_off;
-        ra.fin.Wm = reinterpret_cast<const uint4 *>(p->d_W);
-        ra.fin.partials2 = reinterpret_cast<uint4 *>(p->d_partials2);
-        ra.fin.counters = p->d_fin_counters;
-        ra.fin.out = reinterpret_cast<uint4 *>(p->d_out);
-        ra.fin.out_wide = d_wide;
-        ra.fin.h_out = publish_to_host ? reinterpret_cast<uint4 *>(p->h_out_dev) : nullptr;
-        ra.fin.h_flag = publish_to_host ? p->h_flag_dev : nullptr;
-        ra.fin.seq = p->seq;
-        if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[0], p->stream));
-        if (bind) scd::plan_hit(p->use_f29 ? scd::kPlanBigF29Store : scd::kPlanBigCanonicalStore);
-        HIP_TRY(scd::launch_round_tree(ra, rc, n_pairs, p->d_partials, grid, p->stream, split, skip1));
-        if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[1], p->stream));
-        scaled = 1;
-        if (p->fused_finalize) finalized = true;
-        else p->seq -= 1;
-    }
-    for (uint32_t k = 0; k < p->K && !small && !merged; ++k) {
-        const Product &pr = p->prods[k];
-        FrHost *partials = p->d_partials + pr.partial_off;
-        if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[2 * k], p->stream));
-        if (pr.fused && p->kernel_variant == 3 && (pr.M <= 4 || p->wide_tree)) {
-            // product tree: one argument slot per FACTOR.  The first factor touching a table this round binds and stores it;
-            // a repeat inside the same product re-binds from the old table without storing (mode 3).
-            ProdArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.n_slots = (int)pr.M;
-            int f = 0;
-            for (size_t s = 0; s < pr.tables.size(); ++s) {
-                Table &t = p->tabs[pr.tables[s]];
-                const uint4 *old_src = t.cur;
-                const uint32_t old_f29 = t.cur_f29 ? 1 : 0;
-                bool stored_here = false;
-                for (uint32_t rep = 0; rep < pr.exps[s]; ++rep, ++f) {
-                    a.slot[f].exp = 1;
-                    if (bind && !bound[pr.tables[s]]) {
-                        a.slot[f].mode = 1;
-                        a.slot[f].src = old_src;
-                        a.slot[f].src_f29 = old_f29;
-                        a.slot[f].dst = t.buf[t.next];
-                        a.slot[f].dst_f29 = p->use_f29 ? 1 : 0;
-                        t.cur = t.buf[t.next];
-                        t.cur_f29 = p->use_f29;
-                        t.next ^= 1;
-                        bound[pr.tables[s]] = 1;
-                        stored_here = true;
-                    } else if (stored_here) {
-                        a.slot[f].mode = 3;
-                        a.slot[f].src = old_src;
-                        a.slot[f].src_f29 = old_f29;
-                        a.slot[f].dst = nullptr;
-                        a.slot[f].dst_f29 = p->use_f29 ? 1 : 0; // (nothing is stored: keeps the value in the stored table's form)
-                    } else {
-                        a.slot[f].mode = 0;
-                        a.slot[f].src = t.cur;
-                        a.slot[f].src_f29 = t.cur_f29 ? 1 : 0;
-                        a.slot[f].dst = nullptr;
-                    }
-                }
-            }
-            scd::plan_hit(pr.M <= 4 ? scd::kPlanBigPerProductTree : scd::kPlanBigWide);
-            if (bind) scd::plan_hit(p->use_f29 ? scd::kPlanBigF29Store : scd::kPlanBigCanonicalStore);
-            HIP_TRY(scd::launch_prod_tree((int)pr.M, a, rc, n_pairs, partials, grid, p->stream));
-            scaled = 1;
-        } else if (pr.fused) {
-            ProdArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.n_slots = (int)pr.tables.size();
-            for (size_t s = 0; s < pr.tables.size(); ++s) {
-                Table &t = p->tabs[pr.tables[s]];
-                a.slot[s].exp = pr.exps[s];
-                if (bind && !bound[pr.tables[s]]) { // first product touching this table this round binds it
-                    a.slot[s].mode = 1;
-                    a.slot[s].src = t.cur;
-                    a.slot[s].dst = t.buf[t.next];
-                    t.cur = t.buf[t.next];
-                    t.next ^= 1;
-                    bound[pr.tables[s]] = 1;
-                } else {
-                    a.slot[s].mode = 0;
-                    a.slot[s].src = t.cur;
-                    a.slot[s].dst = nullptr;
-                }
-            }
-#ifdef SC_EXPERIMENTS
-            if (tiled) {
-                HIP_TRY(scd::launch_round_tile((int)pr.M, a, r32, n_pairs, partials, grid, p->stream));
-                scaled = 1;
-            } else if (!p->use_fe) {
-                HIP_TRY(scd::launch_prod_round((int)pr.M, a, rdev, n_pairs, partials, grid, p->stream));
-            } else
-#endif
-            {
-                scd::plan_hit(scd::kPlanBigNodeByNode);
-                HIP_TRY(scd::launch_prod_round_fe((int)pr.M, a, r32, n_pairs, partials, grid, p->stream));
-                scaled = 1;
-            }
-        } else if (pr.M <= (uint32_t)scd::kMaxWideM && p->wide_tree && p->kernel_variant == 3) {
-            // nine to twelve multiplicands: a tree of the trees (kernels_wide16.hip) over the tables the bind pass above left; one slot per
-            // FACTOR, and the sums come back in k_sum_generic's form (the kernel takes its 2^(-5(M-1)) off again)
-            scd::WideArgs16 a;
-            std::memset(&a, 0, sizeof(a));
-            const std::vector<uint32_t> &factors = p->prod_indices[k];
-            a.n_slots = (int)factors.size();
-            for (size_t f = 0; f < factors.size(); ++f) {
-                const Table &t = p->tabs[factors[f]];
-                a.slot[f].mode = 0;
-                a.slot[f].exp = 1;
-                a.slot[f].src = t.cur;
-                a.slot[f].src_f29 = t.cur_f29 ? 1 : 0;
-            }
-            sch::Fr comp = sch::kOne; // 2^(5(M-1)) in Montgomery form
-            for (uint32_t dbl = 0; dbl < 5 * (pr.M - 1); ++dbl) comp = sch::add(comp, comp);
-            scd::plan_hit(scd::kPlanBigWide16);
-            HIP_TRY(scd::launch_prod_tree_wide16((int)pr.M, a, to_dev(comp), n_pairs, partials, grid, p->stream));
-        } else {
-            if (!ptrs_uploaded) {
-                for (uint32_t u = 0; u < p->U; ++u) p->h_cur_tables[u] = p->tabs[u].cur;
-                HIP_TRY(hipMemcpyAsync(p->d_cur_tables, p->h_cur_tables, p->U * sizeof(void *), hipMemcpyHostToDevice, p->stream));
-                ptrs_uploaded = true;
-            }
-            scd::plan_hit(scd::kPlanBigGeneric);
-            HIP_TRY(scd::launch_sum_generic(p->d_cur_tables, p->d_slot_table + pr.slot_off, p->d_slot_exp + pr.slot_off,
-                                            (int)pr.tables.size(), (int)pr.M, n_pairs, partials, grid, p->stream));
-        }
-        if (p->timing) HIP_TRY(hipEventRecord(p->prod_ev[2 * k + 1], p->stream));
-    }
-    if (bind) { // tables that no product refers to still follow the state machine
-        for (uint32_t u = 0; u < p->U; ++u)
-            if (!bound[u]) HIP_TRY(bind_table(u));
-    }
-    if (!finalized) {
-    p->seq += 1;
-    // the multi-block form leaves the round's node sums behind: kept per round parity for the next round's claims (tree rounds only:
-    // their sums all carry the same scaling)
-    const bool keeps = scd::finalize_keeps_sums((int)p->K, (int)p->D, grid, !p->h_finprods.empty(), fin_mb_enabled());
-    scd::ClaimArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    if (skip1) {
-        ca.skip1 = 1;
-        ca.prev = reinterpret_cast<const uint4 *>(p->d_sums[(p->round - 1) & 1]);
-        bool done[5] = {false, false, false, false, false};
-        for (uint32_t k = 0; k < p->K; ++k) {
-            const uint32_t M = p->prods[k].M;
-            if (done[M]) continue;
-            done[M] = true;
-            sch::Fr lam[5];
-            claim_weights(M, r, lam);
-            for (uint32_t s2 = 0; s2 <= M; ++s2) ca.lam[scd::claim_off((int)M) + (int)s2] = to_dev(lam[s2]);
-        }
-    }
-    SlowCallProbe pr_fin("launch k_finalize");
-    HIP_TRY(scd::launch_finalize(p->d_finprods, p->h_finprods.empty() ? nullptr : p->h_finprods.data(), p->d_W, (int)p->K, (int)p->D, grid, p->d_partials,
-                                 keeps ? p->d_sums[p->round & 1] : p->d_scratch, p->d_out, d_wide,
-                                 publish_to_host ? p->h_out_dev : nullptr, publish_to_host ? p->h_flag_dev : nullptr,
-                                 (p->wide_tagged && d_wide) ? p->wide_gen : p->seq, // (tagged lanes: the communicator's generation, the same on every rank)
-                                 scaled | ((p->wide_tagged && d_wide) ? 2 : 0), fin_mb_enabled() ? p->d_fin_mb_counter : nullptr, p->stream, skip1 ? &ca : nullptr));
-    p->sums_round = keeps && merged ? (int64_t)p->round : -1;
-    }
-    if (timed) HIP_TRY(hipEventRecord(p->ev1, p->stream));
-    if (!deferred) { // (a pipelined round leaves the previous round's pending event pairs to the next collect_timing)
-        p->timed = timed;
-        p->timing_pending = timed;
-        p->prod_timed = timed && !small;
-        p->prod_merged = merged;
-        p->timed_round = p->round;
-    }
-    return SC_OK;
+    if (!deferred) rc = collect_timing(p); // (a pipelined round records no events: collecting would wait for the round before it)
+    if (rc) return rc;
+    if (take_staged_round1(p, r_or_null, c)) return SC_OK;
+    rc = open_round(p, r_or_null, c);
+    if (!rc) rc = lag_stage(p, c);
+    if (!rc && c.small) rc = small_round(p, c);
+    if (!rc && c.bind && p->any_generic) rc = bind_all_tables(p, c); // products beyond kMaxFusedM read bound tables
+    if (!rc && c.merged) rc = merged_round(p, c);
+    if (!rc && !c.small && !c.merged) rc = per_product_round(p, c);
+    if (!rc && c.bind) rc = bind_unnamed_tables(p, c);
+    if (!rc && !c.finalized) rc = finalize_round(p, c);
+    return rc ? rc : close_round(p, c);
 }
-
-int await_round(sc_prover *p, uint64_t *out_evals, uint32_t want);
 
 int resident_start(sc_prover *p, const uint64_t *r_or_null, uint64_t *out_evals);
 int resident_round(sc_prover *p, const uint64_t *r_or_null, uint64_t *out_evals);

@@ -61,6 +61,18 @@ int main(int argc, char **argv) {
     CHECK(merged_row_blocks(1ULL << 23, 1) == 768 && merged_row_blocks(1ULL << 21, 1) == 768 && merged_row_blocks(1ULL << 21, 2) == 1024);
     CHECK(merged_row_blocks(1ULL << 20, 1) == 1024 && merged_row_blocks(1ULL << 15, 1) == 768 && merged_row_blocks(1ULL << 15, 2) == 384 && merged_row_blocks(1ULL << 15, 3) == 256);
     CHECK(merged_row_blocks(1ULL << 15, 1, 100) == 400 && merged_row_blocks(1ULL << 15, 1, 0, false) == 192 && merged_row_blocks(1ULL << 23, 1, 0, false) == 768);
+    // the grid a staged round 1 cuts into sections (protocol.hip, staged_copy_and_round1: spelled out there as it is here) is merged_row_blocks
+    // with by_rows = false, over every shape staged_init_applies admits (nv >= 18: 2^17 pairs and more; one to kMetaProds = 16 rows)
+    for (int lg = 17; lg <= 33; ++lg)
+        for (uint32_t rows = 1; rows <= 16; ++rows)
+            for (int cap : {kMaxGrid, 256, 1}) { // (grid_for_pairs: the production cap, and the experiments build's SC_GRID)
+                const uint64_t n_pairs = 1ULL << lg;
+                int G = n_pairs >= (1ULL << 21) ? 1024 : n_pairs >= (1ULL << 20) ? 768 : n_pairs >= (1ULL << 18) ? 384 : n_pairs >= (1ULL << 17) ? 256 : 192;
+                if (rows == 1) G = std::min(G, kRoundTreeGrid);
+                G = std::min(G, grid_blocks_for_pairs(n_pairs, cap));
+                CHECK(std::min(merged_row_blocks(n_pairs, rows, 0, /*by_rows=*/false), grid_blocks_for_pairs(n_pairs, cap)) == G);
+                CHECK(cap != kMaxGrid || G == (lg >= 21 ? (rows == 1 ? 768 : 1024) : lg == 20 ? 768 : lg >= 18 ? 384 : 256));
+            }
     CHECK(tree_two_pairs(2, false) && tree_two_pairs(3, false) && !tree_two_pairs(1, true) && !tree_two_pairs(4, false) && tree_two_pairs(4, true));
     // tree_lane_terms is the busiest lane's count under the kernel's own loops, for every grid and pair count (powers of two and not)
     for (int grid : {1, 2, 3, 7, 192, 768, 1024})
