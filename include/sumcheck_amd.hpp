@@ -937,6 +937,46 @@ struct GKRRoundSumcheck {
         check(sc_gkr_two_point_init_batch((uint32_t)n, (uint32_t)dim, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), pg2.data(), n ? coeffs[0][0].l : nullptr, 0, &h));
         return GKRBatchProverState(h, n, dim);
     }
+    // The values of a circuit's layers for n instances of ONE dim in one library call (sc_gkr_layers_eval_batch): f1_layers[k][i] is the
+    // wiring of layer k of instance i, layer 0 next to the inputs (f2s[i], f3s[i]).  out[0][i][z] = sum over f1_layers[0][i]'s non-zeros
+    // (z | x << dim | y << 2 dim, v) of v f2s[i][x] f3s[i][y]; out[k][i] the same over f1_layers[k][i] with out[k-1][i] on both sides.
+    // Pointers may repeat across instances and layers.  What prover_init_batch and GKRBatchProverState::next_layer take as f2s and f3s.
+    static std::vector<std::vector<DenseMultilinearExtension>> evaluate_layers_batch(const std::vector<std::vector<const SparseMultilinearExtension *>> &f1_layers,
+                                                                                    const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                                                    const std::vector<const DenseMultilinearExtension *> &f3s) {
+        const size_t n = f2s.size(), n_layers = f1_layers.size();
+        if (f3s.size() != n) throw Panic(SC_ERR_BAD_ARG, "one f2 and one f3 per instance");
+        std::vector<std::vector<DenseMultilinearExtension>> out(n_layers);
+        if (n == 0 || n_layers == 0) return out;
+        if (!f2s[0]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+        const size_t dim = f2s[0]->num_vars, total = n * n_layers;
+        std::vector<const uint64_t *> idx(total), vals(total), p2(n), p3(n);
+        std::vector<uint64_t> nnz(total);
+        std::vector<uint64_t *> po(total);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f2s[i]->num_vars != dim || f3s[i]->num_vars != dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+        }
+        for (size_t k = 0; k < n_layers; ++k) {
+            if (f1_layers[k].size() != n) throw Panic(SC_ERR_BAD_ARG, "one f1 per layer and instance");
+            out[k].resize(n);
+            for (size_t i = 0; i < n; ++i) {
+                const SparseMultilinearExtension *f1 = f1_layers[k][i];
+                if (!f1) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+                if (f1->num_vars != 3 * dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+                idx[k * n + i] = f1->indices.data();
+                vals[k * n + i] = f1->values.empty() ? nullptr : f1->values[0].l;
+                nnz[k * n + i] = f1->indices.size();
+                out[k][i].num_vars = dim;
+                out[k][i].evaluations.resize(size_t(1) << dim);
+                po[k * n + i] = out[k][i].evaluations[0].l;
+            }
+        }
+        check(sc_gkr_layers_eval_batch((uint32_t)n, (uint32_t)dim, (uint32_t)n_layers, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), 0, po.data()));
+        return out;
+    }
 };
 
 } // namespace sumcheck

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, sc_gkr_layer_next_batch, and sc_gkr_two_point_init_batch with sc_gkr_two_point_next_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, sc_gkr_layer_next_batch, and sc_gkr_two_point_init_batch with sc_gkr_two_point_next_batch, and sc_gkr_layers_eval_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -494,6 +494,35 @@ SC_API_GKR2 int sc_gkr_two_point_init_batch(uint32_t n, uint32_t dim, const uint
 SC_API_GKR2 int sc_gkr_two_point_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, const uint64_t *const *f1_vals_or_null,
                                             const uint64_t *nnz_or_null, const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
                                             const uint64_t *const *g2, const uint64_t *coef, uint32_t flags);
+/* ---- the values of a circuit's layers: what every call above consumes as f2 and f3 -------------------------------------------------------
+ * The prover's f2 and f3 for a layer are the values W of the layer underneath ["the next layer's values"].  This call computes them, for n
+ * instances of one dim and n_layers layers, on the device:
+ *     L[f1, A, B][z] = sum over f1's non-zeros [z | x << dim | y << 2 dim, v] of  v A[x] B[y]
+ *     out[0 n + i] = L[f1[0 n + i], f2[i], f3[i]]                    layer 0 is the one next to the inputs
+ *     out[k n + i] = L[f1[k n + i], out[[k-1] n + i], out[[k-1] n + i]]   k >= 1: a layer reads the layer before it on both sides
+ * n_layers == 1 is the plain single-layer evaluation with independent f2 and f3.  Index layout, masking, "repeated indices add up", "any
+ * order of the list" and "zero values are ordinary" are exactly sc_gkr_prove's; outputs are canonical Montgomery limbs, 2^dim x 4 each.
+ * f1_idx, f1_vals, nnz and out are n_layers x n arrays, layer-major; f2 and f3 are n arrays.  Pointers may repeat across instances and across
+ * layers [one wiring for all instances is the usual case]; the pointer arrays and nnz[] are always host memory.  flags: SC_TABLES_ON_DEVICE
+ * => every list, table and output is a device pointer, inputs are read in place and outputs are written in place -- out[k] is then usable
+ * directly as f2 / f3 of sc_gkr_batch_prover_init and sc_gkr_layer_next_batch; without it they are host arrays staged through a cached
+ * work area [sc_release_caches frees it].  The call is synchronous, as the handle's init is.
+ * CHECKS, all before any HIP call where the host can make them; the lowest failing [layer, instance] decides and sc_last_error() starts
+ * with "layer %u instance %u: ": n == 0 or n_layers == 0 is SC_OK and touches nothing; a null argument is SC_ERR_BAD_ARG; dim == 0 is
+ * SC_ERR_CONSTANT_POLY; dim > 21 is SC_ERR_BAD_ARG; per [layer, instance] nnz >= 2^31 [a lane of a cell must stay below 2^63], a null
+ * entry, an output range that overlaps another output or any input, a host-resident index with a bit at or above 3 dim ["... f1 has an
+ * index out of range"] are SC_ERR_BAD_ARG.  A device-resident list with such an index is found on the device, over all layers, in front of
+ * the first launch that follows indices [same status and text]: no output has been written then.
+ * PLANS, counted once per successful call, same bits: batch.gkr_eval_layers_one_block [dim <= 9 and every nnz <= 64 x 2^dim, policy "batch"
+ * != 0]: ONE launch for all layers, one block per instance, tables and cells in 128 B x 2^dim of LDS; batch.gkr_eval_cells [every other
+ * shape]: per layer the cells zeroed, a terms launch [integer atomics into 64 B x n x 2^dim of device memory from the cached work area; a
+ * request above 16 GiB is SC_ERR_OOM with the byte count] and a fold launch on one stream.
+ * SC_API_GKRE is SC_API; a marker of its own, for the reason the older families have theirs [tests/test_gkr_layers_eval_host.py compares
+ * the prototype with the shim's declaration; every older scanner asserts a closed set]. */
+#define SC_API_GKRE SC_API /* [nothing but this comment may follow on the line] */
+/* f1_idx, f1_vals, nnz, out: n_layers x n, layer-major; f2, f3: n, layer 0's inputs; out: each 2^dim x 4 limbs. */
+SC_API_GKRE int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals,
+                                         const uint64_t *nnz, const uint64_t *const *f2, const uint64_t *const *f3, uint32_t flags, uint64_t *const *out);
 /* f4 -- the same two initialisations with f1's non-zeros SPREAD OVER SEVERAL GPUs (worth it from dim ~ 24).
  * Every rank passes a disjoint subset of f1's (index, value) pairs -- any partition -- and all of f3 / g.  A rank's scatter is a
  * partial sum of a_hg, so the ranks' dense tables are added with ONE table-sized integer all-reduce of the widened limbs
@@ -615,7 +644,8 @@ SC_API int sc_set_policy(const char *key, int64_t value);
 SC_API int sc_get_policy(const char *key, int64_t *value);
 /* Launch-plan counters (process-wide, monotone): one per path the host side can choose for a round or an initialisation -- which big-round
  * kernel, which table format, which finalize, which latency-bound form, which exchange.  sc_plan_count() plans, sc_plan_name(i) their
- * names ("big.merged.round1", "tail.slices8", "sharded.p2p", ...; NULL past the end), sc_plan_stats fills out[0..n).  What the GPU test
+ * names ("big.merged.round1", "tail.slices8", "sharded.p2p", "batch.gkr_eval_layers_one_block", "batch.gkr_eval_cells", ...; NULL past the
+ * end), sc_plan_stats fills out[0..n).  What the GPU test
  * suite uses to prove that every plan was reached by a test that compared with the oracle (profiles/plan_coverage.json). */
 SC_API uint32_t sc_plan_count(void);
 SC_API const char *sc_plan_name(uint32_t i);

@@ -763,6 +763,52 @@ pub fn gkr_next_layer_batch<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, la
     });
 }
 
+// The values of a circuit's layers (`sc_gkr_layers_eval_batch`): a private declaration behind the safe wrapper below.
+extern "C" {
+    fn sc_gkr_layers_eval_batch(n: u32, dim: u32, n_layers: u32, f1_idx: *const *const u64, f1_vals: *const *const u64, nnz: *const u64,
+                                f2: *const *const u64, f3: *const *const u64, flags: u32, out: *const *mut u64) -> c_int;
+}
+
+/// The values of a circuit's layers for n instances of ONE `dim` in one FFI call (`sc_gkr_layers_eval_batch`): `f1_layers[k][i]` is the
+/// wiring of layer `k` of instance `i`, layer 0 next to the inputs `(f2[i], f3[i])`.  `out[0][i][z]` is the sum over `f1_layers[0][i]`'s
+/// non-zeros `(z | x << dim | y << 2 dim, v)` of `v f2[i][x] f3[i][y]`; `out[k][i]` the same over `f1_layers[k][i]` with `out[k-1][i]` on
+/// both sides.  The same reference may stand for several instances and layers.  What [`gkr_prover_init_batch`] and
+/// [`gkr_next_layer_batch`] take as `f2` and `f3`, layer by layer.
+pub fn gkr_evaluate_layers_batch<F: Limbs4>(f1_layers: &[Vec<&SparseMultilinearExtension<F>>], f2: &[&DenseMultilinearExtension<F>],
+                                            f3: &[&DenseMultilinearExtension<F>]) -> Vec<Vec<DenseMultilinearExtension<F>>> {
+    let (n, n_layers) = (f2.len(), f1_layers.len());
+    assert_eq!(f3.len(), n, "one f2 and one f3 per instance");
+    if n == 0 || n_layers == 0 {
+        return (0..n_layers).map(|_| Vec::new()).collect();
+    }
+    let dim = f2[0].num_vars;
+    let mut arrays = Vec::with_capacity(n * n_layers);
+    for layer in f1_layers.iter() {
+        assert_eq!(layer.len(), n, "one f1 per layer and instance");
+        for f1 in layer.iter() {
+            assert_eq!(f1.num_vars, 3 * dim);
+            arrays.push(sparse_arrays(*f1));
+        }
+    }
+    for i in 0..n {
+        assert_eq!(f2[i].num_vars, dim);
+        assert_eq!(f3[i].num_vars, dim);
+    }
+    let idx: Vec<*const u64> = arrays.iter().map(|a| a.0.as_ptr()).collect();
+    let vals: Vec<*const u64> = arrays.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let nnz: Vec<u64> = arrays.iter().map(|a| a.0.len() as u64).collect();
+    let p2: Vec<*const u64> = f2.iter().map(|m| m.evaluations.as_ptr() as *const u64).collect();
+    let p3: Vec<*const u64> = f3.iter().map(|m| m.evaluations.as_ptr() as *const u64).collect();
+    let mut tables: Vec<Vec<[u64; 4]>> = (0..n * n_layers).map(|_| vec![[0u64; 4]; 1usize << dim]).collect();
+    let out: Vec<*mut u64> = tables.iter_mut().map(|t| t.as_mut_ptr() as *mut u64).collect();
+    check(unsafe {
+        sc_gkr_layers_eval_batch(n as u32, dim as u32, n_layers as u32, idx.as_ptr(), vals.as_ptr(), nnz.as_ptr(), p2.as_ptr(), p3.as_ptr(), 0, out.as_ptr())
+    });
+    (0..n_layers)
+        .map(|k| (0..n).map(|i| DenseMultilinearExtension::from_evaluations_vec(dim, tables[k * n + i].iter().map(|l| F::from_limbs(*l)).collect())).collect())
+        .collect()
+}
+
 // The two-point form of the handle (`sc_gkr_two_point_init_batch`, `sc_gkr_two_point_next_batch`): private declarations, a block each.
 extern "C" {
     fn sc_gkr_two_point_init_batch(n: u32, dim: u32, f1_idx: *const *const u64, f1_vals: *const *const u64, nnz: *const u64, f2: *const *const u64,

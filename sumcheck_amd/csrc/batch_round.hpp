@@ -341,6 +341,32 @@ __device__ __forceinline__ void bg_accumulate(uint64_t *cell, const GkrBatchInst
     __syncthreads();
 }
 
+// bg_accumulate's sibling for a caller that brings its own term (k_batch_gkr_eval_layers: a circuit layer's values): term(i, x, y) returns
+// non-zero i's canonical term, which is added into cell z; store(c, value) takes cell c's canonical element.  The same cells, the same
+// three steps, the same masking of every index component; bg_accumulate itself is left as it is -- k_batch_gkr and k_batch_gkr_phase keep
+// their code (profiles/gkr_layers_eval_kernel_resources.txt).  Ends behind a barrier.
+template <typename Term, typename Store>
+__device__ __forceinline__ void bg_accumulate_terms(uint64_t *cell, const uint64_t *idx, const uint64_t nnz, const uint32_t dim, const Term &term, const Store &store) {
+    const uint32_t tid = threadIdx.x, cap = 1u << dim, mask = cap - 1u;
+    for (uint32_t i = tid; i < 8u * cap; i += kTsBlock) cell[i] = 0;
+    __syncthreads();
+    for (uint64_t i = tid; i < nnz; i += kTsBlock) {
+        const uint64_t id = idx[i];
+        const uint32_t z = (uint32_t)id & mask, x = (uint32_t)(id >> dim) & mask, y = (uint32_t)(id >> (2 * dim)) & mask;
+        const Fr t = term(i, x, y);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) __hip_atomic_fetch_add(cell + (((uint32_t)j << dim) | z), (uint64_t)t.v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    for (uint32_t c = tid; c < cap; c += kTsBlock) {
+        uint64_t lane[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lane[j] = cell[((uint32_t)j << dim) | c];
+        store(c, wide_fold_cell(lane));
+    }
+    __syncthreads();
+}
+
 // (bt_fin_bytes, the head of a batched kernel's dynamic LDS -- finalize scratch | message: batch_shape.hpp)
 
 } // namespace scd

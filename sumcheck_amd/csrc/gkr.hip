@@ -47,6 +47,7 @@ uint64_t sc_internal_cache_limit();                   // abi.hip: sc_set_cache_l
 void sc_internal_release_eval_cache();                // abi.hip: sc_poly_evaluate's cached work areas
 void sc_internal_release_handle_pool();               // abi.hip: the prover sc_ml_prove keeps between one-shot proofs
 void sc_internal_release_batch_cache();               // batch.hip: sc_ml_prove_batch's work areas
+void sc_internal_release_gkr_eval_cache();            // gkr_layers_eval.hip: sc_gkr_layers_eval_batch's work area
 int sc_internal_run_rounds(sc_prover *p, sch::Blake2b512Rng &rng, uint32_t n_rounds, uint64_t *out_msgs, sch::Fr *out_challenges); // api.hip
 hipStream_t sc_internal_prover_stream(sc_prover *p);                                                  // abi.hip (GKR phase two: see there)
 const void *sc_internal_bound_table(sc_prover *p, uint32_t u);
@@ -562,6 +563,7 @@ extern "C" int sc_release_caches(void) {
     sc_internal_release_eval_cache();
     sc_internal_release_handle_pool();
     sc_internal_release_batch_cache();
+    sc_internal_release_gkr_eval_cache();
     std::lock_guard<std::mutex> lk(g_cache.mu);
     if (g_cache.device >= 0) (void)hipSetDevice(g_cache.device);
     if (g_cache.prover) sc_prover_free(g_cache.prover);

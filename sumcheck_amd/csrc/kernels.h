@@ -409,6 +409,28 @@ struct BatchGkrSlicesArgs {
 // points 2: a second pair of half tables for g2, alpha folded into g's low half and beta into g2's; a term's weight is
 // lo[z_lo] hi[z_hi] + lo2[z_lo] hi2[z_hi], canonical -- the number of terms per cell and with it the lanes' bound are those of points 1.
 hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream, int points = 1);
+// The values of GKR circuit layers (kernels_batch_gkr_eval_layers.hip: sc_gkr_layers_eval_batch): per instance i and layer k
+//     W_k[z] = sum over the non-zeros (z | x << dim | y << 2 dim, v) of layer k's list of  v * A[x] * B[y],
+// with (A, B) = (f2, f3) of the record for layer 0 and (W_{k-1}, W_{k-1}) for every later layer.  inst: n_layers x n records, layer-major
+// (GkrBatchInst::g is not read); out: n_layers x n tables of 2^dim canonical elements, disjoint from each other and from every input.
+// The cells are bg_accumulate's and k_batch_gkr_terms': eight uint64 lanes of 32-bit limbs, integer adds, one wide_fold_cell per cell.
+//   k_batch_gkr_eval_layers  ONE launch for all layers, one block per instance: the current layer's two input tables (one from layer 1 on)
+//                            as canonical 32-byte elements in LDS beside the cells, 128 B x 2^dim; within gkr_batch_shape_fits(dim, the
+//                            largest nnz of any layer).  The records of layers k >= 1 need no f2 / f3;
+//   k_batch_gkr_eval_terms   per layer n x blocks_per_inst blocks behind a zeroing of the cells (n x 8 x 2^dim lanes in device memory, zeroed
+//   k_batch_gkr_eval_fold    by the caller on the same stream), relaxed agent-scope atomic adds; then one lane per (instance, cell).  Any
+//                            dim up to 21, nnz < 2^31 per list (a lane stays below 2^63); layer k's records name layer k - 1's outputs
+//                            as f2 and f3, the stream's order is the only dependence.
+struct GkrEvalLayersArgs {
+    const GkrBatchInst *inst;   // device: one-block form n_layers x n records; cells form the n records of ONE layer
+    uint4 *const *out;          // device: the output tables, as the records are laid out
+    uint64_t *cells;            // cells form: n x 8 x 2^dim lanes, zero on entry
+    uint32_t n, dim, n_layers;
+    uint32_t first;             // (filled in by the launchers: the first instance of a launch -- a grid holds fewer than 2^31 blocks)
+    uint32_t blocks_per_inst;   // (filled in by the cells form's launcher from nnz_max: gkr_bs_term_blocks)
+};
+hipError_t launch_batch_gkr_eval_layers(GkrEvalLayersArgs args, hipStream_t stream);                 // (the dynamic LDS: 128 B x 2^dim, at most 64 KB)
+hipError_t launch_batch_gkr_eval_cells(GkrEvalLayersArgs args, uint64_t nnz_max, hipStream_t stream); // terms + fold of one layer
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -466,6 +488,8 @@ enum Plan {
     kPlanTailRounds,          // k_tail_rounds
     kPlanResidentSlices,      // the interactive protocol's resident kernel: k_tail_slices
     kPlanResidentRounds,      // ... k_tail_rounds
+    kPlanBatchGkrEvalLayersOneBlock, // sc_gkr_layers_eval_batch: k_batch_gkr_eval_layers, one block per instance, ONE launch for all layers (dim <= 9, every nnz <= 64 x 2^dim, policy "batch" != 0); counted once per successful call
+    kPlanBatchGkrEvalLayersCells,    // ... per layer a zeroing of the cells, k_batch_gkr_eval_terms and k_batch_gkr_eval_fold on one stream (every other shape)
     kPlanShardedRcclDirect,   // sharded rounds: ncclAllReduce into the host-mapped page
     kPlanShardedRcclPublish,  // ... all-reduce + publish kernel
     kPlanShardedHost,         // ... the caller's host transport

@@ -264,6 +264,8 @@ bool tail_slot_acquire(sc_prover *p, bool resident); // the device's one tail sl
 void tail_slot_release(sc_prover *p);
 // ---- batch.hip ----
 void sc_internal_release_batch_cache(); // sc_release_caches: sc_ml_prove_batch's work areas
+// ---- gkr_layers_eval.hip ----
+void sc_internal_release_gkr_eval_cache(); // sc_release_caches: sc_gkr_layers_eval_batch's work area
 // the structure every instance shares, as the kernels take it (prover_build's records: abi.hip)
 struct SharedMeta {
     uint32_t nv = 0, U = 0, K = 0, D = 0, max_mult = 0;

@@ -396,6 +396,48 @@ class GKRRoundSumcheck:
         return GKRBatchProverState(h, n, dim)
 
     @staticmethod
+    def evaluate_layers_batch(f1_layers: Sequence[Sequence[SparseMultilinearExtension]], f2s: Sequence[DenseMultilinearExtension],
+                              f3s: Sequence[DenseMultilinearExtension]) -> List[List[DenseMultilinearExtension]]:
+        """The values of a circuit's layers for n instances of one dim, on the GPU (sc_gkr_layers_eval_batch): f1_layers[k][i] is the wiring
+        of layer k of instance i, layer 0 next to the inputs f2s[i], f3s[i] -> out[k][i], with
+            out[0][i][z] = sum over f1_layers[0][i]'s non-zeros (z | x << dim | y << 2 dim, v) of v f2s[i][x] f3s[i][y]
+            out[k][i]    = the same over f1_layers[k][i] with out[k-1][i] on both sides.
+        The same object may stand for several instances and layers (one wiring for all instances is the usual case).  Inputs all on the
+        host or all on the GPU; device tensors in give device tensors out, allocated here and usable directly as the f2s / f3s of
+        prover_init_batch and GKRBatchProverState.next_layer -- a layer's values never leave the device."""
+        n_layers, n = len(f1_layers), len(f2s)
+        assert len(f3s) == n and all(len(layer) == n for layer in f1_layers), "one f1 per layer and instance, one f2 and f3 per instance"
+        if n == 0 or n_layers == 0:
+            check(lib().sc_gkr_layers_eval_batch(n, 0, n_layers, None, None, None, None, None, 0, None))
+            return [[] for _ in range(n_layers)]
+        dim = f2s[0].num_vars
+        flat = [f for layer in f1_layers for f in layer]
+        ons = [m.on_device for m in flat + list(f2s) + list(f3s)]
+        dev = all(ons)
+        assert dev or not any(ons), "mixing host and device inputs is not supported"
+        for i in range(n):
+            assert f2s[i].num_vars == dim and f3s[i].num_vars == dim and all(layer[i].num_vars == 3 * dim for layer in f1_layers), f"instance {i}: a batch has one dim"
+        total = n_layers * n
+        if dev:
+            import torch
+            device = f2s[0].evaluations.device
+            outs = [torch.empty((1 << dim, 4), dtype=torch.int64, device=device) for _ in range(total)]
+            torch.cuda.current_stream(device).synchronize()  # the library works on its own stream
+            out_ptrs = [C.c_void_p(t.data_ptr()) for t in outs]
+        else:
+            outs = [np.empty((1 << dim, 4), dtype=np.uint64) for _ in range(total)]
+            out_ptrs = [_ptr(t) for t in outs]
+
+        def ptrs(vals):
+            return (C.c_void_p * len(vals))(*[C.cast(v, C.c_void_p) for v in vals])
+
+        f1p = [f._ptrs() for f in flat]
+        nnz = (C.c_uint64 * total)(*[f.nnz for f in flat])
+        check(lib().sc_gkr_layers_eval_batch(n, dim, n_layers, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
+                                             ptrs([_dense_ptr(m) for m in f3s]), SC_TABLES_ON_DEVICE if dev else 0, ptrs(out_ptrs)))
+        return [[DenseMultilinearExtension(dim, outs[k * n + i]) for i in range(n)] for k in range(n_layers)]
+
+    @staticmethod
     def verify(rng: Blake2b512Rng, f2_num_vars: int, proof: GKRProof, claimed_sum) -> GKRRoundSumcheckSubClaim:
         """mod.rs:147-192"""
         dim = f2_num_vars
