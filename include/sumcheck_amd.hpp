@@ -662,6 +662,53 @@ struct GKRRoundSumcheckSubClaim {
         }
         return ok;
     }
+    // n subclaims of rounds proved in GATE form (GKRRoundSumcheck::prover_init_batch_gates), from existing calls only: evaluate_subclaims_batch
+    // per list and per point, then M f2(u) f3(v) + A (f2(u) + f3(v)) by sc_fr_elementwise, M = alpha mul(g,u,v) + beta mul(g2,u,v) and A
+    // likewise (g2s and coeffs empty: one point, M = mul(g,u,v))
+    static std::vector<bool> verify_subclaim_gates_batch(const std::vector<GKRRoundSumcheckSubClaim> &subclaims, const std::vector<const SparseMultilinearExtension *> &mul_f1s,
+                                                         const std::vector<const SparseMultilinearExtension *> &add_f1s, const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                         const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                                                         const std::vector<std::vector<Fr>> &g2s = {}, const std::vector<std::array<Fr, 2>> &coeffs = {}) {
+        const size_t n = subclaims.size();
+        const bool two = !g2s.empty() || !coeffs.empty();
+        if (mul_f1s.size() != n || add_f1s.size() != n || (two && (g2s.size() != n || coeffs.size() != n))) throw Panic(SC_ERR_BAD_ARG, "one mul, add, f2, f3, g (and g2, (alpha, beta)) per subclaim");
+        std::vector<std::vector<Fr>> uv;
+        for (const GKRRoundSumcheckSubClaim &c : subclaims) {
+            uv.push_back(c.u);
+            uv.back().insert(uv.back().end(), c.v.begin(), c.v.end());
+        }
+        const auto m1 = evaluate_subclaims_batch(mul_f1s, f2s, f3s, gs, uv), a1 = evaluate_subclaims_batch(add_f1s, f2s, f3s, gs, uv);
+        auto m2 = m1, a2 = a1;
+        if (two) {
+            m2 = evaluate_subclaims_batch(mul_f1s, f2s, f3s, g2s, uv);
+            a2 = evaluate_subclaims_batch(add_f1s, f2s, f3s, g2s, uv);
+        }
+        std::vector<bool> ok(n);
+        for (size_t i = 0; i < n; ++i) {
+            Fr M = m1[i][0], A = a1[i][0], t, s, all;
+            if (two) {
+                Fr x, y;
+                check(sc_fr_elementwise(0, coeffs[i][0].l, m1[i][0].l, x.l, 1));
+                check(sc_fr_elementwise(0, coeffs[i][1].l, m2[i][0].l, y.l, 1));
+                check(sc_fr_elementwise(1, x.l, y.l, M.l, 1));
+                check(sc_fr_elementwise(0, coeffs[i][0].l, a1[i][0].l, x.l, 1));
+                check(sc_fr_elementwise(0, coeffs[i][1].l, a2[i][0].l, y.l, 1));
+                check(sc_fr_elementwise(1, x.l, y.l, A.l, 1));
+            }
+            Fr mt, as;
+            check(sc_fr_elementwise(0, M.l, m1[i][1].l, t.l, 1));
+            check(sc_fr_elementwise(0, t.l, m1[i][2].l, mt.l, 1));
+            check(sc_fr_elementwise(1, m1[i][1].l, m1[i][2].l, s.l, 1));
+            check(sc_fr_elementwise(0, A.l, s.l, as.l, 1));
+            check(sc_fr_elementwise(1, mt.l, as.l, all.l, 1));
+            ok[i] = all == subclaims[i].expected_evaluation;
+        }
+        return ok;
+    }
+    bool verify_subclaim_gates(const SparseMultilinearExtension &mul_f1, const SparseMultilinearExtension &add_f1, const DenseMultilinearExtension &f2, const DenseMultilinearExtension &f3,
+                               const std::vector<Fr> &g) const {
+        return verify_subclaim_gates_batch({*this}, {&mul_f1}, {&add_f1}, {&f2}, {&f3}, {g})[0];
+    }
     bool verify_subclaim_two_point(const SparseMultilinearExtension &f1, const DenseMultilinearExtension &f2, const DenseMultilinearExtension &f3, const std::vector<Fr> &g,
                                    const std::vector<Fr> &g2, const Fr &alpha, const Fr &beta) const {
         return verify_subclaim_two_point_batch({*this}, {&f1}, {&f2}, {&f3}, {g}, {g2}, {std::array<Fr, 2>{alpha, beta}})[0];
@@ -735,6 +782,53 @@ class GKRBatchProverState {
                 DenseMultilinearExtension{nv, std::vector<Fr>(buf.begin() + (size_t(1) << nv), buf.end())}};
     }
     void reset() { check(sc_gkr_batch_prover_reset(h_)); }
+    // the argument arrays sc_gkr_gates_init_batch and sc_gkr_gates_next_batch share (lists null: the wiring is kept)
+    struct GatesArgs {
+        std::vector<const uint64_t *> idx[2], vals[2], p2, p3, pg, pg2;
+        std::vector<uint64_t> nnz[2];
+        bool two = false;
+        GatesArgs(size_t n, size_t dim, const std::vector<const SparseMultilinearExtension *> *mul_f1s, const std::vector<const SparseMultilinearExtension *> *add_f1s,
+                  const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                  const std::vector<std::vector<Fr>> &g2s, const std::vector<std::array<Fr, 2>> &coeffs)
+            : p2(n + 1), p3(n + 1), pg(n + 1), pg2(n + 1) {
+            two = !g2s.empty() || !coeffs.empty();
+            if (f2s.size() != n || f3s.size() != n || gs.size() != n || (two && (g2s.size() != n || coeffs.size() != n))) throw Panic(SC_ERR_BAD_ARG, "one f2, f3 and g (and g2, (alpha, beta)) per instance");
+            const std::vector<const SparseMultilinearExtension *> *lists[2] = {mul_f1s, add_f1s};
+            for (int k = 0; k < 2; ++k) {
+                idx[k].assign(n + 1, nullptr);
+                vals[k].assign(n + 1, nullptr);
+                nnz[k].assign(n + 1, 0);
+                if (lists[k] && lists[k]->size() != n) throw Panic(SC_ERR_BAD_ARG, "one mul and one add list per instance");
+            }
+            for (size_t i = 0; i < n; ++i) {
+                if (!f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+                if (f2s[i]->num_vars != dim || f3s[i]->num_vars != dim || gs[i].size() != dim || (two && g2s[i].size() != dim)) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+                for (int k = 0; k < 2 && lists[k]; ++k) {
+                    const SparseMultilinearExtension *f1 = (*lists[k])[i];
+                    if (!f1) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+                    if (f1->num_vars != 3 * dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+                    idx[k][i] = f1->indices.data();
+                    vals[k][i] = f1->values.empty() ? nullptr : f1->values[0].l;
+                    nnz[k][i] = f1->indices.size();
+                }
+                p2[i] = f2s[i]->evaluations[0].l;
+                p3[i] = f3s[i]->evaluations[0].l;
+                pg[i] = gs[i].empty() ? nullptr : gs[i][0].l;
+                if (two) pg2[i] = g2s[i].empty() ? nullptr : g2s[i][0].l;
+            }
+        }
+    };
+    // next_layer for a handle of GKRRoundSumcheck::prover_init_batch_gates (sc_gkr_gates_next_batch): mul_f1s and add_f1s both empty keeps both
+    // lists, both given is new wiring; g2s and coeffs (both or neither) choose the layer's form.  An argument error leaves a proof in progress where it was.
+    void next_layer_gates(const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
+                          const std::vector<const SparseMultilinearExtension *> &mul_f1s = {}, const std::vector<const SparseMultilinearExtension *> &add_f1s = {},
+                          const std::vector<std::vector<Fr>> &g2s = {}, const std::vector<std::array<Fr, 2>> &coeffs = {}) {
+        const bool keep = mul_f1s.empty() && add_f1s.empty();
+        GatesArgs a(n, dim, keep ? nullptr : &mul_f1s, keep ? nullptr : &add_f1s, f2s, f3s, gs, g2s, coeffs);
+        check(sc_gkr_gates_next_batch(h_, keep ? nullptr : a.idx[0].data(), keep ? nullptr : a.vals[0].data(), keep ? nullptr : a.nnz[0].data(), keep ? nullptr : a.idx[1].data(),
+                                      keep ? nullptr : a.vals[1].data(), keep ? nullptr : a.nnz[1].data(), a.p2.data(), a.p3.data(), a.pg.data(), a.two ? a.pg2.data() : nullptr,
+                                      a.two ? coeffs[0][0].l : nullptr, 0));
+    }
     // the handle onto the next layer's inputs (sc_gkr_layer_next_batch): nothing is allocated; afterwards round 0, as prover_init_batch over
     // these inputs would leave it.  f1s empty: the wiring the handle holds is kept.  Pointers may repeat; an argument error leaves the handle where it was.
     void next_layer(const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s, const std::vector<std::vector<Fr>> &gs,
@@ -936,6 +1030,74 @@ struct GKRRoundSumcheck {
         sc_gkr_batch_prover *h = nullptr;
         check(sc_gkr_two_point_init_batch((uint32_t)n, (uint32_t)dim, idx.data(), vals.data(), nnz.data(), p2.data(), p3.data(), pg.data(), pg2.data(), n ? coeffs[0][0].l : nullptr, 0, &h));
         return GKRBatchProverState(h, n, dim);
+    }
+    // prover_init_batch for layers of multiplication AND addition gates (sc_gkr_gates_init_batch):
+    //     W_out[z] = sum over mul_f1 of v f2[x] f3[y] + sum over add_f1 of v (f2[x] + f3[y]),
+    // claimed at gs[i], or -- g2s and coeffs non-empty -- as alpha W_out(g) + beta W_out(g2).  The handle is driven as any other; its finish
+    // returns f2(u), f3(v) and f3(v) T1(v) + T2(v) in f1_guv, f2_u, f2u_f3v -- the LAST is the value the verifier compares; tables() is
+    // refused; later layers come through GKRBatchProverState::next_layer_gates.  Plans batch.gkr_gates_one_block / batch.gkr_gates_composed: same bits.
+    static GKRBatchProverState prover_init_batch_gates(const std::vector<const SparseMultilinearExtension *> &mul_f1s, const std::vector<const SparseMultilinearExtension *> &add_f1s,
+                                                       const std::vector<const DenseMultilinearExtension *> &f2s, const std::vector<const DenseMultilinearExtension *> &f3s,
+                                                       const std::vector<std::vector<Fr>> &gs, const std::vector<std::vector<Fr>> &g2s = {},
+                                                       const std::vector<std::array<Fr, 2>> &coeffs = {}) {
+        const size_t n = f2s.size();
+        const size_t dim = n && f2s[0] ? f2s[0]->num_vars : 0;
+        GKRBatchProverState::GatesArgs a(n, dim, &mul_f1s, &add_f1s, f2s, f3s, gs, g2s, coeffs);
+        sc_gkr_batch_prover *h = nullptr;
+        check(sc_gkr_gates_init_batch((uint32_t)n, (uint32_t)dim, a.idx[0].data(), a.vals[0].data(), a.nnz[0].data(), a.idx[1].data(), a.vals[1].data(), a.nnz[1].data(), a.p2.data(),
+                                      a.p3.data(), a.pg.data(), a.two ? a.pg2.data() : nullptr, a.two ? coeffs[0][0].l : nullptr, 0, &h));
+        return GKRBatchProverState(h, n, dim);
+    }
+    // evaluate_layers_batch for layers of multiplication AND addition gates (sc_gkr_gates_layers_eval_batch): mul_layers[k][i] and add_layers[k][i]
+    // are the two lists of layer k of instance i; out[k][i][z] = sum over mul of v A[x] B[y] + sum over add of v (A[x] + B[y]), (A, B) = (f2s[i], f3s[i])
+    // for layer 0 and out[k-1][i] on both sides afterwards.  What prover_init_batch_gates and next_layer_gates take as f2s and f3s.
+    static std::vector<std::vector<DenseMultilinearExtension>> evaluate_layers_batch_gates(const std::vector<std::vector<const SparseMultilinearExtension *>> &mul_layers,
+                                                                                          const std::vector<std::vector<const SparseMultilinearExtension *>> &add_layers,
+                                                                                          const std::vector<const DenseMultilinearExtension *> &f2s,
+                                                                                          const std::vector<const DenseMultilinearExtension *> &f3s) {
+        const size_t n = f2s.size(), n_layers = mul_layers.size();
+        if (f3s.size() != n || add_layers.size() != n_layers) throw Panic(SC_ERR_BAD_ARG, "one f2 and one f3 per instance, one mul and one add list per layer");
+        std::vector<std::vector<DenseMultilinearExtension>> out(n_layers);
+        if (n == 0 || n_layers == 0) return out;
+        if (!f2s[0]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+        const size_t dim = f2s[0]->num_vars, total = n * n_layers;
+        std::vector<const uint64_t *> idx[2], vals[2], p2(n), p3(n);
+        std::vector<uint64_t> nnz[2];
+        std::vector<uint64_t *> po(total);
+        for (size_t i = 0; i < n; ++i) {
+            if (!f2s[i] || !f3s[i]) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+            if (f2s[i]->num_vars != dim || f3s[i]->num_vars != dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+            p2[i] = f2s[i]->evaluations[0].l;
+            p3[i] = f3s[i]->evaluations[0].l;
+        }
+        for (int q = 0; q < 2; ++q) {
+            const auto &layers = q ? add_layers : mul_layers;
+            idx[q].resize(total);
+            vals[q].resize(total);
+            nnz[q].resize(total);
+            for (size_t k = 0; k < n_layers; ++k) {
+                if (layers[k].size() != n) throw Panic(SC_ERR_BAD_ARG, "one list per layer and instance");
+                for (size_t i = 0; i < n; ++i) {
+                    const SparseMultilinearExtension *f1 = layers[k][i];
+                    if (!f1) throw Panic(SC_ERR_BAD_ARG, "null polynomial");
+                    if (f1->num_vars != 3 * dim) throw Panic(SC_ERR_BAD_ARG, "assertion failed: dimensions");
+                    idx[q][k * n + i] = f1->indices.data();
+                    vals[q][k * n + i] = f1->values.empty() ? nullptr : f1->values[0].l;
+                    nnz[q][k * n + i] = f1->indices.size();
+                }
+            }
+        }
+        for (size_t k = 0; k < n_layers; ++k) {
+            out[k].resize(n);
+            for (size_t i = 0; i < n; ++i) {
+                out[k][i].num_vars = dim;
+                out[k][i].evaluations.resize(size_t(1) << dim);
+                po[k * n + i] = out[k][i].evaluations[0].l;
+            }
+        }
+        check(sc_gkr_gates_layers_eval_batch((uint32_t)n, (uint32_t)dim, (uint32_t)n_layers, idx[0].data(), vals[0].data(), nnz[0].data(), idx[1].data(), vals[1].data(), nnz[1].data(),
+                                             p2.data(), p3.data(), 0, po.data()));
+        return out;
     }
     // The values of a circuit's layers for n instances of ONE dim in one library call (sc_gkr_layers_eval_batch): f1_layers[k][i] is the
     // wiring of layer k of instance i, layer 0 next to the inputs (f2s[i], f3s[i]).  out[0][i][z] = sum over f1_layers[0][i]'s non-zeros

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, sc_gkr_layer_next_batch, and sc_gkr_two_point_init_batch with sc_gkr_two_point_next_batch, and sc_gkr_layers_eval_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
+#define SC_ABI_VERSION 5 /* 5: sc_set_policy, sc_get_policy, sc_plan_count, sc_plan_name, sc_plan_stats (additions only), and later, still within 5, sc_ml_prove_batch, sc_gkr_prove_batch, sc_poly_evaluate_batch, sc_gkr_subclaim_batch, the sc_batch_prover_* family and the sc_gkr_batch_prover_* family with sc_gkr_batch_prove_round, sc_gkr_layer_next_batch, and sc_gkr_two_point_init_batch with sc_gkr_two_point_next_batch, sc_gkr_layers_eval_batch, and sc_gkr_gates_init_batch with sc_gkr_gates_next_batch and sc_gkr_gates_layers_eval_batch (additions: a caller detects the symbol itself); 4: sc_comm_info, sc_comm_exchange_bench, sc_set_publish_timeout_ms, sc_prover_get_round_timing, sc_library_stats (additions only); 3: sc_prover_set_polling, sc_prover_set_resident, SC_NO_DEVICE_POLLING, sc_set_cache_limit, sc_comm_init_p2p, sc_gkr_prove_sharded (additions only) */
 #define SC_API __attribute__((visibility("default")))
 
 enum sc_status {
@@ -523,6 +523,64 @@ SC_API_GKR2 int sc_gkr_two_point_next_batch(sc_gkr_batch_prover *bp, const uint6
 /* f1_idx, f1_vals, nnz, out: n_layers x n, layer-major; f2, f3: n, layer 0's inputs; out: each 2^dim x 4 limbs. */
 SC_API_GKRE int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals,
                                          const uint64_t *nnz, const uint64_t *const *f2, const uint64_t *const *f3, uint32_t flags, uint64_t *const *out);
+/* ---- the GATE form of the handle: layers of multiplication AND addition gates -----------------------------------------------------------------
+ * Every layer the calls above prove is a sum of multiplication gates.  XZZPS19 [the paper the two-point form follows] proves layers of both
+ * kinds of gate, two wiring lists per layer:
+ *     W_out[z] = sum over MUL [z,x,y,v] of  v f2[x] f3[y]   +   sum over ADD [z,x,y,v] of  v [f2[x] + f3[y]].
+ * With E[z] = eq[g,z], or alpha eq[g,z] + beta eq[g2,z] in two-point form, the claim E-weighted over z is proved by two sumchecks of one shape:
+ *     phase one over x:  f2[x] H1[x] + H2[x],   H1[x] = sum_MUL E[z] v f3[y] + sum_ADD E[z] v,   H2[x] = sum_ADD E[z] v f3[y];
+ *     phase two over y:  f3[y] T1[y] + T2[y],   T1[y] = f2[u] sum_MUL E[z] eq[u,x] v + sum_ADD E[z] eq[u,x] v,   T2[y] = f2[u] sum_ADD E[z] eq[u,x] v.
+ * Messages are three evaluations at 0, 1, 2, as before: n x 3 x 4 limbs per round call, 2 x dim round calls per layer.  P_0[0] + P_0[1] is
+ * alpha W_out[g] + beta W_out[g2]; phase one's last message at u_last is phase two's claim; phase two's last message at v_last is
+ * M f2[u] f3[v] + A [f2[u] + f3[v]] with M and A the E-weighted extensions of the two lists at [u, v].  Every message is the field sum of the
+ * messages of the three multiplication-only instances [MUL, f2, f3], [ADD, f2, 1], [ADD, 1, f3] under the same challenges.
+ * A handle built by sc_gkr_gates_init_batch is a sc_gkr_batch_prover: sc_gkr_batch_prove_round, _finish, _reset, _state and _free work on it
+ * with the calling convention and status codes they have.  On this form
+ *     finish's out_final is  f2[u], f3[v], f3[v] T1[v] + T2[v]  -- the THIRD value is what the verifier compares with its expected evaluation;
+ *     state returns the round and the randomness; a non-NULL tables_out is SC_ERR_BAD_ARG [the plans hold different tables];
+ *     sc_gkr_layer_next_batch and sc_gkr_two_point_next_batch refuse the handle with SC_ERR_BAD_ARG, and sc_gkr_gates_next_batch refuses a
+ *     handle of the older inits.
+ * PLANS, chosen at init, same bits [every output is a canonical element]: batch.gkr_gates_one_block -- dim <= 9, each list <= 64 x 2^dim,
+ * policy "batch" != 0 and policy "gkr_gates_fused" = 1 [the default; read at init]: one block per instance fills work areas of three
+ * tables [k_batch_gkr_gates_phase, two passes over one array of cells inside 128 B x 2^dim of LDS], the rounds are the batch handle's
+ * round kernel over three tables and two products; batch.gkr_gates_composed -- every other shape up to dim 21: an inner handle of 3 n
+ * multiplication-only instances on whatever plan IT chooses [one block, "batch_slices", serial], challenges replicated, the three messages
+ * added on the host.  Each is counted once per round call.
+ * SC_API_GKRG is SC_API; a marker of its own, for the reason the older families have theirs [tests/test_gkr_gates_host.py compares these
+ * prototypes with the shim's declarations; every older scanner asserts a closed set]. */
+#define SC_API_GKRG SC_API /* [nothing but this comment may follow on the line] */
+/* sc_gkr_two_point_init_batch with two lists.  Argument meaning, SC_TABLES_ON_DEVICE, "copied once per distinct pointer" and the checks with
+ * their order are that call's; each list is checked as f1 is there and an error names the list ["instance %u: mul index %llu out of range"
+ * for a host list, "instance %u: mul has an index out of range" / "instance %u: add has an index out of range" for a device list].  A list
+ * with nnz == 0 may have null pointers.  g2_or_null and coef_or_null both NULL: one point; both given: two points; a mixture is
+ * SC_ERR_BAD_ARG. */
+SC_API_GKRG int sc_gkr_gates_init_batch(uint32_t n, uint32_t dim, const uint64_t *const *mul_idx, const uint64_t *const *mul_vals, const uint64_t *mul_nnz,
+                                        const uint64_t *const *add_idx, const uint64_t *const *add_vals, const uint64_t *add_nnz, const uint64_t *const *f2,
+                                        const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2_or_null, const uint64_t *coef_or_null,
+                                        uint32_t flags, sc_gkr_batch_prover **out);
+/* sc_gkr_two_point_next_batch for a gate handle [g2_or_null and coef_or_null as at init: the layer's form].  The six wiring arguments are all
+ * NULL [both lists are kept] or all given; anything else is SC_ERR_BAD_ARG.  The plan is init's; on batch.gkr_gates_one_block a new list
+ * above 64 x 2^dim is SC_ERR_BAD_ARG naming the instance and the list.  CAPACITY: the handle's copy of the inputs is laid out again by
+ * init's rule -- the lists at the front, f2 / f3 behind them, every distinct [pointer, size] once -- inside the bytes init reserved; kept
+ * wiring stays where it is.  A call always fits if its pointers repeat in init's pattern and its lists are kept or no longer than init's.  Every check -- the host's, the capacity rule, the
+ * index check of new device-resident lists over the caller's arrays -- comes before the first write: ANY such error leaves the proof in
+ * progress exactly where it was.  [A HIP error later leaves the handle exhausted until the next successful call.] */
+SC_API_GKRG int sc_gkr_gates_next_batch(sc_gkr_batch_prover *bp, const uint64_t *const *mul_idx_or_null, const uint64_t *const *mul_vals_or_null,
+                                        const uint64_t *mul_nnz_or_null, const uint64_t *const *add_idx_or_null, const uint64_t *const *add_vals_or_null,
+                                        const uint64_t *add_nnz_or_null, const uint64_t *const *f2, const uint64_t *const *f3, const uint64_t *const *g,
+                                        const uint64_t *const *g2_or_null, const uint64_t *coef_or_null, uint32_t flags);
+/* sc_gkr_layers_eval_batch with both lists per [layer, instance]: out = L[mul, A, B] + sum over add's non-zeros [z | x << dim | y << 2 dim, v]
+ * of v [A[x] + B[y]], [A, B] = [f2, f3] for layer 0 and the layer before on both sides afterwards -- what sc_gkr_gates_init_batch and
+ * sc_gkr_gates_next_batch consume as f2 and f3.  mul_* and add_*: n_layers x n arrays, layer-major; a list with nnz == 0 may have null
+ * pointers.  Every check of that call holds, the overlap check included [the ADD lists are inputs as the MUL lists are]; an index error names
+ * the list ["layer %u instance %u: mul has an index out of range" / "... add has an index out of range"], a device-resident one is found
+ * over all layers before any output is written.  The condition on the lanes applies to the two lists together: mul_nnz + add_nnz < 2^31
+ * per [layer, instance].  PLANS, counted once per successful call, same bits: batch.gkr_gates_eval_one_block [dim <= 9, every list of either
+ * kind <= 64 x 2^dim, policy "batch" != 0: ONE launch for all layers, both lists into the same cells in LDS] and batch.gkr_gates_eval_cells
+ * [every other shape: per layer the cells zeroed, a terms launch per kind of list, a fold launch]. */
+SC_API_GKRG int sc_gkr_gates_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *mul_idx, const uint64_t *const *mul_vals,
+                                               const uint64_t *mul_nnz, const uint64_t *const *add_idx, const uint64_t *const *add_vals, const uint64_t *add_nnz,
+                                               const uint64_t *const *f2, const uint64_t *const *f3, uint32_t flags, uint64_t *const *out);
 /* f4 -- the same two initialisations with f1's non-zeros SPREAD OVER SEVERAL GPUs (worth it from dim ~ 24).
  * Every rank passes a disjoint subset of f1's (index, value) pairs -- any partition -- and all of f3 / g.  A rank's scatter is a
  * partial sum of a_hg, so the ranks' dense tables are added with ONE table-sized integer all-reduce of the widened limbs
@@ -639,6 +697,9 @@ SC_API int sc_library_stats(uint64_t *out, uint32_t n);
  *                            still forces the serial plan.  0 until the sliced plan has been measured.  For sc_gkr_batch_prover_init the key opens
  *                            dim 10 .. 16 [nnz <= 64 x 2^dim, at most 16 GiB of work areas and cells] to plan batch.gkr_rounds_slices: both
  *                            initialisations spread over many blocks per instance, the first rounds of each phase sliced (dim >= 11).
+ *   "gkr_gates_fused" (1)    sc_gkr_gates_init_batch: 0 every gate handle built from now on is composed of three multiplication-only instances per
+ *                            instance (plan batch.gkr_gates_composed) even where one block per instance would hold it (batch.gkr_gates_one_block);
+ *                            read when a handle is built.
  * Unknown key or value out of range: SC_ERR_BAD_ARG. */
 SC_API int sc_set_policy(const char *key, int64_t value);
 SC_API int sc_get_policy(const char *key, int64_t *value);

@@ -909,6 +909,167 @@ pub fn gkr_next_layer_batch_two_point<F: Limbs4>(state: &mut HipGkrBatchProverSt
     });
 }
 
+// The gate form of the handle (`sc_gkr_gates_init_batch`, `sc_gkr_gates_next_batch`): private declarations, a block each.
+extern "C" {
+    fn sc_gkr_gates_init_batch(n: u32, dim: u32, mul_idx: *const *const u64, mul_vals: *const *const u64, mul_nnz: *const u64, add_idx: *const *const u64,
+                               add_vals: *const *const u64, add_nnz: *const u64, f2: *const *const u64, f3: *const *const u64, g: *const *const u64,
+                               g2_or_null: *const *const u64, coef_or_null: *const u64, flags: u32, out: *mut *mut sc_gkr_batch_prover) -> c_int;
+}
+extern "C" {
+    fn sc_gkr_gates_next_batch(bp: *mut sc_gkr_batch_prover, mul_idx_or_null: *const *const u64, mul_vals_or_null: *const *const u64, mul_nnz_or_null: *const u64,
+                               add_idx_or_null: *const *const u64, add_vals_or_null: *const *const u64, add_nnz_or_null: *const u64, f2: *const *const u64,
+                               f3: *const *const u64, g: *const *const u64, g2_or_null: *const *const u64, coef_or_null: *const u64, flags: u32) -> c_int;
+}
+
+extern "C" {
+    fn sc_gkr_gates_layers_eval_batch(n: u32, dim: u32, n_layers: u32, mul_idx: *const *const u64, mul_vals: *const *const u64, mul_nnz: *const u64,
+                                      add_idx: *const *const u64, add_vals: *const *const u64, add_nnz: *const u64, f2: *const *const u64,
+                                      f3: *const *const u64, flags: u32, out: *const *mut u64) -> c_int;
+}
+
+/// [`gkr_evaluate_layers_batch`] for layers of multiplication and addition gates (`sc_gkr_gates_layers_eval_batch`): `mul_layers[k][i]` and
+/// `add_layers[k][i]` are the two lists of layer `k` of instance `i`; `out[k][i][z]` is the sum over `mul` of `v A[x] B[y]` plus the sum
+/// over `add` of `v (A[x] + B[y])`, `(A, B) = (f2[i], f3[i])` for layer 0 and `out[k-1][i]` on both sides afterwards.
+pub fn gkr_evaluate_layers_batch_gates<F: Limbs4>(mul_layers: &[Vec<&SparseMultilinearExtension<F>>], add_layers: &[Vec<&SparseMultilinearExtension<F>>],
+                                                  f2: &[&DenseMultilinearExtension<F>], f3: &[&DenseMultilinearExtension<F>]) -> Vec<Vec<DenseMultilinearExtension<F>>> {
+    let (n, n_layers) = (f2.len(), mul_layers.len());
+    assert_eq!(f3.len(), n, "one f2 and one f3 per instance");
+    assert_eq!(add_layers.len(), n_layers, "one mul and one add list per layer");
+    if n == 0 || n_layers == 0 {
+        return (0..n_layers).map(|_| Vec::new()).collect();
+    }
+    let dim = f2[0].num_vars;
+    let collect = |layers: &[Vec<&SparseMultilinearExtension<F>>]| {
+        let mut arrays = Vec::with_capacity(n * n_layers);
+        for layer in layers.iter() {
+            assert_eq!(layer.len(), n, "one list per layer and instance");
+            for f1 in layer.iter() {
+                assert_eq!(f1.num_vars, 3 * dim);
+                arrays.push(sparse_arrays(*f1));
+            }
+        }
+        arrays
+    };
+    let (ma, aa) = (collect(mul_layers), collect(add_layers));
+    for i in 0..n {
+        assert_eq!(f2[i].num_vars, dim);
+        assert_eq!(f3[i].num_vars, dim);
+    }
+    let mi: Vec<*const u64> = ma.iter().map(|a| a.0.as_ptr()).collect();
+    let mv: Vec<*const u64> = ma.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let mn: Vec<u64> = ma.iter().map(|a| a.0.len() as u64).collect();
+    let ai: Vec<*const u64> = aa.iter().map(|a| a.0.as_ptr()).collect();
+    let av: Vec<*const u64> = aa.iter().map(|a| a.1.as_ptr() as *const u64).collect();
+    let an: Vec<u64> = aa.iter().map(|a| a.0.len() as u64).collect();
+    let p2: Vec<*const u64> = f2.iter().map(|m| m.evaluations.as_ptr() as *const u64).collect();
+    let p3: Vec<*const u64> = f3.iter().map(|m| m.evaluations.as_ptr() as *const u64).collect();
+    let mut tables: Vec<Vec<[u64; 4]>> = (0..n * n_layers).map(|_| vec![[0u64; 4]; 1usize << dim]).collect();
+    let out: Vec<*mut u64> = tables.iter_mut().map(|t| t.as_mut_ptr() as *mut u64).collect();
+    check(unsafe {
+        sc_gkr_gates_layers_eval_batch(n as u32, dim as u32, n_layers as u32, mi.as_ptr(), mv.as_ptr(), mn.as_ptr(), ai.as_ptr(), av.as_ptr(), an.as_ptr(), p2.as_ptr(),
+                                       p3.as_ptr(), 0, out.as_ptr())
+    });
+    (0..n_layers)
+        .map(|k| (0..n).map(|i| DenseMultilinearExtension::from_evaluations_vec(dim, tables[k * n + i].iter().map(|l| F::from_limbs(*l)).collect())).collect())
+        .collect()
+}
+
+/// One instance of a layer of multiplication and addition gates:
+/// `W_out[z] = sum over mul of v f2[x] f3[y] + sum over add of v (f2[x] + f3[y])`, claimed at `g`.  `mul` and `add` are `None`
+/// together -- only in [`gkr_next_layer_batch_gates`], where that keeps the wiring the handle holds.
+pub struct GkrGatesInstance<'a, F: Limbs4> {
+    pub mul: Option<&'a SparseMultilinearExtension<F>>,
+    pub add: Option<&'a SparseMultilinearExtension<F>>,
+    pub f2: &'a DenseMultilinearExtension<F>,
+    pub f3: &'a DenseMultilinearExtension<F>,
+    pub g: &'a [F],
+}
+
+struct GatesArrays {
+    lists: Vec<(Vec<u64>, Vec<[u64; 4]>)>, // mul, add per instance
+    gls: Vec<Vec<[u64; 4]>>,
+    g2s: Vec<Vec<[u64; 4]>>,
+    coef: Vec<[u64; 4]>,
+}
+
+fn gates_arrays<F: Limbs4>(layer: &[GkrGatesInstance<F>], second: Option<&[GkrSecondPoint<F>]>, dim: usize) -> GatesArrays {
+    let n = layer.len();
+    let mut a = GatesArrays { lists: Vec::new(), gls: Vec::with_capacity(n), g2s: Vec::new(), coef: Vec::new() };
+    for inst in layer.iter() {
+        assert_eq!(inst.f2.num_vars, dim);
+        assert_eq!(inst.f3.num_vars, dim);
+        assert_eq!(inst.g.len(), dim);
+        if let (Some(m), Some(d)) = (inst.mul, inst.add) {
+            assert_eq!(m.num_vars, 3 * dim);
+            assert_eq!(d.num_vars, 3 * dim);
+            a.lists.push(sparse_arrays(m));
+            a.lists.push(sparse_arrays(d));
+        }
+        a.gls.push(inst.g.iter().map(|x| x.to_limbs()).collect());
+    }
+    if let Some(s) = second {
+        let (g2s, coef) = second_point_arrays(s, n, dim);
+        a.g2s = g2s;
+        a.coef = coef;
+    }
+    a
+}
+
+/// [`gkr_prover_init_batch`] for layers of multiplication and addition gates (`sc_gkr_gates_init_batch`), in one-point form or -- with
+/// `second` -- in two-point form.  Rounds, reset and state are the handle's; [`gkr_finish_batch`] returns `f2(u)`, `f3(v)` and
+/// `f3(v) T1(v) + T2(v)` in the three value fields, the last being what the verifier compares with its expected evaluation; later layers
+/// come through [`gkr_next_layer_batch_gates`].
+pub fn gkr_prover_init_batch_gates<F: Limbs4>(instances: &[GkrGatesInstance<F>], second: Option<&[GkrSecondPoint<F>]>) -> HipGkrBatchProverState<F> {
+    let n = instances.len();
+    let dim = if n > 0 { instances[0].f2.num_vars } else { 0 };
+    assert!(instances.iter().all(|i| i.mul.is_some() && i.add.is_some()), "init takes both lists of every instance");
+    let a = gates_arrays(instances, second, dim);
+    let list = |k: usize| -> (Vec<*const u64>, Vec<*const u64>, Vec<u64>) {
+        let own: Vec<&(Vec<u64>, Vec<[u64; 4]>)> = a.lists.iter().skip(k).step_by(2).collect();
+        (own.iter().map(|l| l.0.as_ptr()).collect(), own.iter().map(|l| l.1.as_ptr() as *const u64).collect(), own.iter().map(|l| l.0.len() as u64).collect())
+    };
+    let (mi, mv, mn) = list(0);
+    let (ai, av, an) = list(1);
+    let f2: Vec<*const u64> = instances.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = instances.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = a.gls.iter().map(|x| x.as_ptr() as *const u64).collect();
+    let g2: Vec<*const u64> = a.g2s.iter().map(|x| x.as_ptr() as *const u64).collect();
+    let mut handle: *mut sc_gkr_batch_prover = core::ptr::null_mut();
+    check(unsafe {
+        sc_gkr_gates_init_batch(n as u32, dim as u32, mi.as_ptr(), mv.as_ptr(), mn.as_ptr(), ai.as_ptr(), av.as_ptr(), an.as_ptr(), f2.as_ptr(), f3.as_ptr(), g.as_ptr(),
+                                if second.is_some() { g2.as_ptr() } else { core::ptr::null() },
+                                if second.is_some() { a.coef.as_ptr() as *const u64 } else { core::ptr::null() }, 0, &mut handle)
+    });
+    HipGkrBatchProverState { handle, n, dim, _f: core::marker::PhantomData }
+}
+
+/// [`gkr_next_layer_batch`] for a handle of [`gkr_prover_init_batch_gates`] (`sc_gkr_gates_next_batch`): every instance with both
+/// lists (new wiring) or every instance with neither (the handle's wiring is kept); `second` chooses the layer's form.
+pub fn gkr_next_layer_batch_gates<F: Limbs4>(state: &mut HipGkrBatchProverState<F>, layer: &[GkrGatesInstance<F>], second: Option<&[GkrSecondPoint<F>]>) {
+    let (n, dim) = (state.n, state.dim);
+    assert_eq!(layer.len(), n, "one entry per instance of the handle");
+    let keep = layer.iter().all(|i| i.mul.is_none() && i.add.is_none());
+    assert!(keep || layer.iter().all(|i| i.mul.is_some() && i.add.is_some()), "new wiring for every instance, or for none");
+    let a = gates_arrays(layer, second, dim);
+    let list = |k: usize| -> (Vec<*const u64>, Vec<*const u64>, Vec<u64>) {
+        let own: Vec<&(Vec<u64>, Vec<[u64; 4]>)> = a.lists.iter().skip(k).step_by(2).collect();
+        (own.iter().map(|l| l.0.as_ptr()).collect(), own.iter().map(|l| l.1.as_ptr() as *const u64).collect(), own.iter().map(|l| l.0.len() as u64).collect())
+    };
+    let (mi, mv, mn) = list(0);
+    let (ai, av, an) = list(1);
+    let f2: Vec<*const u64> = layer.iter().map(|i| i.f2.evaluations.as_ptr() as *const u64).collect();
+    let f3: Vec<*const u64> = layer.iter().map(|i| i.f3.evaluations.as_ptr() as *const u64).collect();
+    let g: Vec<*const u64> = a.gls.iter().map(|x| x.as_ptr() as *const u64).collect();
+    let g2: Vec<*const u64> = a.g2s.iter().map(|x| x.as_ptr() as *const u64).collect();
+    let pp = |v: &Vec<*const u64>| if keep { core::ptr::null() } else { v.as_ptr() };
+    let pn = |v: &Vec<u64>| if keep { core::ptr::null() } else { v.as_ptr() };
+    check(unsafe {
+        sc_gkr_gates_next_batch(state.handle, pp(&mi), pp(&mv), pn(&mn), pp(&ai), pp(&av), pn(&an), f2.as_ptr(), f3.as_ptr(), g.as_ptr(),
+                                if second.is_some() { g2.as_ptr() } else { core::ptr::null() },
+                                if second.is_some() { a.coef.as_ptr() as *const u64 } else { core::ptr::null() }, 0)
+    });
+}
+
 /// What [`gkr_finish_batch`] returns per instance: the points and the subclaim's oracle values, at no extra pass over the tables.
 pub struct GkrBatchFinal<F: Limbs4> {
     pub u: Vec<F>,

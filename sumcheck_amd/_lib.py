@@ -164,6 +164,16 @@ SIGNATURES_GKRE = {
     "sc_gkr_layers_eval_batch": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), C.c_uint32, C.POINTER(_V)]),
 }
 
+# ... and with SC_API_GKRG: the gate form of the GKR batch handle (sc_gkr_gates_init_batch / _next_batch), also within ABI version 5
+SIGNATURES_GKRG = {
+    "sc_gkr_gates_init_batch": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V),
+                                          C.POINTER(_V), C.POINTER(_V), _V, C.c_uint32, C.POINTER(_V)]),
+    "sc_gkr_gates_next_batch": (C.c_int, [_V, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V),
+                                          C.POINTER(_V), _V, C.c_uint32]),
+    "sc_gkr_gates_layers_eval_batch": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V), C.POINTER(_V), u64p, C.POINTER(_V),
+                                                 C.POINTER(_V), C.c_uint32, C.POINTER(_V)]),
+}
+
 ABI_VERSION = 5  # SC_ABI_VERSION of include/sumcheck_hip.h as declared above
 _lib = None
 
@@ -201,7 +211,7 @@ def lib():
         # An A/B run against an OLDER build (tools/ab.sh) sets SC_AB_ALLOW_MISSING=1 next to SC_LIB_PATH: entry points that build lacks
         # become stubs that raise when called.  Without it every declared symbol must resolve, whatever file SC_LIB_PATH names.
         allow_missing = os.environ.get("SC_AB_ALLOW_MISSING") == "1"
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()) + list(SIGNATURES_GKRB.items()) + list(SIGNATURES_GKRL.items()) + list(SIGNATURES_GKR2.items()) + list(SIGNATURES_GKRE.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()) + list(SIGNATURES_GKRB.items()) + list(SIGNATURES_GKRL.items()) + list(SIGNATURES_GKR2.items()) + list(SIGNATURES_GKRE.items()) + list(SIGNATURES_GKRG.items()):
             try:
                 fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:

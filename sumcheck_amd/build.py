@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsumcheck_hip.so")
 OUT_EXP = os.path.join(HERE, "libsumcheck_hip_exp.so")
-SOURCES = ["kernels_big.hip", "kernels_lag.hip", "kernels.hip", "kernels_tail.hip", "kernels_batch.hip", "kernels_batch_gkr.hip", "kernels_batch_eval.hip", "kernels_batch_rounds.hip", "kernels_batch_round_slices.hip", "kernels_batch_gkr_rounds.hip", "kernels_batch_gkr_round_slices.hip", "kernels_batch_gkr_eval_layers.hip", "kernels_wide.hip", "kernels_wide16.hip", "gkr.hip", "abi.hip", "protocol.hip", "batch.hip", "batch_rounds.hip", "gkr_batch_rounds.hip", "gkr_layers_eval.hip", "comm.hip", "kernels_selftest.hip"]
+SOURCES = ["kernels_big.hip", "kernels_lag.hip", "kernels.hip", "kernels_tail.hip", "kernels_batch.hip", "kernels_batch_gkr.hip", "kernels_batch_eval.hip", "kernels_batch_rounds.hip", "kernels_batch_round_slices.hip", "kernels_batch_gkr_rounds.hip", "kernels_batch_gkr_round_slices.hip", "kernels_batch_gkr_eval_layers.hip", "kernels_batch_gkr_gates.hip", "kernels_wide.hip", "kernels_wide16.hip", "gkr.hip", "abi.hip", "protocol.hip", "batch.hip", "batch_rounds.hip", "gkr_batch_rounds.hip", "gkr_gates.hip", "gkr_layers_eval.hip", "comm.hip", "kernels_selftest.hip"]
 HEADERS = ["fr_device.hpp", "fe_device.hpp", "f29_pack.hpp","kernel_common.hpp", "finalize_device.hpp", "batch_round.hpp", "wide_cell.hpp", "fe_mad_chain.inc", "fr_mac.inc", "fr_mul_gen.inc", "kernels.h", "host_fr.hpp", "transcript.hpp", "prover_internal.hpp", "load_factor.hpp", "wide_tree.hpp", "lag_index.hpp", "lane_sum.hpp", "batch_shape.hpp", "batch_slices.hpp", "round_slots.hpp", os.path.join("..", "..", "include", "sumcheck_hip.h")]
 EXTRA = os.environ.get("SC_BUILD_EXTRA", "").split()  # e.g. SC_BUILD_EXTRA="-DSC_TAIL_CLOCKS" for a one-off local build
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]

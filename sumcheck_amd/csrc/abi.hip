@@ -1137,7 +1137,7 @@ constexpr PolicyDef kPolicyDefs[scd::kPolCount] = {
     {"pipeline", 1, 0, 1},     {"resident", 1, 0, 1},          {"tail_slices", 1, 0, 1}, {"vram_mailbox", 1, 0, 1},           {"wide_tree", 1, 0, 1},
     {"rccl_direct", 1, 0, 1},  {"shard_gather_log2", 15, 1, 15}, {"gkr_direct", 1, 0, 1},  {"wait_spins", 1 << 22, 1, 0xffffffffLL}, {"tail", 1, 0, 1},
     {"staged_init", 1, 0, 1},  {"batch", 1, 0, 2},        {"lag_single", 2, 0, scd::kLagMaxSkip},
-    {"batch_slices", 0, 0, 1},
+    {"batch_slices", 0, 0, 1}, {"gkr_gates_fused", 1, 0, 1},
 };
 struct PolicyTable {
     std::atomic<int64_t> v[scd::kPolCount];
@@ -1162,7 +1162,7 @@ constexpr const char *kPlanNames[scd::kPlanCount] = {
     "big.merged.round1", "big.merged.bind_chain", "big.merged.bind", "big.claim_identity", "big.store_f29", "big.store_canonical", "big.per_product_tree",
     "big.wide", "big.wide16", "big.generic", "big.node_by_node", "big.bind_pass", "big.streamed", "big.staged_round1", "big.lag_class_round", "big.lag_catch_up", "big.lag_materialize", "finalize.multi_block", "finalize.one_block", "finalize.no_lds",
     "small.launched", "small.combos_table", "small.ptrs", "small.pipelined", "tail.slices8", "tail.slices12", "tail.rounds", "resident.slices",
-    "resident.rounds", "batch.gkr_eval_layers_one_block", "batch.gkr_eval_cells", "sharded.rccl_direct", "sharded.rccl_publish", "sharded.host", "sharded.p2p", "batch.gkr_two_point", "sharded.gather_tail", "batch.rounds_slices", "gkr.bucketed_grouped",
+    "resident.rounds", "batch.gkr_eval_layers_one_block", "batch.gkr_eval_cells", "batch.gkr_gates_one_block", "batch.gkr_gates_composed", "batch.gkr_gates_eval_one_block", "batch.gkr_gates_eval_cells", "sharded.rccl_direct", "sharded.rccl_publish", "sharded.host", "sharded.p2p", "batch.gkr_two_point", "sharded.gather_tail", "batch.rounds_slices", "gkr.bucketed_grouped",
     "batch.gkr_next_layer", "gkr.bucketed_counted", "batch.gkr_rounds_slices", "gkr.list_form", "gkr.eq_direct", "gkr.coeff_from_bound_table", "batch.gkr_rounds_one_block", "batch.gkr_rounds_serial", "gkr.sharded", "batch.rounds_one_block", "batch.rounds_serial", "fold_multi",
     "batch.eval_one_block", "batch.eval_serial", "batch.gkr_eval_one_block", "batch.gkr_eval_serial",
     "batch.one_block", "batch.serial", "batch.gkr_one_block", "batch.gkr_serial",

@@ -67,12 +67,22 @@ struct sc_gkr_batch_prover {
     size_t nl_g2_off = 0, nl_coef_off = 0; // ... and their places in a layer's staging image, behind its g
     char *d_tab2 = nullptr;          // (inside d_buf, serial plan) ONE scratch table of 2^dim elements: the dense table of g2 before it is combined
     int points() const { return two_point ? 2 : 1; }
+    // ---- the gate form (sc_gkr_gates_init_batch, gkr_gates.hip): a handle built there is nothing but this, and every call below forwards ----
+    GkrGates *gates = nullptr;
 };
+
+sc_gkr_batch_prover *gkr_gates_wrap(GkrGates *g) {
+    sc_gkr_batch_prover *bp = new (std::nothrow) sc_gkr_batch_prover();
+    if (bp) bp->gates = g;
+    return bp;
+}
+GkrGates *gkr_gates_of(sc_gkr_batch_prover *bp) { return bp->gates; }
 
 namespace {
 
 void destroy(sc_gkr_batch_prover *bp) {
     if (!bp) return;
+    if (bp->gates) gkr_gates_destroy(bp->gates);
     for (sc_prover *p : bp->p1)
         if (p) sc_prover_free(p);
     for (sc_prover *p : bp->p2)
@@ -409,6 +419,7 @@ extern "C" void sc_gkr_batch_prover_free(sc_gkr_batch_prover *bp) { destroy(bp);
 
 extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t *r_or_null, uint32_t r_shared, uint64_t *out_evals) {
     if (!bp || !out_evals) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    if (bp->gates) return gkr_gates_prove_round(bp->gates, r_or_null, r_shared, out_evals);
     // validation, sc_batch_prove_round's precedence; every check comes before the first change to the handle
     if (bp->exhausted) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "Prover is not active");
     if (r_or_null && bp->round == 0) return sc_internal_fail(SC_ERR_FIRST_ROUND_HAS_MSG, "first round should be prover first.");
@@ -482,6 +493,7 @@ extern "C" int sc_gkr_batch_prove_round(sc_gkr_batch_prover *bp, const uint64_t 
 
 extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_t *r, uint32_t r_shared, uint64_t *out_uv_or_null, uint64_t *out_final_or_null) {
     if (!bp || !r) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
+    if (bp->gates) return gkr_gates_finish(bp->gates, r, r_shared, out_uv_or_null, out_final_or_null);
     if (bp->exhausted || bp->round != 2 * bp->dim) return sc_internal_fail(SC_ERR_NOT_ACTIVE, "finish needs a prover that has answered its last round");
     std::vector<sch::Fr> chal;
     if (int rc = take_challenges(bp->n, r, r_shared, chal)) return rc;
@@ -526,6 +538,7 @@ extern "C" int sc_gkr_batch_prover_finish(sc_gkr_batch_prover *bp, const uint64_
 
 extern "C" int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness, uint64_t *tables_out, uint32_t *round) {
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (bp->gates) return gkr_gates_state(bp->gates, instance, randomness, n_randomness, tables_out, round);
     if (instance >= bp->n) return sc_internal_fail(SC_ERR_BAD_ARG, "instance %u: the handle holds %u instances", instance, bp->n);
     batch_state_head(bp->randomness, instance, bp->round, randomness, n_randomness, round);
     if (!tables_out) return SC_OK;
@@ -541,6 +554,7 @@ extern "C" int sc_gkr_batch_prover_state(sc_gkr_batch_prover *bp, uint32_t insta
 
 extern "C" int sc_gkr_batch_prover_reset(sc_gkr_batch_prover *bp) {
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (bp->gates) return gkr_gates_reset(bp->gates);
     if (!bp->work_areas())
         for (uint32_t i = 0; i < bp->n; ++i) // phase one's provers borrow the handle's own tables: rewound in place (phase two's are rewound over new tables at the phase change)
             if (int rc = sc_prover_reset(bp->p1[i], nullptr, SC_TABLES_ON_DEVICE)) return prefix_instance(rc, i);
@@ -584,6 +598,7 @@ int next_layer(sc_gkr_batch_prover *bp, const uint64_t *const *f1_idx_or_null, c
                const uint64_t *const *f3, const uint64_t *const *g, const uint64_t *const *g2, const uint64_t *coef, uint32_t flags) {
     // ---- everything the host can check, before any HIP call and before the first change to the handle ----
     if (!bp) return sc_internal_fail(SC_ERR_BAD_ARG, "null prover");
+    if (bp->gates) return sc_internal_fail(SC_ERR_BAD_ARG, "the handle was built by sc_gkr_gates_init_batch: its layers come through sc_gkr_gates_next_batch");
     if (!f2 || !f3 || !g) return sc_internal_fail(SC_ERR_BAD_ARG, "null argument");
     const bool new_f1 = f1_idx_or_null && f1_vals_or_null && nnz_or_null;
     if (!new_f1 && (f1_idx_or_null || f1_vals_or_null || nnz_or_null))

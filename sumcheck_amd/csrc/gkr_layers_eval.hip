@@ -76,9 +76,34 @@ void sc_internal_release_gkr_eval_cache() {
     g_eval_area.free_all();
 }
 
+namespace {
+// sc_gkr_layers_eval_batch (add_idx, add_vals and add_nnz null: multiplication gates only, errors name the list f1) and
+// sc_gkr_gates_layers_eval_batch (an ADD list beside every MUL list, errors name mul or add): the same checks, the same image with the ADD
+// records behind the MUL records, the same work area; the gate form launches kernels_batch_gkr_gates.hip's kernels and counts its own plans
+int eval_layers(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *add_idx,
+                const uint64_t *const *add_vals, const uint64_t *add_nnz, const uint64_t *const *f2, const uint64_t *const *f3, uint32_t flags, uint64_t *const *out);
+} // namespace
+
 extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz,
                                         const uint64_t *const *f2, const uint64_t *const *f3, uint32_t flags, uint64_t *const *out) {
+    return eval_layers(n, dim, n_layers, f1_idx, f1_vals, nnz, nullptr, nullptr, nullptr, f2, f3, flags, out);
+}
+
+// sc_gkr_layers_eval_batch with both lists per (layer, instance): W_out[z] = sum_MUL v A[x] B[y] + sum_ADD v (A[x] + B[y])
+extern "C" int sc_gkr_gates_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *mul_idx, const uint64_t *const *mul_vals, const uint64_t *mul_nnz,
+                                              const uint64_t *const *add_idx, const uint64_t *const *add_vals, const uint64_t *add_nnz, const uint64_t *const *f2,
+                                              const uint64_t *const *f3, uint32_t flags, uint64_t *const *out) {
     if (n == 0 || n_layers == 0) return SC_OK;
+    if (!add_idx || !add_vals || !add_nnz) return sc_internal_fail(SC_ERR_BAD_ARG, "layer 0 instance 0: null argument");
+    return eval_layers(n, dim, n_layers, mul_idx, mul_vals, mul_nnz, add_idx, add_vals, add_nnz, f2, f3, flags, out);
+}
+
+namespace {
+int eval_layers(uint32_t n, uint32_t dim, uint32_t n_layers, const uint64_t *const *f1_idx, const uint64_t *const *f1_vals, const uint64_t *nnz, const uint64_t *const *add_idx,
+                const uint64_t *const *add_vals, const uint64_t *add_nnz, const uint64_t *const *f2, const uint64_t *const *f3, uint32_t flags, uint64_t *const *out) {
+    if (n == 0 || n_layers == 0) return SC_OK;
+    const bool gates = add_idx != nullptr;
+    const char *const mul_name = gates ? "mul" : "f1";
     // ---- everything the host can check, before any HIP call: the lowest failing (layer, instance) decides ----
     if (!f1_idx || !f1_vals || !nnz || !f2 || !f3 || !out) return sc_internal_fail(SC_ERR_BAD_ARG, "layer 0 instance 0: null argument");
     if (dim == 0) return sc_internal_fail(SC_ERR_CONSTANT_POLY, "layer 0 instance 0: Attempt to prove a constant.");
@@ -98,6 +123,10 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
             if (nnz[r] >= (1ULL << 31)) continue; // (refused below)
             add(f1_idx[r], (size_t)nnz[r] * 8);
             add(f1_vals[r], (size_t)nnz[r] * 32);
+            if (gates && add_nnz[r] < (1ULL << 31)) {
+                add(add_idx[r], (size_t)add_nnz[r] * 8);
+                add(add_vals[r], (size_t)add_nnz[r] * 32);
+            }
         }
         for (uint32_t i = 0; i < n; ++i) {
             add(f2[i], tab_bytes);
@@ -122,16 +151,23 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
         for (uint32_t i = 0; i < n; ++i) {
             const size_t r = (size_t)k * n + i;
             if (nnz[r] >= (1ULL << 31)) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: nnz too large (a list holds fewer than 2^31 non-zeros)", k, i);
+            if (gates && (add_nnz[r] >= (1ULL << 31) || nnz[r] + add_nnz[r] >= (1ULL << 31)))
+                return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: nnz too large (the two lists together hold fewer than 2^31 non-zeros)", k, i);
             if ((nnz[r] && (!f1_idx[r] || !f1_vals[r])) || (k == 0 && (!f2[i] || !f3[i])) || !out[r]) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: null argument", k, i);
+            if (gates && add_nnz[r] && (!add_idx[r] || !add_vals[r])) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: null argument", k, i);
             const uintptr_t ob = reinterpret_cast<uintptr_t>(out[r]), oe = ob + tab_bytes;
             if (meets(ins, ins_pre, ob, oe, -1)) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: the output overlaps an input", k, i);
             const ptrdiff_t self = std::lower_bound(outs.begin(), outs.end(), Range{ob, oe}, by_begin) - outs.begin();
             if (meets(outs, outs_pre, ob, oe, self)) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: the output overlaps another output", k, i);
             if (!dev_in)
                 for (uint64_t t = 0; t < nnz[r]; ++t)
-                    if ((f1_idx[r][t] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: f1 has an index out of range", k, i);
-            nnz_layer[k] = std::max(nnz_layer[k], nnz[r]);
-            nnz_all = std::max(nnz_all, nnz[r]);
+                    if ((f1_idx[r][t] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: %s has an index out of range", k, i, mul_name);
+            if (!dev_in && gates)
+                for (uint64_t t = 0; t < add_nnz[r]; ++t)
+                    if ((add_idx[r][t] >> (3 * dim)) != 0) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: add has an index out of range", k, i);
+            const uint64_t longest = gates ? std::max(nnz[r], add_nnz[r]) : nnz[r];
+            nnz_layer[k] = std::max(nnz_layer[k], longest);
+            nnz_all = std::max(nnz_all, longest);
         }
     const bool one_block = scd::policy(scd::kPolBatch) != 0 && scd::gkr_batch_shape_fits(dim, nnz_all);
     const uint64_t cells_bytes = one_block ? 0 : ((uint64_t)n * scd::kBsGkrCellBytes) << dim;
@@ -141,12 +177,20 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
     if (sc_device_count() <= 0) return sc_internal_fail(SC_ERR_HIP, "no HIP device visible: libsumcheck_hip has no CPU fallback");
 
     // ---- the image: records | output pointers | index flags; behind it on the device the staged host arrays and outputs, then the cells ----
-    const size_t rec_off = 0, out_off = rec_off + round_up(total * sizeof(scd::GkrBatchInst), 256), flag_off = out_off + round_up(total * sizeof(void *), 256);
-    const size_t image_bytes = flag_off + round_up(total * 4, 256);
+    const size_t rec_off = 0, out_off = rec_off + round_up((add_idx ? 2 : 1) * total * sizeof(scd::GkrBatchInst), 256), flag_off = out_off + round_up(total * sizeof(void *), 256);
+    const size_t n_rec = gates ? 2 * total : total; // (gate form: the ADD records behind the MUL records, and their flags behind the MUL records' flags)
+    const size_t image_bytes = flag_off + round_up(n_rec * 4, 256);
     StageMap st;
     st.align = 256;
     st.base = image_bytes;
-    std::vector<size_t> offs; // host arrays: per record idx, vals; then per instance f2, f3
+    std::vector<size_t> offs, add_offs; // host arrays: per record idx, vals; then per instance f2, f3; (gate form) per record the ADD list's idx, vals
+    if (!dev_in && gates) {
+        add_offs.resize(2 * total);
+        for (size_t r = 0; r < total; ++r) {
+            add_offs[2 * r + 0] = add_nnz[r] ? st.add(add_idx[r], (size_t)add_nnz[r] * 8) : st.base;
+            add_offs[2 * r + 1] = add_nnz[r] ? st.add(add_vals[r], (size_t)add_nnz[r] * 32) : st.base;
+        }
+    }
     if (!dev_in) {
         offs.resize(2 * total + 2 * (size_t)n);
         for (size_t r = 0; r < total; ++r) {
@@ -188,22 +232,31 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
                     R.f2 = R.f3 = reinterpret_cast<const uint4 *>(d_out(r - n)); // the layer before, on both sides
                 }
                 outp[r] = d_out(r);
+                if (gates) { // (the ADD record: its list; the tables are read through the MUL record)
+                    scd::GkrBatchInst &D = rec[total + r];
+                    D = R;
+                    D.nnz = add_nnz[r];
+                    D.idx = dev_in ? add_idx[r] : reinterpret_cast<const uint64_t *>(d_up + add_offs[2 * r + 0]);
+                    D.vals = reinterpret_cast<const uint4 *>(dev_in ? reinterpret_cast<const char *>(add_vals[r]) : d_up + add_offs[2 * r + 1]);
+                }
             }
         HIP_TRY(hipMemcpyAsync(d_up, a.h_pin, image_bytes, hipMemcpyHostToDevice, a.stream));
         for (const StageMap::Item &it : st.items) HIP_TRY(hipMemcpyAsync(d_up + it.off, it.src, it.bytes, hipMemcpyHostToDevice, a.stream));
         const scd::GkrBatchInst *d_rec = reinterpret_cast<const scd::GkrBatchInst *>(d_up + rec_off);
         // device-resident lists: an index out of range is found here, over all layers, in front of the first launch that follows indices
         if (dev_in)
-            for (size_t first = 0; first < total; first += 1u << 30) { // (the check's n is 32 bits wide)
-                const uint32_t count = (uint32_t)std::min<size_t>(total - first, 1u << 30);
+            for (size_t first = 0; first < n_rec; first += 1u << 30) { // (the check's n is 32 bits wide)
+                const uint32_t count = (uint32_t)std::min<size_t>(n_rec - first, 1u << 30);
                 HIP_TRY(scd::launch_batch_gkr_idx_range(d_rec + first, count, dim, reinterpret_cast<uint32_t *>(d_up + flag_off) + first, a.stream));
             }
         if (dev_in) {
-            HIP_TRY(hipMemcpyAsync(a.h_pin + flag_off, d_up + flag_off, total * 4, hipMemcpyDeviceToHost, a.stream));
+            HIP_TRY(hipMemcpyAsync(a.h_pin + flag_off, d_up + flag_off, n_rec * 4, hipMemcpyDeviceToHost, a.stream));
             HIP_TRY(hipStreamSynchronize(a.stream));
             const uint32_t *fl = reinterpret_cast<const uint32_t *>(a.h_pin + flag_off);
-            for (size_t r = 0; r < total; ++r)
-                if (fl[r]) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: f1 has an index out of range", (uint32_t)(r / n), (uint32_t)(r % n));
+            for (size_t r = 0; r < total; ++r) { // (the lowest failing (layer, instance) decides, mul before add)
+                if (fl[r]) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: %s has an index out of range", (uint32_t)(r / n), (uint32_t)(r % n), mul_name);
+                if (gates && fl[total + r]) return sc_internal_fail(SC_ERR_BAD_ARG, "layer %u instance %u: add has an index out of range", (uint32_t)(r / n), (uint32_t)(r % n));
+            }
         }
         scd::GkrEvalLayersArgs A;
         std::memset(&A, 0, sizeof(A));
@@ -213,7 +266,8 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
             A.inst = d_rec;
             A.out = reinterpret_cast<uint4 *const *>(d_up + out_off);
             A.n_layers = n_layers;
-            HIP_TRY(scd::launch_batch_gkr_eval_layers(A, a.stream));
+            if (gates) HIP_TRY(scd::launch_batch_gkr_gates_eval_layers(scd::GkrGatesEvalArgs{A, d_rec + total}, a.stream));
+            else HIP_TRY(scd::launch_batch_gkr_eval_layers(A, a.stream));
         } else {
             A.cells = reinterpret_cast<uint64_t *>(d_up + cells_off);
             A.n_layers = 1;
@@ -221,7 +275,8 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
                 A.inst = d_rec + (size_t)k * n;
                 A.out = reinterpret_cast<uint4 *const *>(d_up + out_off) + (size_t)k * n;
                 HIP_TRY(hipMemsetAsync(A.cells, 0, (size_t)cells_bytes, a.stream));
-                HIP_TRY(scd::launch_batch_gkr_eval_cells(A, nnz_layer[k], a.stream));
+                if (gates) HIP_TRY(scd::launch_batch_gkr_gates_eval_cells(scd::GkrGatesEvalArgs{A, d_rec + total + (size_t)k * n}, nnz_layer[k], a.stream));
+                else HIP_TRY(scd::launch_batch_gkr_eval_cells(A, nnz_layer[k], a.stream));
             }
         }
         if (!dev_in)
@@ -242,6 +297,8 @@ extern "C" int sc_gkr_layers_eval_batch(uint32_t n, uint32_t dim, uint32_t n_lay
         if (rc) return sc_internal_fail(rc, "%s", why.c_str());
     }
     if (rc) return rc;
-    scd::plan_hit(one_block ? scd::kPlanBatchGkrEvalLayersOneBlock : scd::kPlanBatchGkrEvalLayersCells);
+    if (gates) scd::plan_hit(one_block ? scd::kPlanBatchGkrGatesEvalOneBlock : scd::kPlanBatchGkrGatesEvalCells);
+    else scd::plan_hit(one_block ? scd::kPlanBatchGkrEvalLayersOneBlock : scd::kPlanBatchGkrEvalLayersCells);
     return SC_OK;
 }
+} // namespace

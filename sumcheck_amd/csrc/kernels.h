@@ -409,6 +409,31 @@ struct BatchGkrSlicesArgs {
 // points 2: a second pair of half tables for g2, alpha folded into g's low half and beta into g2's; a term's weight is
 // lo[z_lo] hi[z_hi] + lo2[z_lo] hi2[z_hi], canonical -- the number of terms per cell and with it the lanes' bound are those of points 1.
 hipError_t launch_batch_gkr_slices_phase(int phase, BatchGkrSlicesArgs args, uint64_t nnz_max, hipStream_t stream, int points = 1);
+// The gate form of the batched interactive GKR rounds (kernels_batch_gkr_gates.hip: sc_gkr_gates_*): a layer of multiplication AND addition
+// gates, W_out[z] = sum_MUL v f2[x] f3[y] + sum_ADD v (f2[x] + f3[y]).  Both phases are a sumcheck over three tables and two products,
+// t0 t1 + t2 (coefficients one, D = 3), in k_batch_round's work areas with U = 3:
+//   k_batch_gkr_gates_phase<1>  E (eq(g, .), or alpha eq(g, .) + beta eq(g2, .)); area A: t0 = f2, t1 = H1, t2 = H2 with
+//                               H1[x] = sum_MUL E[z] v f3[y] + sum_ADD E[z] v,  H2[x] = sum_ADD E[z] v f3[y];
+//   k_batch_gkr_gates_phase<2>  f2(u) out of area A's t0 as k_batch_gkr_phase<2> binds it (kept in f2u[i]); area B: t0 = f3, t1 = T1, t2 = T2 with
+//                               T1[y] = f2(u) sum_MUL E[z] eq(u,x) v + sum_ADD E[z] eq(u,x) v,  T2[y] = f2(u) sum_ADD E[z] eq(u,x) v.
+// One block per instance, two passes over ONE array of cells (128 B x 2^dim of LDS, as k_batch_gkr_phase); dim <= kGkrBatchMaxDim and each
+// list <= kGkrBatchMaxNnzPerCell x 2^dim, so a cell's 64-bit lane takes at most 2^16 terms of 32-bit limbs.
+struct GkrGatesInst { // device memory, one per instance; every pointer is device memory that is only read
+    const uint64_t *mul_idx, *add_idx; // indices (z, x, y) of the two lists: z in the low dim bits
+    const uint4 *mul_vals, *add_vals;
+    const uint4 *f2, *f3; // 2^dim entries each
+    const uint4 *g;       // dim elements
+    uint64_t mul_nnz, add_nnz;
+};
+struct BatchGkrGatesArgs {
+    const GkrGatesInst *inst;   // device, n records
+    int32_t *work_a, *work_b;   // device: n x 3 x 2 x 2^dim slots each (phase 1 writes A; phase 2 reads A and writes B)
+    const uint4 *u;             // as in BatchGkrPhaseArgs
+    uint4 *f2u;                 // device: n elements (phase 2 writes)
+    uint32_t n, dim;
+    const uint4 *g2, *coef;     // points = 2 only: as in BatchGkrPhaseArgs
+};
+hipError_t launch_batch_gkr_gates_phase(int phase, const BatchGkrGatesArgs &args, hipStream_t stream, int points);
 // The values of GKR circuit layers (kernels_batch_gkr_eval_layers.hip: sc_gkr_layers_eval_batch): per instance i and layer k
 //     W_k[z] = sum over the non-zeros (z | x << dim | y << 2 dim, v) of layer k's list of  v * A[x] * B[y],
 // with (A, B) = (f2, f3) of the record for layer 0 and (W_{k-1}, W_{k-1}) for every later layer.  inst: n_layers x n records, layer-major
@@ -431,6 +456,16 @@ struct GkrEvalLayersArgs {
 };
 hipError_t launch_batch_gkr_eval_layers(GkrEvalLayersArgs args, hipStream_t stream);                 // (the dynamic LDS: 128 B x 2^dim, at most 64 KB)
 hipError_t launch_batch_gkr_eval_cells(GkrEvalLayersArgs args, uint64_t nnz_max, hipStream_t stream); // terms + fold of one layer
+// ... with an ADD list beside every MUL list (kernels_batch_gkr_gates.hip: sc_gkr_gates_layers_eval_batch): W_out[z] = sum_MUL v A[x] B[y] +
+// sum_ADD v (A[x] + B[y]), both lists into the same cells.  base.inst: the MUL records (with the tables f2 / f3), add: the ADD records in
+// the same order (idx, vals and nnz are read); mul_nnz + add_nnz < 2^31 per (layer, instance).  The one-block form is ONE launch for all
+// layers; the cells form is two terms launches and a fold per layer behind the caller's zeroing.
+struct GkrGatesEvalArgs {
+    GkrEvalLayersArgs base;
+    const GkrBatchInst *add;
+};
+hipError_t launch_batch_gkr_gates_eval_layers(GkrGatesEvalArgs args, hipStream_t stream);
+hipError_t launch_batch_gkr_gates_eval_cells(GkrGatesEvalArgs args, uint64_t nnz_max, hipStream_t stream); // nnz_max: the layer's longest list of either kind
 int tail_max_resident_blocks(int device); // co-resident blocks of the tail kernel (0: unknown -> the tail kernel is not used)
 uint32_t wait_spins_default(); // bound of the device-side polls for a challenge (sc_set_policy("wait_spins", n) overrides it: tests)
 
@@ -451,6 +486,7 @@ enum PolicyKey {
     kPolBatch,            // "batch"              sc_ml_prove_batch, sc_gkr_prove_batch: 0 always the serial plan; 1 the batched kernel from the measured crossover on; 2 the batched kernel for every n (tests, A/B runs)
     kPolLagSingle,        // "lag_single"         tables that only single-table products name skip this many big rounds after the first (0: off .. 4): class sums stand in for them (lag_index.hpp)
     kPolBatchSlices,      // "batch_slices"       sc_batch_prover_init, sc_gkr_batch_prover_init (dim 10 .. 16): 1 shapes beyond one block's LDS (to 2^16 entries) run their first rounds sliced over several blocks per instance (batch_slices.hpp); 0 they take the serial plan
+    kPolGkrGatesFused,    // "gkr_gates_fused"    sc_gkr_gates_init_batch: 1 shapes of one block per instance run k_batch_gkr_gates_phase (batch.gkr_gates_one_block); 0 every handle is composed of three multiplication-only instances per instance (batch.gkr_gates_composed)
     kPolCount
 };
 int64_t policy(int key);
@@ -490,6 +526,10 @@ enum Plan {
     kPlanResidentRounds,      // ... k_tail_rounds
     kPlanBatchGkrEvalLayersOneBlock, // sc_gkr_layers_eval_batch: k_batch_gkr_eval_layers, one block per instance, ONE launch for all layers (dim <= 9, every nnz <= 64 x 2^dim, policy "batch" != 0); counted once per successful call
     kPlanBatchGkrEvalLayersCells,    // ... per layer a zeroing of the cells, k_batch_gkr_eval_terms and k_batch_gkr_eval_fold on one stream (every other shape)
+    kPlanBatchGkrGatesOneBlock, // a round call on a handle of sc_gkr_gates_init_batch: k_batch_round (three tables, two products) over the work areas k_batch_gkr_gates_phase<1|2> fill (dim <= 9, each list <= 64 x 2^dim, policy "batch" != 0, policy "gkr_gates_fused" = 1); counted once per round call
+    kPlanBatchGkrGatesComposed, // ... an inner sc_gkr_batch_prover of 3 n multiplication-only instances (MUL, f2, f3), (ADD, f2, 1), (ADD, 1, f3) on a plan of its own, their messages added on the host (every other shape, or "gkr_gates_fused" = 0); counted once per round call
+    kPlanBatchGkrGatesEvalOneBlock, // sc_gkr_gates_layers_eval_batch: k_batch_gkr_gates_eval_layers, one block per instance, ONE launch for all layers (dim <= 9, every list of either kind <= 64 x 2^dim, policy "batch" != 0); counted once per successful call
+    kPlanBatchGkrGatesEvalCells,    // ... per layer a zeroing of the cells, k_batch_gkr_gates_eval_terms over the MUL and over the ADD lists, k_batch_gkr_gates_eval_fold on one stream (every other shape)
     kPlanShardedRcclDirect,   // sharded rounds: ncclAllReduce into the host-mapped page
     kPlanShardedRcclPublish,  // ... all-reduce + publish kernel
     kPlanShardedHost,         // ... the caller's host transport

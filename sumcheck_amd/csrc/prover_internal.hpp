@@ -330,6 +330,16 @@ void batch_state_head(const std::vector<std::vector<sch::Fr>> &rand, uint32_t in
 // to the caller's `out`; the caller holds the device gate
 int batch_export_out(const int32_t *work, uint32_t first, uint32_t count, uint32_t n_tables, uint32_t nv, uint32_t bound, const uint4 *d_chal_or_null, uint32_t chal_shared, char *d_exp,
                      char *h_exp, void *out, hipStream_t stream);
+// ---- gkr_gates.hip: the gate form of the GKR batch handle (sc_gkr_gates_*).  A handle built there is a sc_gkr_batch_prover that holds
+// nothing but a GkrGates; gkr_batch_rounds.hip forwards such a handle's round, finish, state, reset and free calls ----
+struct GkrGates;
+sc_gkr_batch_prover *gkr_gates_wrap(GkrGates *g); // (gkr_batch_rounds.hip) null: out of host memory
+GkrGates *gkr_gates_of(sc_gkr_batch_prover *bp);  // (gkr_batch_rounds.hip) null for a handle of the older inits
+void gkr_gates_destroy(GkrGates *g);
+int gkr_gates_prove_round(GkrGates *g, const uint64_t *r_or_null, uint32_t r_shared, uint64_t *out_evals);
+int gkr_gates_finish(GkrGates *g, const uint64_t *r, uint32_t r_shared, uint64_t *out_uv_or_null, uint64_t *out_final_or_null);
+int gkr_gates_state(GkrGates *g, uint32_t instance, uint64_t *randomness, uint32_t *n_randomness, uint64_t *tables_out, uint32_t *round);
+int gkr_gates_reset(GkrGates *g);
 // ---- gkr.hip ----
 int sc_internal_gkr_dense_table(int phase, const uint64_t *d_idx, const void *d_vals, uint64_t nnz, uint32_t dim, const void *d_f3, const uint64_t *g, const uint64_t *u_or_null,
                                 void *d_out); // one dense table of a GKR proof by sc_gkr_prove's route, device-resident inputs

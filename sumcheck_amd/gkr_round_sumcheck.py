@@ -218,6 +218,39 @@ class GKRRoundSumcheckSubClaim:  # data_structures.rs:22-31
         return out
 
 
+    def verify_subclaim_gates(self, mul_f1: SparseMultilinearExtension, add_f1: SparseMultilinearExtension, f2: DenseMultilinearExtension, f3: DenseMultilinearExtension,
+                              g, g2=None, alpha=None, beta=None) -> bool:
+        """verify_subclaim for a round proved in gate form: M f2(u) f3(v) + A (f2(u) + f3(v)) against expected_evaluation, M and A the
+        E-weighted extensions of the two lists at (u, v)"""
+        coeffs = None if g2 is None else [np.stack([_np64(alpha).reshape(4), _np64(beta).reshape(4)])]
+        return GKRRoundSumcheckSubClaim.verify_subclaim_gates_batch([self], [mul_f1], [add_f1], [f2], [f3], [g], None if g2 is None else [g2], coeffs)[0]
+
+    @staticmethod
+    def verify_subclaim_gates_batch(subclaims: Sequence["GKRRoundSumcheckSubClaim"], mul_f1s, add_f1s, f2s, f3s, gs, g2s=None, coeffs=None) -> List[bool]:
+        """n subclaims of rounds proved in gate form (GKRRoundSumcheck.prover_init_batch_gates), from existing calls only:
+        GKRRoundSumcheck.evaluate_subclaims_batch per list and per point, then M f2(u) f3(v) + A (f2(u) + f3(v)) in host field arithmetic,
+        with M = alpha mul(g,u,v) + beta mul(g2,u,v) and A likewise (one point: M = mul(g,u,v))."""
+        n = len(subclaims)
+        assert len(mul_f1s) == n and len(add_f1s) == n and len(f2s) == n and len(f3s) == n and len(gs) == n, "one mul, add, f2, f3 and g per subclaim"
+        assert (g2s is None) == (coeffs is None) and (g2s is None or (len(g2s) == n and len(coeffs) == n)), "g2s and coeffs come together, one per subclaim"
+        if n == 0:
+            return []
+        uv = np.stack([np.concatenate([_np64(c.u).reshape(-1, 4), _np64(c.v).reshape(-1, 4)]) for c in subclaims])
+        ev = {(k, pt): GKRRoundSumcheck.evaluate_subclaims_batch(f1s, f2s, f3s, pts, uv)
+              for k, f1s in (("mul", mul_f1s), ("add", add_f1s)) for pt, pts in ((0, gs), (1, g2s)) if pts is not None}
+        out = []
+        for i, c in enumerate(subclaims):
+            w = {}
+            for k in ("mul", "add"):
+                w[k] = field.to_int(ev[k, 0][i, 0])
+                if g2s is not None:
+                    ab = _np64(coeffs[i]).reshape(2, 4)
+                    w[k] = (field.to_int(ab[0]) * w[k] + field.to_int(ab[1]) * field.to_int(ev[k, 1][i, 0])) % field.P
+            f2u, f3v = field.to_int(ev["mul", 0][i, 1]), field.to_int(ev["mul", 0][i, 2])
+            out.append((w["mul"] * f2u % field.P * f3v + w["add"] * (f2u + f3v)) % field.P == field.to_int(c.expected_evaluation))
+        return out
+
+
 def _second_point(g2s, coeffs, n: int, dim: int):
     """the two-point form's extra arguments -> None (one-point form), or (n arrays (dim, 4), one array (n, 2, 4))"""
     if (g2s is None) != (coeffs is None):
@@ -252,6 +285,46 @@ def _verify_phase(rng: Blake2b512Rng, msgs: Sequence[ProverMsg], dim: int, asser
             raise SumcheckError(8, "Prover message is not consistent with the claim.")
         expected = field.to_int(interpolate_uni_poly(ev, rs[i]))
     return np.stack(rs) if rs else np.zeros((0, 4), np.uint64), field.from_int(expected)
+
+
+def _gates_args(n: int, dim: int, mul_f1s, add_f1s, f2s, f3s, gs, second):
+    """the argument arrays sc_gkr_gates_init_batch and sc_gkr_gates_next_batch share, from mul_idx to coef (lists None: six NULLs) -> (args, on_device)"""
+    lists = [] if mul_f1s is None else list(mul_f1s) + list(add_f1s)
+    assert mul_f1s is None or (len(mul_f1s) == n and len(add_f1s) == n), "one mul and one add list per instance"
+    ons = [m.on_device for m in lists + list(f2s) + list(f3s)]
+    dev = bool(ons) and all(ons)
+    assert dev or not any(ons), "mixing host and device inputs is not supported"
+    g_arr = []
+    for i in range(n):
+        assert f2s[i].num_vars == dim and f3s[i].num_vars == dim and all(f.num_vars == 3 * dim for f in lists), f"instance {i}: a batch has one dim"
+        g_arr.append(np.ascontiguousarray(_np64(gs[i]).reshape(-1, 4)))
+        assert g_arr[i].shape[0] == dim
+    if dev:
+        import torch
+        torch.cuda.current_stream(f2s[0].evaluations.device).synchronize()  # the library works on its own stream
+
+    def ptrs(vals):
+        return (C.c_void_p * max(n, 1))(*[C.cast(v, C.c_void_p) for v in vals])
+
+    wiring = []
+    for f1s in ((mul_f1s, add_f1s) if mul_f1s is not None else ()):
+        p = [f._ptrs() for f in f1s]
+        wiring += [ptrs([q[0] for q in p]), ptrs([q[1] for q in p]), (C.c_uint64 * max(n, 1))(*[f.nnz for f in f1s])]
+    if mul_f1s is None:
+        wiring = [None] * 6
+    g2_arr, coef = second if second is not None else (None, None)
+    args = (*wiring, ptrs([_dense_ptr(m) for m in f2s]), ptrs([_dense_ptr(m) for m in f3s]), ptrs([_ptr(a) for a in g_arr]),
+            None if g2_arr is None else ptrs([_ptr(a) for a in g2_arr]), None if coef is None else _ptr(coef))
+    return _Kept(args, (g_arr, g2_arr, coef, lists)), dev
+
+
+class _Kept(tuple):
+    """a tuple of ctypes arguments that also holds the numpy arrays their pointers were taken from"""
+
+    def __new__(cls, args, keep):
+        t = super().__new__(cls, args)
+        t.keep = keep
+        return t
 
 
 class GKRRoundSumcheck:
@@ -396,6 +469,27 @@ class GKRRoundSumcheck:
         return GKRBatchProverState(h, n, dim)
 
     @staticmethod
+    def prover_init_batch_gates(mul_f1s: Sequence[SparseMultilinearExtension], add_f1s: Sequence[SparseMultilinearExtension], f2s: Sequence[DenseMultilinearExtension],
+                                f3s: Sequence[DenseMultilinearExtension], gs, g2s=None, coeffs=None) -> "GKRBatchProverState":
+        """prover_init_batch for layers of multiplication AND addition gates (sc_gkr_gates_init_batch):
+            W_out[z] = sum over mul_f1 of v f2[x] f3[y] + sum over add_f1 of v (f2[x] + f3[y]),
+        claimed at gs[i], or -- with g2s and coeffs -- as alpha W_out(g) + beta W_out(g2).  The handle is driven as any other (2 dim calls of
+        prove_round, finish, reset, randomness); its finish returns f2(u), f3(v) and f3(v) T1(v) + T2(v), the value the verifier compares;
+        tables() is refused; later layers come through next_layer_gates.  Plans: dim <= 9 with each list <= 64 x 2^dim runs one block per
+        instance (batch.gkr_gates_one_block); every other shape, and every handle built under _lib.policy(gkr_gates_fused=0), is composed
+        of three multiplication-only instances per instance (batch.gkr_gates_composed) -- same bits."""
+        n = len(f2s)
+        assert len(mul_f1s) == n and len(add_f1s) == n and len(f3s) == n and len(gs) == n, "one mul, add, f2, f3 and g per instance"
+        dim = f2s[0].num_vars if n else 0
+        second = _second_point(g2s, coeffs, n, dim)
+        args, dev = _gates_args(n, dim, mul_f1s, add_f1s, f2s, f3s, gs, second)
+        h = C.c_void_p()
+        check(lib().sc_gkr_gates_init_batch(n, dim, *args, SC_TABLES_ON_DEVICE if dev else 0, C.byref(h)))
+        st = GKRBatchProverState(h, n, dim)
+        st._keep = args  # (nothing is read after init; kept only so that ctypes arrays outlive the call on every interpreter)
+        return st
+
+    @staticmethod
     def evaluate_layers_batch(f1_layers: Sequence[Sequence[SparseMultilinearExtension]], f2s: Sequence[DenseMultilinearExtension],
                               f3s: Sequence[DenseMultilinearExtension]) -> List[List[DenseMultilinearExtension]]:
         """The values of a circuit's layers for n instances of one dim, on the GPU (sc_gkr_layers_eval_batch): f1_layers[k][i] is the wiring
@@ -435,6 +529,49 @@ class GKRRoundSumcheck:
         nnz = (C.c_uint64 * total)(*[f.nnz for f in flat])
         check(lib().sc_gkr_layers_eval_batch(n, dim, n_layers, ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), nnz, ptrs([_dense_ptr(m) for m in f2s]),
                                              ptrs([_dense_ptr(m) for m in f3s]), SC_TABLES_ON_DEVICE if dev else 0, ptrs(out_ptrs)))
+        return [[DenseMultilinearExtension(dim, outs[k * n + i]) for i in range(n)] for k in range(n_layers)]
+
+    @staticmethod
+    def evaluate_layers_batch_gates(mul_layers: Sequence[Sequence[SparseMultilinearExtension]], add_layers: Sequence[Sequence[SparseMultilinearExtension]],
+                                    f2s: Sequence[DenseMultilinearExtension], f3s: Sequence[DenseMultilinearExtension]) -> List[List[DenseMultilinearExtension]]:
+        """evaluate_layers_batch for layers of multiplication AND addition gates (sc_gkr_gates_layers_eval_batch): mul_layers[k][i] and
+        add_layers[k][i] are the two wiring lists of layer k of instance i, and
+            out[0][i][z] = sum over mul of v f2s[i][x] f3s[i][y] + sum over add of v (f2s[i][x] + f3s[i][y])
+            out[k][i]    = the same over layer k's lists with out[k-1][i] on both sides.
+        Device tensors in give device tensors out, usable directly as the f2s / f3s of prover_init_batch_gates and next_layer_gates."""
+        n_layers, n = len(mul_layers), len(f2s)
+        assert len(add_layers) == n_layers and len(f3s) == n and all(len(layer) == n for layer in list(mul_layers) + list(add_layers)), "one mul and one add list per layer and instance"
+        if n == 0 or n_layers == 0:
+            check(lib().sc_gkr_gates_layers_eval_batch(n, 0, n_layers, None, None, None, None, None, None, None, None, 0, None))
+            return [[] for _ in range(n_layers)]
+        dim = f2s[0].num_vars
+        flat_m, flat_a = [f for layer in mul_layers for f in layer], [f for layer in add_layers for f in layer]
+        ons = [m.on_device for m in flat_m + flat_a + list(f2s) + list(f3s)]
+        dev = all(ons)
+        assert dev or not any(ons), "mixing host and device inputs is not supported"
+        for i in range(n):
+            assert f2s[i].num_vars == dim and f3s[i].num_vars == dim, f"instance {i}: a batch has one dim"
+        assert all(f.num_vars == 3 * dim for f in flat_m + flat_a), "a batch has one dim"
+        total = n_layers * n
+        if dev:
+            import torch
+            device = f2s[0].evaluations.device
+            outs = [torch.empty((1 << dim, 4), dtype=torch.int64, device=device) for _ in range(total)]
+            torch.cuda.current_stream(device).synchronize()  # the library works on its own stream
+            out_ptrs = [C.c_void_p(t.data_ptr()) for t in outs]
+        else:
+            outs = [np.empty((1 << dim, 4), dtype=np.uint64) for _ in range(total)]
+            out_ptrs = [_ptr(t) for t in outs]
+
+        def ptrs(vals):
+            return (C.c_void_p * len(vals))(*[C.cast(v, C.c_void_p) for v in vals])
+
+        lists = []
+        for flat in (flat_m, flat_a):
+            f1p = [f._ptrs() for f in flat]
+            lists += [ptrs([p[0] for p in f1p]), ptrs([p[1] for p in f1p]), (C.c_uint64 * total)(*[f.nnz for f in flat])]
+        check(lib().sc_gkr_gates_layers_eval_batch(n, dim, n_layers, *lists, ptrs([_dense_ptr(m) for m in f2s]), ptrs([_dense_ptr(m) for m in f3s]),
+                                                   SC_TABLES_ON_DEVICE if dev else 0, ptrs(out_ptrs)))
         return [[DenseMultilinearExtension(dim, outs[k * n + i]) for i in range(n)] for k in range(n_layers)]
 
     @staticmethod
@@ -531,6 +668,18 @@ class GKRBatchProverState:
         else:
             g2_arr, coef = second
             check(lib().sc_gkr_two_point_next_batch(*head, ptrs([_ptr(a) for a in g2_arr]), _ptr(coef), SC_TABLES_ON_DEVICE if dev else 0))
+
+    def next_layer_gates(self, f2s, f3s, gs, mul_f1s=None, add_f1s=None, g2s=None, coeffs=None) -> None:
+        """next_layer for a handle of prover_init_batch_gates (sc_gkr_gates_next_batch): mul_f1s and add_f1s both None keeps both lists,
+        both given is new wiring.  g2s and coeffs (both or neither) choose the layer's form.  An argument error leaves a proof in progress
+        exactly where it was."""
+        n, dim = self.n, self.dim
+        if (mul_f1s is None) != (add_f1s is None):
+            raise ValueError("mul_f1s and add_f1s come together (new wiring) or not at all (the handle's wiring is kept)")
+        assert len(f2s) == n and len(f3s) == n and len(gs) == n, "one f2, f3 and g per instance"
+        second = _second_point(g2s, coeffs, n, dim)
+        args, dev = _gates_args(n, dim, mul_f1s, add_f1s, f2s, f3s, gs, second)
+        check(lib().sc_gkr_gates_next_batch(self._h, *args, SC_TABLES_ON_DEVICE if dev else 0))
 
     def close(self) -> None:
         if self._h:
